@@ -7,12 +7,17 @@ WGC99(+TF+vW) + PBE, synthetic density (the converged fcc-Al 32^3 fixture tiled 
 seeded low-|k| perturbation, SURVEY.md §8d option A).  Inputs are resident in HBM before the timed
 region.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed in a separate profiling pass) and `cpu_baseline` (the oracle's op-for-op torch-CPU
-restatement of the reference path, timed on a bounded sample).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`).  A plain run does only what that figure needs: set-up, W warm-up steps, K timed steps.
+--full adds everything else, outside the timed region: `kernels` / `roofline` / `eval_roofline` (a
+separate HIP-event profiling pass, the device-copy ceiling), `reference_check` (E, mu and chi.grad against
+the reference's run of this workload; exit code 3 on a mismatch), `cpu_baseline` (the oracle's op-for-op
+torch-CPU restatement of the reference path, timed on a bounded sample), and on N > 1 ranks the parity
+against one GPU and the 512^3 one-GPU / N-GPU pair (`scale_512`).
+--dump-outputs DIR writes what the last timed step returned (see `dump_outputs`).
 """
 import argparse
 import json
@@ -384,6 +389,23 @@ def reference_check(n, cfg, dtype, E, mu, grad=None):
     return out
 
 
+def dump_outputs(d, E, mu, g, max_points=1 << 21):
+    """What the last timed step returned, as d/<name>.npy: `energy_terms` (float64, one entry per term of the engine's
+    term order, zero for terms not in the set), `mu` (float64) and `grad` (chi.grad in the step's precision; on N > 1
+    ranks rank 0's x-slab).  A gradient of more than `max_points` points is written at a fixed seeded sample of them
+    (`grad_index`: their flat indices, float64), which keeps the files of a 256^3 fp64 run near 32 MB."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'energy_terms.npy'), np.array(list(E.values()), dtype=np.float64))
+    np.save(os.path.join(d, 'mu.npy'), np.array([mu], dtype=np.float64))
+    flat = g.reshape(-1)
+    if flat.numel() <= max_points:
+        np.save(os.path.join(d, 'grad.npy'), g.cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(20240601).integers(0, flat.numel(), size=max_points))
+    np.save(os.path.join(d, 'grad.npy'), flat[torch.as_tensor(idx, device=g.device)].cpu().numpy())
+    np.save(os.path.join(d, 'grad_index.npy'), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -393,9 +415,15 @@ def main():
     ap.add_argument('--cfg', default='cfg3', choices=['cfg2', 'cfg3'])
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'],
                     help='f64: the reference precision (BASELINE metric); f32: the fp32 build (config 5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also profile the kernels, pin the result to the reference, time the CPU baseline and, on N > 1 ranks, '
+                         'the parity against one GPU and the 512^3 pair (all outside the timed region)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
     ap.add_argument('--cpu-sample-grid', type=int, default=128)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         launch_workers(a.gpus, sys.argv[1:])
@@ -535,93 +563,8 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / a.steps * 1e3
     evals_per_s = a.steps / dt                    # whole-job rate: all ranks work on the same n^3 system
-    n_fft = int(eng.query(0))
-    n_launch = int(eng.query(4))
-    n_ypass = float(eng.query(5))          # whole-spectrum y line passes actually executed
-    n_yfwd = int(eng.query(10))            # y-forward transforms that rode inside a yderiv launch
-    dev_ms = raw.query(3) or None          # begin .. end of the last evaluation on this rank's stream (HIP events); the
-                                           # persistent small-grid kernel's calls are not bracketed by events (reads 0)
-
-    # ---- per-kernel HIP-event profile (separate pass, not inside the timed region; events are recorded on the streams the
-    # kernels are launched on).  Durations are measured with the chains serialised on ONE stream: with the side streams
-    # on, kernels of different chains share the GPU and a launch's begin-to-end time is not that kernel's own cost
-    raw.set_option(1, 0)
-    raw.set_profiling(True)
-    nprof = 3
-    for _ in range(nprof):
-        step()
-    prof = raw.profile()
-    raw.set_profiling(False)
-    if os.environ.get('OFDFT_SIDE_STREAM') != '0':
-        raw.set_option(1, 1)
-    if world > 1 and ('ypass_send' in prof or 'ypass_recv' in prof):
-        # slab-decomposed path: the y passes read / write the exchange buffers; one class for the roofline
-        ys = [prof.pop(k) for k in ('ypass_send', 'ypass_recv') if k in prof]
-        prof['cpass_y'] = (sum(v[0] for v in ys), sum(v[1] for v in ys))
-    tot_ms = sum(v[0] for v in prof.values()) or 1.0
-    cab = class_alg_bytes(a.cfg, n, word, n_ypass, n_yfwd) if default_options else {}
-    # rocprofv3 FETCH_SIZE / WRITE_SIZE of the same command, committed under profiles/ by tools/profile.sh and stamped
-    # with the hash of the sources it profiled: used only when it belongs to THIS build (else traffic = null)
-    pmc, pmc_name, stamp = None, None, source_stamp()
-    if world == 1:
-        import glob
-        # pmc_traffic_rNN[_<grid>][_f32][_cfg2].json: the default workload has no tag; other single-GPU workloads that were profiled
-        # (tools/profile.sh <dir> --grid 512, ... --dtype f32 --grid 1024 --cfg cfg2) carry theirs
-        suffix = ('' if n == 256 else '_%d' % n) + ('' if a.dtype == 'f64' else '_f32') + ('' if a.cfg == 'cfg3' else '_' + a.cfg)
-        for fn in sorted(glob.glob(os.path.join(ROOT, 'profiles', 'pmc_traffic_r[0-9][0-9]%s.json' % suffix)), reverse=True):
-            with open(fn) as fh:
-                cand = json.load(fh)
-            if cand.get('source_stamp') == stamp:
-                pmc, pmc_name = cand, os.path.basename(fn)
-                break
-    kernels = {}
-    for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0]):
-        ent = {'ms_per_eval': round(v[0] / nprof, 4), 'launches_per_eval': v[1] // nprof, 'share': round(v[0] / tot_ms, 4)}
-        if cab.get(k):
-            gbs = cab[k] / world / (v[0] / nprof * 1e-3) / 1e9       # per GPU: a rank holds 1/world of every array
-            ent.update(alg_MB_per_eval=round(cab[k] / world / 1e6, 1), achieved_GBs=round(gbs, 1), frac=round(gbs / HBM_PEAK_GBS, 4))
-        if pmc and k in pmc.get('kernels', {}):
-            pk = pmc['kernels'][k]
-            ent['traffic_MB_per_eval'] = round(pk['launches'] * (pk['read_MB'] + pk['write_MB']) / pmc['evaluations'], 1)
-            if k == 'xfused_wgc' and 'alg_MB_per_eval' in ent:      # what the kernel tables cost on top of the spectra
-                ent['table_MB_per_eval'] = round(ent['traffic_MB_per_eval'] - ent['alg_MB_per_eval'], 1)
-        kernels[k] = ent
-    dom = max((k for k in prof if cab.get(k)), key=lambda k: prof[k][0], default=None)
-    roofline = None
-    if dom:
-        launches = prof[dom][1] / nprof
-        class_ms = prof[dom][0] / nprof
-        per_launch = cab[dom] / world / launches
-        ach = kernels[dom]['achieved_GBs']
-        traffic = None
-        if pmc and dom in pmc.get('kernels', {}):
-            pk = pmc['kernels'][dom]
-            traffic = int(round((pk['read_MB'] + pk['write_MB']) * 1e6))
-        roofline = {'bound': 'hbm', 'kernel': dom, 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': round(ach / HBM_PEAK_GBS, 4), 'traffic': traffic,
-                    'launches_per_eval': launches, 'avg_launch_ms': round(class_ms / launches, 5),
-                    'alg_bytes_per_launch': per_launch,
-                    'traffic_source': ('profiles/%s (source stamp %s): %s' % (pmc_name, stamp, pmc['source'])) if traffic else None,
-                    'note': 'the class with the largest share of the evaluation among all kernel classes; launch durations '
-                            'from a profiling pass with the chains serialised on one stream (the setting of the committed '
-                            'rocprofv3 summary); the timed region overlaps independent chains on side streams'}
-    alg, R, Cc = algorithmic_bytes(n, a.cfg, word)
-    measured_hbm = None
-    if pmc:       # rocprofv3 FETCH_SIZE / WRITE_SIZE of every kernel of the committed profile, per evaluation
-        measured_hbm = sum(k['launches'] * (k['read_MB'] + k['write_MB']) for k in pmc['kernels'].values()) / pmc['evaluations'] * 1e6
-    class_bytes = sum(cab[k] for k in prof if cab.get(k))        # algorithmic bytes of the kernel classes that ran
-    # the box's own streaming ceiling beside the 8 TB/s spec figure: device-to-device copy of 512 MiB, read + write
-    cp_a = torch.empty(64 * 1024 * 1024, dtype=torch.double, device=device)
-    cp_b = torch.empty_like(cp_a)
-    cp_b.copy_(cp_a)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(10):
-        cp_b.copy_(cp_a)
-    ev1.record()
-    torch.cuda.synchronize(device)
-    copy_gbs = 10 * 2 * cp_a.numel() * 8 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-    del cp_a, cp_b
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, E, mu, g)
 
     E_tot = sum(E.values())
     out = {
@@ -635,77 +578,170 @@ def main():
                    ('x-slab decomposition over %d GPUs, 6 exchanges as RCCL all-to-alls pipelined by kz chunks inside each of two overlapped chains + 2 small all-reduces per evaluation' % world)
                    if transport == 'collective' else
                    ('x-slab decomposition over %d GPUs, library-issued peer copies over hipIpc mappings (6 exchanges pipelined by kz chunks inside each of two overlapped chains) + 2 mailbox reductions per evaluation, no collective call' % world)},
-        'roofline': roofline,
-        'eval_roofline': eval_roofline_block(alg, ms_per_step, world, measured_hbm, class_bytes, {
-            'measured_copy_GBs': round(copy_gbs, 1), 'ffts_executed': n_fft, 'kernel_launches': n_launch,
-            'device_ms_last_eval': round(dev_ms, 4) if dev_ms is not None else None}),
-        'kernels': kernels,
-        'energy_Ha': E_tot, 'mu': mu, 'source_stamp': stamp,
+        'energy_Ha': E_tot, 'mu': mu,
     }
     if transport_probe:
         out['transport'] = {'used': transport, 'probe': transport_probe}
-    if world > 1:
-        # what crosses the fabric per evaluation and rank: every transposed spectrum leaves (world-1)/world
-        # of its slab; with the ipc transport the profiling pass also times the scatter kernels (all links driven at once) and
-        # the epoch waits (peer skew + delivery)
-        ntr = 19 if a.cfg == 'cfg3' else 6
-        sent = ntr * (Cc / world) * (world - 1) / world
-        ex = {'spectra_transposed_per_eval': ntr, 'sent_MB_per_rank_per_eval': round(sent / 1e6, 1),
-              'MB_per_link_per_eval': round(sent / (world - 1) / 1e6, 1)}
-        if 'ipc_scatter' in kernels:
-            ms = kernels['ipc_scatter']['ms_per_eval']
-            ex.update(scatter_ms_per_eval=ms, scatter_GBs_per_rank=round(sent / (ms * 1e-3) / 1e9, 1) if ms else None,
-                      scatter_GBs_per_link=round(sent / (world - 1) / (ms * 1e-3) / 1e9, 1) if ms else None,
-                      wait_ms_per_eval=kernels.get('ipc_sync', {}).get('ms_per_eval'))
-        out['exchange'] = ex
-    # (chi.grad of the timed call itself; on slabs every rank contributes its planes' share of the statistics)
-    gst = grad_stats(g) if world == 1 else grad_stats(g, dist, eng.plan.x_range().start, n ** 3)
-    chk = reference_check(n, a.cfg, a.dtype, E_tot, mu, gst)
-    out['reference_check'] = chk
-    if world > 1 and rank == 0 and os.environ.get('OFDFT_BENCH_NO_PARITY') != '1':
-        # the slab-decomposed result against ONE engine on the whole grid of this rank's GPU (outside the timed region)
-        one = Engine((n, n, n), device, dtype=tdtype).set_cell(torch.as_tensor(box)).set_terms(names)
-        E1, mu1, g1 = one.energy_grad_chi(torch.as_tensor(chi_full, dtype=tdtype, device=device), n_elec,
-                                          torch.as_tensor(vext_full, dtype=tdtype, device=device))
-        gs = g1[eng.plan.x_range()]
-        out['parity_vs_single_gpu'] = {
-            'rel_dE': abs(E_tot - sum(E1.values())) / abs(sum(E1.values())), 'rel_dmu': abs(mu - mu1) / abs(mu1),
-            'grad_slab_max_rel': float((g - gs).abs().max() / gs.abs().max())}
-        one.close()
-        del g1, gs
-    if world > 1:
-        out['exchange']['xchg_chunks'] = eng.stages.nchunks
-    if world > 1 and (n == 256 or os.environ.get('OFDFT_BENCH_SCALE_ANY_GRID') == '1') and a.cfg == 'cfg3' and os.environ.get('OFDFT_BENCH_NO_SCALE512') != '1':
-        # the 512^3 one-GPU / N-GPU pair of the north star, inside this very command (the driver passes no --grid)
-        working = [tr for tr, v in (transport_probe or {}).items() if not v.get('failed') and not v.get('disagrees_with_collective')]
-        eng.close(sync_peers=True)
-        del g
-        if rank == 0:       # the primary line survives whatever happens in the optional block (a copy on stderr; stdout stays ONE line)
-            sys.stderr.write('bench.py: 256^3 line before the optional scale_512 block: %s\n' % json.dumps(out))
-            sys.stderr.flush()
-        try:
-            sc = scale_512_block(dist, device, backend, rank, world, tdtype, names, box, chi_full, vext_full, n_elec, E_tot, working)
-        except Exception as e:  # noqa: BLE001  (a failure every rank shares, e.g. memory: the 256^3 line above must survive it)
-            sc = {'error': repr(e)[:300]}
-        if rank == 0:
-            out['scale_512'] = sc
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cb = cpu_baseline(a.cpu_sample_grid, n)
-        if cb['full']:
-            f = cb['full']
-            out['cpu_baseline'] = {
-                'value': round(1.0 / f['best'], 5), 'unit': 'evals/s', 'cores': cb['cores'], 'kind': 'port',
-                'sample': '%d^3 grid (the full workload), same terms, best of %d after 1 warm-up (%.2f s/eval; first call '
-                          '%.1f s incl. WGC99 kernel generation); %d^3 pre-sample: %.3f s/eval'
-                          % (f['n'], max(f['count'], 1), f['best'], f['first'], cb['n'], cb['best'])}
-        else:
-            scale = (a.cpu_sample_grid / n) ** 3
-            out['cpu_baseline'] = {
-                'value': round(scale / cb['best'], 5), 'unit': 'evals/s', 'cores': cb['cores'], 'kind': 'port',
-                'sample': '%d^3 grid, same terms, best of %d after 1 warm-up (%.2f s/eval; first call %.1f s incl. WGC99 '
-                          'kernel generation); value = measured %d^3 rate x (%d/%d)^3 grid-point scaling to %d^3'
-                          % (cb['n'], cb['count'], cb['best'], cb['first'], cb['n'], cb['n'], n, n),
-                'measured_evals_per_s_on_sample': round(1.0 / cb['best'], 4)}
+    chk = None
+    if a.full:
+        n_fft = int(eng.query(0))
+        n_launch = int(eng.query(4))
+        n_ypass = float(eng.query(5))          # whole-spectrum y line passes actually executed
+        n_yfwd = int(eng.query(10))            # y-forward transforms that rode inside a yderiv launch
+        dev_ms = raw.query(3) or None          # begin .. end of the last evaluation on this rank's stream (HIP events); the
+                                               # persistent small-grid kernel's calls are not bracketed by events (reads 0)
+
+        # ---- per-kernel HIP-event profile (separate pass, not inside the timed region; events are recorded on the streams the
+        # kernels are launched on).  Durations are measured with the chains serialised on ONE stream: with the side streams
+        # on, kernels of different chains share the GPU and a launch's begin-to-end time is not that kernel's own cost
+        raw.set_option(1, 0)
+        raw.set_profiling(True)
+        nprof = 3
+        for _ in range(nprof):
+            step()
+        prof = raw.profile()
+        raw.set_profiling(False)
+        if os.environ.get('OFDFT_SIDE_STREAM') != '0':
+            raw.set_option(1, 1)
+        if world > 1 and ('ypass_send' in prof or 'ypass_recv' in prof):
+            # slab-decomposed path: the y passes read / write the exchange buffers; one class for the roofline
+            ys = [prof.pop(k) for k in ('ypass_send', 'ypass_recv') if k in prof]
+            prof['cpass_y'] = (sum(v[0] for v in ys), sum(v[1] for v in ys))
+        tot_ms = sum(v[0] for v in prof.values()) or 1.0
+        cab = class_alg_bytes(a.cfg, n, word, n_ypass, n_yfwd) if default_options else {}
+        # rocprofv3 FETCH_SIZE / WRITE_SIZE of the same command, committed under profiles/ by tools/profile.sh and stamped
+        # with the hash of the sources it profiled: used only when it belongs to THIS build (else traffic = null)
+        pmc, pmc_name, stamp = None, None, source_stamp()
+        if world == 1:
+            import glob
+            # pmc_traffic_rNN[_<grid>][_f32][_cfg2].json: the default workload has no tag; other single-GPU workloads that were profiled
+            # (tools/profile.sh <dir> --grid 512, ... --dtype f32 --grid 1024 --cfg cfg2) carry theirs
+            suffix = ('' if n == 256 else '_%d' % n) + ('' if a.dtype == 'f64' else '_f32') + ('' if a.cfg == 'cfg3' else '_' + a.cfg)
+            for fn in sorted(glob.glob(os.path.join(ROOT, 'profiles', 'pmc_traffic_r[0-9][0-9]%s.json' % suffix)), reverse=True):
+                with open(fn) as fh:
+                    cand = json.load(fh)
+                if cand.get('source_stamp') == stamp:
+                    pmc, pmc_name = cand, os.path.basename(fn)
+                    break
+        kernels = {}
+        for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0]):
+            ent = {'ms_per_eval': round(v[0] / nprof, 4), 'launches_per_eval': v[1] // nprof, 'share': round(v[0] / tot_ms, 4)}
+            if cab.get(k):
+                gbs = cab[k] / world / (v[0] / nprof * 1e-3) / 1e9       # per GPU: a rank holds 1/world of every array
+                ent.update(alg_MB_per_eval=round(cab[k] / world / 1e6, 1), achieved_GBs=round(gbs, 1), frac=round(gbs / HBM_PEAK_GBS, 4))
+            if pmc and k in pmc.get('kernels', {}):
+                pk = pmc['kernels'][k]
+                ent['traffic_MB_per_eval'] = round(pk['launches'] * (pk['read_MB'] + pk['write_MB']) / pmc['evaluations'], 1)
+                if k == 'xfused_wgc' and 'alg_MB_per_eval' in ent:      # what the kernel tables cost on top of the spectra
+                    ent['table_MB_per_eval'] = round(ent['traffic_MB_per_eval'] - ent['alg_MB_per_eval'], 1)
+            kernels[k] = ent
+        dom = max((k for k in prof if cab.get(k)), key=lambda k: prof[k][0], default=None)
+        roofline = None
+        if dom:
+            launches = prof[dom][1] / nprof
+            class_ms = prof[dom][0] / nprof
+            per_launch = cab[dom] / world / launches
+            ach = kernels[dom]['achieved_GBs']
+            traffic = None
+            if pmc and dom in pmc.get('kernels', {}):
+                pk = pmc['kernels'][dom]
+                traffic = int(round((pk['read_MB'] + pk['write_MB']) * 1e6))
+            roofline = {'bound': 'hbm', 'kernel': dom, 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': round(ach / HBM_PEAK_GBS, 4), 'traffic': traffic,
+                        'launches_per_eval': launches, 'avg_launch_ms': round(class_ms / launches, 5),
+                        'alg_bytes_per_launch': per_launch,
+                        'traffic_source': ('profiles/%s (source stamp %s): %s' % (pmc_name, stamp, pmc['source'])) if traffic else None,
+                        'note': 'the class with the largest share of the evaluation among all kernel classes; launch durations '
+                                'from a profiling pass with the chains serialised on one stream (the setting of the committed '
+                                'rocprofv3 summary); the timed region overlaps independent chains on side streams'}
+        alg, R, Cc = algorithmic_bytes(n, a.cfg, word)
+        measured_hbm = None
+        if pmc:       # rocprofv3 FETCH_SIZE / WRITE_SIZE of every kernel of the committed profile, per evaluation
+            measured_hbm = sum(k['launches'] * (k['read_MB'] + k['write_MB']) for k in pmc['kernels'].values()) / pmc['evaluations'] * 1e6
+        class_bytes = sum(cab[k] for k in prof if cab.get(k))        # algorithmic bytes of the kernel classes that ran
+        # the box's own streaming ceiling beside the 8 TB/s spec figure: device-to-device copy of 512 MiB, read + write
+        cp_a = torch.empty(64 * 1024 * 1024, dtype=torch.double, device=device)
+        cp_b = torch.empty_like(cp_a)
+        cp_b.copy_(cp_a)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(10):
+            cp_b.copy_(cp_a)
+        ev1.record()
+        torch.cuda.synchronize(device)
+        copy_gbs = 10 * 2 * cp_a.numel() * 8 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+        del cp_a, cp_b
+
+        out.update({
+            'roofline': roofline,
+            'eval_roofline': eval_roofline_block(alg, ms_per_step, world, measured_hbm, class_bytes, {
+                'measured_copy_GBs': round(copy_gbs, 1), 'ffts_executed': n_fft, 'kernel_launches': n_launch,
+                'device_ms_last_eval': round(dev_ms, 4) if dev_ms is not None else None}),
+            'kernels': kernels,
+            'source_stamp': stamp,
+        })
+        if world > 1:
+            # what crosses the fabric per evaluation and rank: every transposed spectrum leaves (world-1)/world
+            # of its slab; with the ipc transport the profiling pass also times the scatter kernels (all links driven at once) and
+            # the epoch waits (peer skew + delivery)
+            ntr = 19 if a.cfg == 'cfg3' else 6
+            sent = ntr * (Cc / world) * (world - 1) / world
+            ex = {'spectra_transposed_per_eval': ntr, 'sent_MB_per_rank_per_eval': round(sent / 1e6, 1),
+                  'MB_per_link_per_eval': round(sent / (world - 1) / 1e6, 1)}
+            if 'ipc_scatter' in kernels:
+                ms = kernels['ipc_scatter']['ms_per_eval']
+                ex.update(scatter_ms_per_eval=ms, scatter_GBs_per_rank=round(sent / (ms * 1e-3) / 1e9, 1) if ms else None,
+                          scatter_GBs_per_link=round(sent / (world - 1) / (ms * 1e-3) / 1e9, 1) if ms else None,
+                          wait_ms_per_eval=kernels.get('ipc_sync', {}).get('ms_per_eval'))
+            out['exchange'] = ex
+        # (chi.grad of the timed call itself; on slabs every rank contributes its planes' share of the statistics)
+        gst = grad_stats(g) if world == 1 else grad_stats(g, dist, eng.plan.x_range().start, n ** 3)
+        chk = reference_check(n, a.cfg, a.dtype, E_tot, mu, gst)
+        out['reference_check'] = chk
+        if world > 1 and rank == 0 and os.environ.get('OFDFT_BENCH_NO_PARITY') != '1':
+            # the slab-decomposed result against ONE engine on the whole grid of this rank's GPU (outside the timed region)
+            one = Engine((n, n, n), device, dtype=tdtype).set_cell(torch.as_tensor(box)).set_terms(names)
+            E1, mu1, g1 = one.energy_grad_chi(torch.as_tensor(chi_full, dtype=tdtype, device=device), n_elec,
+                                              torch.as_tensor(vext_full, dtype=tdtype, device=device))
+            gs = g1[eng.plan.x_range()]
+            out['parity_vs_single_gpu'] = {
+                'rel_dE': abs(E_tot - sum(E1.values())) / abs(sum(E1.values())), 'rel_dmu': abs(mu - mu1) / abs(mu1),
+                'grad_slab_max_rel': float((g - gs).abs().max() / gs.abs().max())}
+            one.close()
+            del g1, gs
+        if world > 1:
+            out['exchange']['xchg_chunks'] = eng.stages.nchunks
+        if world > 1 and (n == 256 or os.environ.get('OFDFT_BENCH_SCALE_ANY_GRID') == '1') and a.cfg == 'cfg3' and os.environ.get('OFDFT_BENCH_NO_SCALE512') != '1':
+            # the 512^3 one-GPU / N-GPU pair of the north star, inside this very command (the driver passes no --grid)
+            working = [tr for tr, v in (transport_probe or {}).items() if not v.get('failed') and not v.get('disagrees_with_collective')]
+            eng.close(sync_peers=True)
+            del g
+            if rank == 0:       # the primary line survives whatever happens in the optional block (a copy on stderr; stdout stays ONE line)
+                sys.stderr.write('bench.py: 256^3 line before the optional scale_512 block: %s\n' % json.dumps(out))
+                sys.stderr.flush()
+            try:
+                sc = scale_512_block(dist, device, backend, rank, world, tdtype, names, box, chi_full, vext_full, n_elec, E_tot, working)
+            except Exception as e:  # noqa: BLE001  (a failure every rank shares, e.g. memory: the 256^3 line above must survive it)
+                sc = {'error': repr(e)[:300]}
+            if rank == 0:
+                out['scale_512'] = sc
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            cb = cpu_baseline(a.cpu_sample_grid, n)
+            if cb['full']:
+                f = cb['full']
+                out['cpu_baseline'] = {
+                    'value': round(1.0 / f['best'], 5), 'unit': 'evals/s', 'cores': cb['cores'], 'kind': 'port',
+                    'sample': '%d^3 grid (the full workload), same terms, best of %d after 1 warm-up (%.2f s/eval; first call '
+                              '%.1f s incl. WGC99 kernel generation); %d^3 pre-sample: %.3f s/eval'
+                              % (f['n'], max(f['count'], 1), f['best'], f['first'], cb['n'], cb['best'])}
+            else:
+                scale = (a.cpu_sample_grid / n) ** 3
+                out['cpu_baseline'] = {
+                    'value': round(scale / cb['best'], 5), 'unit': 'evals/s', 'cores': cb['cores'], 'kind': 'port',
+                    'sample': '%d^3 grid, same terms, best of %d after 1 warm-up (%.2f s/eval; first call %.1f s incl. WGC99 '
+                              'kernel generation); value = measured %d^3 rate x (%d/%d)^3 grid-point scaling to %d^3'
+                              % (cb['n'], cb['count'], cb['best'], cb['first'], cb['n'], cb['n'], n, n),
+                    'measured_evals_per_s_on_sample': round(1.0 / cb['best'], 4)}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

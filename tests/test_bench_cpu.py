@@ -158,6 +158,26 @@ def test_oracle_reproduces_the_bench_pin_at_64():
     assert abs(E - ref['E']) <= 1e-11 * abs(ref['E'])
 
 
+def test_dump_outputs_writes_a_large_gradient_at_a_fixed_seeded_sample(tmp_path):
+    """--dump-outputs: float files only, a gradient above the point budget at the same indices run after run, within 64 MB"""
+    import torch
+    E = {'ion_electron': -1.5, 'hartree': 0.25}
+    g = torch.arange(160 ** 3, dtype=torch.double).reshape(160, 160, 160) * 1e-3
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), E, 0.125, g)
+        runs.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) < 64e6
+    a, b = runs
+    assert sorted(a) == ['energy_terms', 'grad', 'grad_index', 'mu']
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert list(a['energy_terms']) == [-1.5, 0.25] and list(a['mu']) == [0.125]
+    idx = a['grad_index'].astype(np.int64)
+    assert 0 < idx.size <= 1 << 21 and np.array_equal(a['grad'], g.reshape(-1).numpy()[idx])
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+
+
 def test_source_stamp_is_stable_and_tracks_the_sources():
     a, b = bench.source_stamp(), bench.source_stamp()
     assert a == b and len(a) == 16

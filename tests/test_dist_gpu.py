@@ -336,7 +336,7 @@ def test_bench_scale_pair_rehearsal_ranks_sharing_the_gpu(ranks):
     env = dict(os.environ, OFDFT_BENCH_SHARE_GPU='1', OFDFT_BENCH_BACKEND='gloo', OFDFT_BENCH_SCALE_ANY_GRID='1',
                HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--grid', '64', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        '--full', '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors='replace')[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith('{')]
     assert len(lines) == 1, lines                      # ONE JSON line on stdout

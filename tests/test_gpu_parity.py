@@ -176,6 +176,32 @@ def test_bench_workload_energy_mu_and_gradient_match_the_reference_pin(n):
     eng.close()
 
 
+def test_plain_bench_run_prints_the_headline_and_dumps_what_the_timed_steps_returned(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: ONE JSON line with the headline and none of the --full
+    blocks, K timed steps, and the dumped result of the last timed step (energies, mu, chi.grad) on the reference pin"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--grid', '64', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line['metric'] == 'energy+grad evals/sec' and line['unit'] == 'evals/s' and line['higher_is_better'] is True
+    assert line['dtype'] == 'f64' and line['steps'] == 3 and line['ms_per_step'] > 0
+    assert abs(line['value'] * line['ms_per_step'] - 1e3) < 1e-2 * 1e3
+    assert not {'roofline', 'eval_roofline', 'kernels', 'reference_check', 'cpu_baseline'} & set(line), sorted(line)
+    E, mu, g = (np.load(str(tmp_path / (nm + '.npy'))) for nm in ('energy_terms', 'mu', 'grad'))
+    assert E.dtype == mu.dtype == g.dtype == np.float64 and g.shape == (64, 64, 64)
+    assert abs(float(E.sum()) - line['energy_Ha']) <= 1e-12 * abs(line['energy_Ha']) and float(mu[0]) == line['mu']
+    chk = bench.reference_check(64, 'cfg3', 'f64', float(E.sum()), float(mu[0]), bench.grad_stats(torch.as_tensor(g)))
+    assert chk['ok'], chk
+
+
 @pytest.mark.parametrize('shape,cell', [((256, 16, 32), ('cubic', 32)), ((256, 32, 16), ('tri', 1.1)), ((512, 8, 16), ('cubic', 16))])
 def test_folded_wgc99_table_reads_change_nothing(shape, cell):
     """round 5: on cells with orthogonal axes the cross-wave x pass reads the WGC99 table entry of x > n0 / 2 at n0 - x (|k| is

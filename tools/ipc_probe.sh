@@ -3,7 +3,7 @@
 # copies (ipc) vs host-staged all-to-alls.  Not a scaling measurement (one GPU does all the work): it shows parity and what
 # the host path costs.   usage: bash tools/ipc_probe.sh > gpurun_out/ipc_probe.txt
 for t in ipc collective; do for g in 128 256; do for n in 2 4; do
-  OFDFT_BENCH_SHARE_GPU=1 OFDFT_BENCH_BACKEND=gloo OFDFT_BENCH_TRANSPORT=$t timeout -k 10 200 python bench.py --gpus $n --grid $g --steps 5 --warmup 2 --no-cpu-baseline > /tmp/ipc_probe.out 2>/tmp/ipc_probe.err
+  OFDFT_BENCH_SHARE_GPU=1 OFDFT_BENCH_BACKEND=gloo OFDFT_BENCH_TRANSPORT=$t timeout -k 10 200 python bench.py --gpus $n --grid $g --steps 5 --warmup 2 --full --no-cpu-baseline > /tmp/ipc_probe.out 2>/tmp/ipc_probe.err
   python - "$t" <<'PY'
 import json, sys
 lines = [l for l in open('/tmp/ipc_probe.out').read().splitlines() if l.startswith('{')]

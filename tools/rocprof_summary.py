@@ -127,7 +127,7 @@ def main():
     if json_out:
         import json
         out = {'source': 'rocprofv3 --kernel-trace (durations) and two --pmc passes (FETCH_SIZE, WRITE_SIZE) of '
-                         '`OFDFT_SIDE_STREAM=0 python3 bench.py --steps 8 --warmup 1 --no-cpu-baseline`; '
+                         '`OFDFT_SIDE_STREAM=0 python3 bench.py --steps 8 --warmup 1 --full --no-cpu-baseline`; '
                          'reads = 2 x FETCH_SIZE KiB (gfx950 correction, MI355X_MICROARCH.md HBM section), '
                          'writes = WRITE_SIZE KiB; per launch',
                'source_stamp': stamp, 'evaluations': evaluations,
