@@ -107,6 +107,13 @@ typedef struct ofdft_ctx ofdft_ctx;
 #define OFDFT_Q_YFWD_FUSED      10  /* y-forward transforms of the last energy call that rode inside a yderiv launch (1C -> 2C in one pass) */
 #define OFDFT_Q_RESIDENT_FALLBACKS 8 /* evaluations re-run on the staged path because a grid barrier of the persistent kernel timed out
                                         (the kernel is switched off for the context after the first one) */
+#define OFDFT_Q_XPASS_KINDS     11  /* bitmask of the fused x-pass kernel families the last energy call launched (OFDFT_XPASS_*); like
+                                        OFDFT_Q_LAUNCH_COUNT it is reset per call and a hipGraph replay reports what its captured call launched */
+#define OFDFT_XPASS_GROUP    (1u << 0)  /* group-parallel kernel (fft_kernels.h: xfused_kernel)                               */
+#define OFDFT_XPASS_WAVE     (1u << 1)  /* wave-local kernel (xwave.h)                                                        */
+#define OFDFT_XPASS_CROSS1   (1u << 2)  /* cross-wave kernel (xcross.h), one line per lane                                    */
+#define OFDFT_XPASS_CROSS2   (1u << 3)  /* cross-wave kernel, two memory-adjacent lines per lane (fp32 build)                 */
+#define OFDFT_XPASS_CHIRPZ   (1u << 4)  /* chirp-z forward-x / mix / inverse-x kernel (bluestein.h: bluestein_xmix_kernel)    */
 
 int  ofdft_create(ofdft_ctx** out, int n0, int n1, int n2, int dtype, int device_id);
 void ofdft_destroy(ofdft_ctx* ctx);

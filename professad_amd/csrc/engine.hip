@@ -1184,11 +1184,13 @@ int closure_graph(ofdft_ctx* c, const real* chi, const real* vext, double nel, r
         ge->collect = unfused ? ((c->mask & kGgaAny) ? 0 : kCollectNoGga) : collect_flags(zrun(c), zrun(c).late_join);
         ge->fft_count = c->fft_count;
         ge->launch_count = c->launch_count;
+        ge->xpass_kinds = c->xpass_kinds;
         ge->ypass_count = c->ypass_count;
         ge->yfwd_fused = c->yfwd_fused;
     }
     c->fft_count = ge->fft_count;
     c->launch_count = ge->launch_count;
+    c->xpass_kinds = ge->xpass_kinds;
     c->ypass_count = ge->ypass_count;
     c->yfwd_fused = ge->yfwd_fused;
     HIP_TRY(c, hipGraphLaunch(ge->exec, st));
@@ -1707,6 +1709,7 @@ int ofdft_query(ofdft_ctx* c, int what, double* out) {
         case OFDFT_Q_RESIDENT_FALLBACKS: *out = (double)c->resident_fallbacks; return OFDFT_OK;
         case OFDFT_Q_XCHG_CHUNKS: *out = (double)c->xc.n; return OFDFT_OK;
         case OFDFT_Q_YFWD_FUSED: *out = (double)c->yfwd_fused; return OFDFT_OK;
+        case OFDFT_Q_XPASS_KINDS: *out = (double)c->xpass_kinds; return OFDFT_OK;
         case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27:      // phase clock of the last persistent-kernel evaluation (microseconds)
             *out = c->h_partial[what] * 0.01;
             return OFDFT_OK;

@@ -80,6 +80,7 @@ struct ofdft_ctx {
     bool wgc_fold = true;          // orthogonal cells: the cross-wave x pass reads the table entry of x > n0 / 2 at n0 - x (OFDFT_OPT_WGC_FOLD)
     // stats
     int fft_count = 0, launch_count = 0;
+    unsigned xpass_kinds = 0;   // OFDFT_XPASS_* bits of the fused x-pass kernels the last energy call launched (OFDFT_Q_XPASS_KINDS)
     double ypass_count = 0.0;   // whole-spectrum y passes executed (fractions for x- / kz-range launches)
     float last_ms = 0.f;
     bool ms_pending = false;    // ev1 recorded without a host wait (device-resident dist finish): elapsed time read on demand
@@ -117,6 +118,7 @@ struct ofdft_ctx {
         hipGraphExec_t exec = nullptr;
         int collect = 0;                     // zfused_collect flags of the captured evaluation
         int fft_count = 0, launch_count = 0, yfwd_fused = 0;
+        unsigned xpass_kinds = 0;
         double ypass_count = 0.0;
     };
     std::vector<GraphEntry> graphs;

@@ -723,6 +723,7 @@ int begin_call(ofdft_ctx* c, hipStream_t st, bool timed = true) {
     if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
     c->fft_count = 0;
     c->launch_count = 0;
+    c->xpass_kinds = 0;
     c->ypass_count = 0.0;
     c->yfwd_fused = 0;
     if (timed) HIP_TRY(c, hipEventRecord(c->ev0, st));

@@ -307,6 +307,7 @@ static int launch_xmix_t(ofdft_ctx* c, const BsMixIo& io, const Mix& mix, const 
     const long long nlines = (long long)c->n1 * c->g.nzc;
     const long long tiles = (nlines + Cfg::LPW - 1) / Cfg::LPW;
     const int blocks = (int)std::min<long long>(tiles, (long long)device_cus(c) * OFDFT_BS_WGS);
+    c->xpass_kinds |= OFDFT_XPASS_CHIRPZ;
     OFDFT_LAUNCH(c, st, "bluestein_xmix", (bluestein_xmix_kernel<M, NIN, NOUT, Mix>), dim3(blocks), dim3(Cfg::TPB), Cfg::LDS, io, c->g,
                  c->n0, nlines, (const cplx*)t.chirp, (const cplx*)t.filt, (const cplx*)tw, mix);
     return 0;

@@ -36,6 +36,7 @@ int launch_xfused_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout
     }
     main.blk0 = line0 / Cfg::LPW;
     const int mb = (main.nlines - line0 + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
+    c->xpass_kinds |= OFDFT_XPASS_GROUP;
     OFDFT_LAUNCH(c, st, nm, (xfused_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb,
                  gk, tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;
@@ -72,6 +73,7 @@ int launch_xw_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
     }
     main.blk0 = line0 / Cfg::LPB;
     const int mb = (main.nlines - line0 + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
+    c->xpass_kinds |= OFDFT_XPASS_WAVE;
     OFDFT_LAUNCH(c, st, nm, (xw_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb, gk,
                  (const cplx*)tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;
@@ -125,6 +127,7 @@ int launch_xc_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
             declared[dv] = true;
         }
     }
+    c->xpass_kinds |= Cfg::NL == 2 ? OFDFT_XPASS_CROSS2 : OFDFT_XPASS_CROSS1;
     OFDFT_LAUNCH(c, st, nm, (xc_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), lds, io, main, rem, mb, gk,
                  (const cplx*)tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;

@@ -30,6 +30,12 @@ def test_header_constants_match_python_mirror():
         assert int(bits[nm.upper()]) == bit.bit_length() - 1
     assert N.TERM_ORDER == sorted(N.TERM_BITS, key=lambda k: N.TERM_BITS[k])
     assert int(re.search(r'#define OFDFT_NTERMS\s+(\d+)', header).group(1)) == N.NTERMS == len(N.TERM_ORDER)
+    queries = {nm: int(v) for nm, v in re.findall(r'#define OFDFT_Q_([A-Z0-9_]+)\s+(\d+)', header)}
+    for nm, v in queries.items():
+        assert getattr(N, 'Q_' + nm) == v, nm
+    assert len(set(queries.values())) == len(queries)
+    for nm in ('GROUP', 'WAVE', 'CROSS1', 'CROSS2', 'CHIRPZ'):
+        assert getattr(N, 'XPASS_' + nm) == 1 << int(bits['XPASS_' + nm]), nm
 
 
 def test_error_paths_without_gpu():
