@@ -332,6 +332,11 @@ int  ofdft_lbfgs_update(ofdft_lbfgs* h, const double* coef_s, const double* coef
 #define OFDFT_OPT_BS_FUSED 15     /* chirp-z path (extents without a line-transform plan, i.e. what the reference's System.ecut2shape, system.py:74-89, gives):
                                      1 (default) = forward-x, spectral multiply and inverse-x of every convolution in ONE kernel (x extents up to 256);
                                      0 = three passes per transform and separate multiply kernels */
+#define OFDFT_OPT_POT_SPECTRUM 16 /* 1 (default): one GPU, split-derivative GGA with Hartree: the Hartree potential rides in the divergence spectrum
+                                     (v_H^ / -2 beside i f_a G_a^ in the divergence x pass, which also forms E_H by Parseval), and D_b G_b plus the
+                                     y-inverse of that spectrum are one y pass -- the combine kernel reads one spectrum where it read three.
+                                     0: the Hartree spectrum and the two divergence parts travel separately (slabs, chirp-z path and the persistent
+                                     small-grid kernel always do) */
 #define OFDFT_OPT_WGC_FOLD 28     /* 1 (default): on cells with orthogonal axes the cross-wave x pass reads the WGC99 table entry of x > n0 / 2 at
                                      n0 - x (|k| is even along a line there; functionals.py:968-972 depends on |k| only): both uses of an entry
                                      fall into one tile, the second is a cache hit, the pass' table traffic halves.  0: every k-point its own entry */

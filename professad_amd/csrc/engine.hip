@@ -1623,6 +1623,9 @@ int ofdft_set_option(ofdft_ctx* c, int option, double value) {
         case OFDFT_OPT_GGA_SPLIT:
             c->gga_split = value != 0.0;
             return OFDFT_OK;
+        case OFDFT_OPT_POT_SPECTRUM:
+            c->pot_spectrum = value != 0.0;
+            return OFDFT_OK;
         case OFDFT_OPT_SPLIT_COMBINE:
             c->split_combine = value != 0.0;
             c->defer_vpart = value != 1.0;

@@ -80,6 +80,7 @@ struct ofdft_ctx {
     bool wgc_fold = true;          // orthogonal cells: the cross-wave x pass reads the table entry of x > n0 / 2 at n0 - x (OFDFT_OPT_WGC_FOLD)
     // stats
     int fft_count = 0, launch_count = 0;
+    int xpass_blocks = 0;       // workgroups of the last fused x pass launched (rows of its energy partials, if its mix has any)
     unsigned xpass_kinds = 0;   // OFDFT_XPASS_* bits of the fused x-pass kernels the last energy call launched (OFDFT_Q_XPASS_KINDS)
     double ypass_count = 0.0;   // whole-spectrum y passes executed (fractions for x- / kz-range launches)
     float last_ms = 0.f;
@@ -90,6 +91,7 @@ struct ofdft_ctx {
     bool bs_fused = true;        // chirp-z path: forward-x, spectral multiply and inverse-x in one kernel (OFDFT_OPT_BS_FUSED)
     bool use_bluestein = true;   // non power-of-two extents <= 512: chirp-z line transforms (else the plain O(N^2) DFT kernels)
     bool gga_split = true;       // GGA chain in split-derivative form: only the x index-derivative visits the x pass
+    bool pot_spectrum = true;    // OFDFT_OPT_POT_SPECTRUM: Hartree potential folded into the divergence spectrum (one GPU, split GGA)
     bool split_combine = true;   // WGC99 part of the combine as its own kernel on the nonlocal chain's stream (forked runs)
     bool defer_vpart = true;     // ... and, in closure evaluations, merged into the potential by chi_grad (the combine kernel does not wait for it)
     int ybatch = 1;         // OFDFT_OPT_YBATCH: the y passes of the three spectra of a WGC99 half as ONE launch (grid.y = 3).  A 256^3 y pass is
@@ -324,6 +326,8 @@ template <bool INV> int fast_axis_pass(ofdft_ctx* c, int axis, cplx* spec, hipSt
 template <bool INV> int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStream_t st, int xk = -1);
 // (fwd: also store the y-forward transform of `in` there -- in place when fwd == in; fft_kernels.h: yderiv_kernel)
 int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd = nullptr);
+// out = y-inverse of (i f_b scale y-forward(in) + add), add a y-forwarded spectrum of the same layout (add == out: in place)
+int yderiv_add(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st);
 int rfftn_internal(ofdft_ctx* c, const real* in, cplx* spec, hipStream_t st);
 int rfftn_internal_multi(ofdft_ctx* c, const real* const* in, cplx* const* spec, int n, hipStream_t st);
 // chirp-z path with the fused x pass (lines.hip): z + y passes | forward-x, mix, inverse-x | y + z passes
@@ -353,6 +357,11 @@ int xfused(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const c
 // the WGC99 pass (3 -> 3): with folded table reads (MixWgcFold) where the cell's axes are orthogonal and the cross-wave kernel serves
 // the pass, the plain form everywhere else (xpass_b.hip)
 int xfused_wgc(ofdft_ctx* c, const XfIo& io, const MixWgc& mix, hipStream_t st, const char* nm, const XfLayout& lay = XfLayout{});
+// a pass whose mix also integrates an energy over its input spectra (one partial per workgroup; c->xpass_blocks of them): one GPU,
+// cross-wave or wave-local kernel (xpass_a.hip); xfused_energy_serves = whether one of them takes the pass (xpass_impl.h)
+template <int NIN, class Mix>
+int xfused_energy(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const char* nm);
+bool xfused_energy_serves(const ofdft_ctx* c, int nin);
 
 // ---- launchers of the fused z kernels (zfused.hip).  (chunk, nchunks): the launch covers that share of the rows, i.e. the
 // x planes [chunk, chunk + 1) * n0 / nchunks (x-chunked pipeline); partial sums land where a full launch would put them.

@@ -32,6 +32,9 @@ void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pb
 //   stage 3  y-inverse of the results; PBE mid stage on chip; y-forward of the flux          -> exchange
 //   stage 4  fused x pass of the divergence                                                  -> exchange
 //   stage 5  y-inverse of the divergence; combine kernel (potential + energy integrands)
+// Potential-spectrum form (one GPU, split-derivative GGA with Hartree; OFDFT_OPT_POT_SPECTRUM): stage 2 forms i f_a n^ only, stage 4
+// reads n^ beside G_a^ and returns i f_a G_a^ - v_H^ / 2 (+ E_H by Parseval), stage 5 adds D_b G_b inside the y-inverse of that
+// spectrum -- the combine kernel reads one spectrum for Hartree + divergence where it read three (v_H, D_a part, D_b part).
 struct ZRun {
     DenSrc ds{};
     double nel = 0.0;
@@ -51,6 +54,9 @@ struct ZRun {
     std::vector<cplx*> xlist[2];
     bool gsplit = false;           // split-derivative form of the GGA chain (only D_a visits the x pass)
     bool lapl = false;             // Laplacian-dependent Pauli-Gaussian member: lap n in, lap(df/dL) out ride the same chain
+    // potential-spectrum form (OFDFT_OPT_POT_SPECTRUM; one GPU, split GGA + Hartree): v_H^ rides in the divergence x pass (which reads
+    // n^ again and forms E_H by Parseval), D_b G_b + the y-inverse of that spectrum are one y pass, the combine reads one spectrum
+    bool pspec = false;
     cplx* s_l = nullptr;
     real* dzn = nullptr;
     bool wgc_yinv_done = false;    // kz-chunked form: the y-inverse of the WGC99 results already ran next to the x pass
@@ -120,6 +126,7 @@ int zsetup(ofdft_ctx* c) {
     r.wgc_yinv_done = false;
     r.s_g[0] = r.s_g[1] = r.s_g[2] = nullptr;
     r.s_n = r.s_s = r.s_vh = r.s_b = r.s_a = nullptr;
+    r.pspec = false;
     if ((mask & OFDFT_ION_ELECTRON) && !r.vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
     r.setup_done = true;
     return 0;
@@ -148,6 +155,8 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             r.gsplit = r.has_g && c->gga_split;
             r.lapl = r.gsplit && gga_needs_laplacian(c);
             r.s_l = nullptr;
+            // (n^ stays in s_n, y-forwarded, until the divergence x pass of stage 4: stage 2 writes its results elsewhere)
+            r.pspec = r.gsplit && r.has_h && !dx && c->pot_spectrum && xfused_energy_serves(c, r.lapl ? 3 : 2);
             if (r.gsplit) {
                 if ((rc = real_ws(c, "dzn", &r.dzn))) return rc;
                 if ((rc = spec_ws(c, "zgx", &r.s_g[0]))) return rc;
@@ -298,7 +307,8 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             XfIo io{};
             io.in[0] = in_of(r.s_n);
             int no = 0;
-            if (r.has_h) {
+            const bool vh = r.has_h && !r.pspec;      // (potential-spectrum form: v_H^ comes out of the divergence pass instead)
+            if (vh) {
                 if ((rc = spec_ws(c, "zvh", &r.s_vh))) return rc;
                 io.out[no++] = out_of(r.s_vh);
             }
@@ -312,9 +322,9 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                     io.out[no++] = out_of(r.s_g[k]);
                 }
             }
-            if (r.lapl && r.has_h) rc = xfused<1, 3>(c, io, MixDensityA<true, true>{c->kg}, st, "xfused_n", lay);
+            if (r.lapl && vh) rc = xfused<1, 3>(c, io, MixDensityA<true, true>{c->kg}, st, "xfused_n", lay);
             else if (r.lapl) rc = xfused<1, 2>(c, io, MixDensityA<false, true>{c->kg}, st, "xfused_n", lay);
-            else if (r.gsplit && r.has_h) rc = xfused<1, 2>(c, io, MixDensityA<true>{c->kg}, st, "xfused_n", lay);
+            else if (r.gsplit && vh) rc = xfused<1, 2>(c, io, MixDensityA<true>{c->kg}, st, "xfused_n", lay);
             else if (r.gsplit) rc = xfused<1, 1>(c, io, MixDensityA<false>{c->kg}, st, "xfused_n", lay);
             else if (r.has_h && r.has_g) rc = xfused<1, 4>(c, io, MixDensity<true, true>{c->kg}, st, "xfused_n", lay);
             else if (r.has_h) rc = xfused<1, 1>(c, io, MixDensity<true, false>{c->kg}, st, "xfused_n", lay);
@@ -452,7 +462,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
         r.stage[1] = 3;
         return 0;
     }
-    if (r.has_h) r.za.vh = r.s_vh;
+    if (r.has_h && !r.pspec) r.za.vh = r.s_vh;
     if (r.s_s) r.za.lap = r.s_s;
     if (r.has_g && r.gsplit) {
         // split-derivative form: A = (D_a n) came back from the x pass and was y-inverted above, B = (D_b n) is local
@@ -461,7 +471,8 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
             return rc;
         OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kCombineScalars, c->h_partial + kCombineScalars);
         // D_b G_b in one y pass, in place (scaled like B); only G_a goes on to the x pass
-        if ((rc = yderiv(c, r.s_g[1], r.s_g[1], (double)c->n0g, st))) return rc;
+        // (potential-spectrum form: G_b waits for stage 5, where its D_b joins the y-inverse of the divergence spectrum)
+        if (!r.pspec && (rc = yderiv(c, r.s_g[1], r.s_g[1], (double)c->n0g, st))) return rc;
         if (!dx && (rc = fast_axis_pass<false>(c, 1, r.s_g[0], st))) return rc;
         xl.push_back(r.s_g[0]);
         if (r.lapl) {             // (df/dL)^ goes on to the x pass beside G_a
@@ -507,7 +518,27 @@ int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
     }
     r.xlist[chain].clear();
     const XcView xv = xc_view(c, xk < 0 ? 0 : xk);
-    if (chain == 0 && r.has_g && r.gsplit) {
+    if (chain == 0 && r.pspec) {
+        // i f_a G_a^ [+ (k^2 / 2) (df/dL)^] - v_H^ / 2 in place of G_a^, and the partial sums of E_H (one per workgroup)
+        acc_t* ehp;
+        const size_t rows = (size_t)(c->gx.total / c->gx.n0) + 1;        // >= workgroups of the pass (at least one line each)
+        if (int rc = get_ws(c, "zh:part", sizeof(acc_t) * rows, (void**)&ehp)) return rc;
+        XfIo dio{};
+        dio.in[0] = dio.out[0] = r.s_g[0];
+        const double ehpref = 2.0 * kPi / (double)c->npts_g;
+        if (r.lapl) {
+            dio.in[1] = r.s_l;
+            dio.in[2] = r.s_n;
+            if (int rc = xfused_energy<3>(c, dio, MixDerivAH<true>{c->kg, ehp, ehpref, c->n2 / 2}, st, "xfused_div")) return rc;
+        } else {
+            dio.in[1] = r.s_n;
+            if (int rc = xfused_energy<2>(c, dio, MixDerivAH<false>{c->kg, ehp, ehpref, c->n2 / 2}, st, "xfused_div")) return rc;
+        }
+        r.za.eh_part = ehp;
+        r.za.eh_rows = c->xpass_blocks;
+        c->fft_count++;           // (the inverse transform of v_H^ rides in this spectrum: counted as before)
+        r.xlist[0].push_back(r.s_g[0]);
+    } else if (chain == 0 && r.has_g && r.gsplit) {
         XfIo dio{};
         XfLayout lay{};
         dio.in[0] = dio.out[0] = r.s_g[0];
@@ -588,6 +619,8 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
             cplx *send, *recv;
             if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
             if (part != 2 && (rc = ypass_xchg<true>(c, {dsp}, recv, st))) return rc;
+        } else if (r.pspec) {     // D_b G_b + the y-inverse of the divergence spectrum (+ v_H) in one pass, into that spectrum
+            if ((rc = yderiv_add(c, r.s_g[1], dsp, dsp, (double)c->n0g, st))) return rc;      // (x-chunked combine: before its loop)
         } else if (chunked) {
             r.deferred.push_back(dsp);
         } else if ((rc = fast_axis_pass<true>(c, 1, dsp, st))) {
@@ -595,7 +628,7 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
         }
         c->fft_count++;
         r.za.div = dsp;
-        r.za.div2 = r.gsplit ? r.s_g[1] : nullptr;
+        r.za.div2 = (r.gsplit && !r.pspec) ? r.s_g[1] : nullptr;
         r.za.dfdn = r.dfdn;
     }
     r.xlist[0].clear();

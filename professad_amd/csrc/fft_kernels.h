@@ -208,11 +208,14 @@ __device__ __forceinline__ void repattern_out_to_in(cplx (&v)[PL::E], int j, rea
 // functional_tools.py:152-154) times `scale`, inverse FFT.  Out of place or in place (in == out).
 // fwd != nullptr (round 4): the forward transform of the line is stored there as well (in place: fwd == in) -- the density
 // spectrum needs BOTH its y-forward (for the x pass) and D_b n, which were two passes reading the same array.
-template <int LEN>
+// ADD: `add` is a y-forwarded spectrum of the same layout whose line is added (in the forward transform's output order) before
+// the inverse: D_b G_b and the y-inverse of the x pass' result of the divergence in one pass, 2 spectra in and 1 out (add == out:
+// in place -- the line's loads precede the transforms' barriers, as for fwd).
+template <int LEN, bool ADD = false>
 __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* in, cplx* out,
                                                                    LineMap m_main, LineMap m_rem, int main_blocks,
                                                                    long long rem_offset, const cplx* __restrict__ tw,
-                                                                   real scale, cplx* fwd) {
+                                                                   real scale, cplx* fwd, const cplx* add = nullptr) {
     constexpr int P = PassCfg<LEN>::P, E = PassCfg<LEN>::E, LPW = PassCfg<LEN>::LPW;
     extern __shared__ __attribute__((aligned(16))) real lds[];
     const int tid = threadIdx.x;
@@ -234,6 +237,12 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* i
 #pragma unroll
     for (int q = 0; q < E; ++q)
         v[q] = (PL::slot_in(q) && valid && PL::lane_in(j, q)) ? buf_load_c(in + roff + b0 + PL::cin(q) * se_u, voff) : mkc(0.0, 0.0);
+    cplx x[ADD ? E : 1];
+    if constexpr (ADD) {
+#pragma unroll
+        for (int q = 0; q < E; ++q)
+            x[q] = (PL::slot_out(q) && valid && PL::lane_out(j, q)) ? buf_load_c(add + roff + b0 + PL::cout(q) * se_u, voff) : mkc(0.0, 0.0);
+    }
     real* mine = lds + l * PassCfg<LEN>::LSTR;
     line_fft<LEN, false, kCX>(v, j, mine, tw);
     if (fwd && valid) {       // (every load of the workgroup's lines precedes the transform's barriers: in place is safe)
@@ -246,6 +255,7 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* i
         const int e = j + PL::cout(q);
         const real f = scale * (real)(e <= LEN / 2 ? e : e - LEN);
         v[q] = mkc(-f * v[q].y, f * v[q].x);
+        if constexpr (ADD) v[q] = cadd(v[q], x[q]);
     }
     __syncthreads();
     repattern_out_to_in<PL, false>(v, j, mine);

@@ -512,6 +512,44 @@ struct MixDerivAL {
     }
 };
 
+// (G_a^, [L^,] n^) -> i f_a G_a^ [+ (k^2 / 2) L^] - (2 pi / k^2) n^ : MixDerivA / MixDerivAL with the Hartree potential folded in.
+// The combine kernel subtracts this spectrum twice, so -v_H^ / 2 comes back as +v_H (k = 0 stays 0, as in MixDensityA).  The
+// pass holds the whole density spectrum, so it also forms E_H = 1/2 sum_k 4 pi |n^_k|^2 / k^2 by Parseval over the half spectrum
+// (the planes kz = 0 and kz = n2 / 2 once, every other plane twice for its conjugate): ehpref = 2 pi / N puts it on the scale of
+// the combine's real-space sum 1/2 sum_r n v_H (inv_n = 1 / N); one partial per workgroup in epart.
+template <bool HAS_L> struct MixDerivAH {
+    KGeom kg;
+    acc_t* epart;
+    double ehpref;
+    int kz_nyq;
+    static constexpr bool kEnergy = true;
+    static constexpr int NI = HAS_L ? 3 : 2;
+    static __device__ __forceinline__ constexpr bool imag(int) { return true; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool present() { return true; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool imag_oi() { return I == 0; }
+    template <int O, int I>
+    __device__ __forceinline__ real coef(int x, int y, int z, long long, unsigned) const {
+        if constexpr (I == 0) {
+            return ifreq(x, kg.g.n0);
+        } else {
+            real kx, ky, kz, k2;
+            kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
+            if constexpr (HAS_L && I == 1) return 0.5 * k2;
+            return (k2 != 0.0) ? -2.0 * kPiR / k2 : 0.0;
+        }
+    }
+    template <int NIN>
+    __device__ __forceinline__ acc_t energy(const cplx (&in)[NIN], int x, int y, int z) const {
+        static_assert(NIN == NI, "inputs");
+        real kx, ky, kz, k2;
+        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
+        if (k2 == 0.0) return 0.0;
+        const cplx nk = in[NIN - 1];
+        const acc_t w = (z == 0 || z == kz_nyq) ? 1.0 : 2.0;
+        return w * ehpref * ((acc_t)nk.x * nk.x + (acc_t)nk.y * nk.y) / (acc_t)k2;
+    }
+};
+
 // one spectrum times a real f(k): OP as spec_scale_kernel
 template <int OP> struct MixScale {
     KGeom kg;

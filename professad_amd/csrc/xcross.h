@@ -288,6 +288,7 @@ __global__ __launch_bounds__(XcCfg<LEN>::TPB, (xc_waves<LEN, NIN, NOUT>())) void
             }
     });
     // ---- mix, in registers: the thread owns k-points x = J + PP m of its lines in every spectrum
+    acc_t eacc = 0.0;
 #pragma unroll
     for (int nl = 0; nl < NL; ++nl)
 #pragma unroll
@@ -297,6 +298,7 @@ __global__ __launch_bounds__(XcCfg<LEN>::TPB, (xc_waves<LEN, NIN, NOUT>())) void
             for (int I = 0; I < NIN; ++I) in[I] = v[I][nl][q];
             if constexpr (NC > 0) mix.apply(out, in, cfs[nl][q]);
             else xw_outputs<NIN, NOUT, 0, Mix>(out, in, mix, J + PP * q, y[nl], kz[nl], b0 + q * tqstep, tloff + nl);
+            if constexpr (mix_has_energy<Mix>::value) eacc += mix.energy(in, J + PP * q, y[nl], kz[nl]);
 #pragma unroll
             for (int O = 0; O < NOUT; ++O) v[O][nl][q] = out[O];
         }
@@ -342,6 +344,7 @@ __global__ __launch_bounds__(XcCfg<LEN>::TPB, (xc_waves<LEN, NIN, NOUT>())) void
             }
         }
     });
+    if constexpr (mix_has_energy<Mix>::value) xpart_store<TPB>(eacc, mix.epart, lds);
 }
 
 }  // namespace ofdft

@@ -8,6 +8,8 @@ namespace eng {
 
 template <int LEN, int NIN, int NOUT, class Mix>
 int launch_xfused_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& lay, hipStream_t st, const char* nm) {
+    if constexpr (mix_has_energy<Mix>::value)      // (the group-parallel kernel has no energy partials: xfused_energy never routes here)
+        return fail(c, OFDFT_EINVAL, "%s: the group-parallel x pass does not integrate energies", nm);
     constexpr int G = NIN > NOUT ? NIN : NOUT;
     using Cfg = XfCfg<LEN, G, NOUT>;
     cplx* tw;
@@ -37,6 +39,7 @@ int launch_xfused_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout
     main.blk0 = line0 / Cfg::LPW;
     const int mb = (main.nlines - line0 + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
     c->xpass_kinds |= OFDFT_XPASS_GROUP;
+    c->xpass_blocks = mb + rb;
     OFDFT_LAUNCH(c, st, nm, (xfused_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb,
                  gk, tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;
@@ -74,6 +77,7 @@ int launch_xw_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
     main.blk0 = line0 / Cfg::LPB;
     const int mb = (main.nlines - line0 + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
     c->xpass_kinds |= OFDFT_XPASS_WAVE;
+    c->xpass_blocks = mb + rb;
     OFDFT_LAUNCH(c, st, nm, (xw_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb, gk,
                  (const cplx*)tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;
@@ -128,6 +132,7 @@ int launch_xc_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
         }
     }
     c->xpass_kinds |= Cfg::NL == 2 ? OFDFT_XPASS_CROSS2 : OFDFT_XPASS_CROSS1;
+    c->xpass_blocks = mb + rb;
     OFDFT_LAUNCH(c, st, nm, (xc_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), lds, io, main, rem, mb, gk,
                  (const cplx*)tw, mix, XfStride{lay.se_out, lay.tse});
     return 0;
@@ -191,6 +196,30 @@ int xfused(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const c
 #undef X
     }
     return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n0g);
+}
+
+// a pass whose mix integrates an energy (mix_has_energy): the cross-wave or wave-local kernel only (xfused_energy_serves: xpass_a.hip)
+template <int NIN, class Mix>
+int xfused_energy(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const char* nm) {
+    const XfLayout lay{};
+    if (xc_serves<NIN, 1>(c)) {
+        switch (c->n0g) {
+            case 128: return launch_xc_t<128, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+            case 256: return launch_xc_t<256, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+            case 512: return launch_xc_t<512, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+            case 1024: return launch_xc_t<1024, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        }
+    }
+    switch (c->n0g) {
+        case 8: return launch_xw_t<8, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 16: return launch_xw_t<16, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 32: return launch_xw_t<32, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 64: return launch_xw_t<64, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 128: return launch_xw_t<128, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 256: return launch_xw_t<256, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+        case 512: return launch_xw_t<512, NIN, 1, Mix>(c, io, mix, lay, st, nm);
+    }
+    return fail(c, OFDFT_EINVAL, "%s: no energy-integrating x pass for %d-point lines", nm, c->n0g);
 }
 
 }  // namespace eng

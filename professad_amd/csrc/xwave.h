@@ -84,6 +84,26 @@ template <class Mix, class = void> struct mix_has_fold : std::false_type {};
 template <class Mix> struct mix_has_fold<Mix, std::void_t<decltype(std::declval<const Mix&>().fold_n0)>> : std::true_type {};
 template <class Mix, class = void> struct mix_coef_count { static constexpr int N = 0; };
 template <class Mix> struct mix_coef_count<Mix, std::void_t<decltype(Mix::kTableReals)>> { static constexpr int N = Mix::kTableReals; };
+// mixes that also integrate an energy over the spectrum they read (MixDerivAH: E_H by Parseval) -- each thread sums its k-points
+// mix.energy(), the workgroup's total goes to mix.epart[blockIdx.x]
+template <class Mix, class = void> struct mix_has_energy : std::false_type {};
+template <class Mix> struct mix_has_energy<Mix, std::void_t<decltype(Mix::kEnergy)>> : std::bool_constant<Mix::kEnergy> {};
+// the workgroup sum of v -> out[blockIdx.x], through the kernel's own (dynamic) LDS once every wave is done with it
+template <int TPB>
+__device__ __forceinline__ void xpart_store(acc_t v, acc_t* __restrict__ out, real* lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    acc_t* red = reinterpret_cast<acc_t*>(lds);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        acc_t t = 0.0;
+#pragma unroll
+        for (int w = 0; w < TPB / 64; ++w) t += red[w];
+        out[blockIdx.x] = t;
+    }
+}
 
 template <int NIN, int NOUT, int O, int I, class Mix>
 __device__ __forceinline__ void xw_accumulate(real& acr, real& aci, const cplx (&in)[NIN], const Mix& mix, int x, int y, int kz,
@@ -208,6 +228,7 @@ __global__ __launch_bounds__(XwCfg<LEN>::TPB, (NIN + NOUT > 3 ? OFDFT_XW_WAVES :
         exchange_sync<true>();
     });
     // ---- mix, in registers: the lane owns k-points x = j + P q of its line in every spectrum
+    acc_t eacc = 0.0;
 #pragma unroll
     for (int q = 0; q < E; ++q) {
         cplx in[NIN], out[NOUT];
@@ -215,6 +236,7 @@ __global__ __launch_bounds__(XwCfg<LEN>::TPB, (NIN + NOUT > 3 ? OFDFT_XW_WAVES :
         for (int I = 0; I < NIN; ++I) in[I] = a[I][q];
         if constexpr (NC > 0) mix.apply(out, in, cfs[q]);
         else xw_outputs<NIN, NOUT, 0, Mix>(out, in, mix, j + P * q, y, kz, b0 + q * tqstep, tloff);
+        if constexpr (mix_has_energy<Mix>::value) eacc += mix.energy(in, j + P * q, y, kz);
 #pragma unroll
         for (int O = 0; O < NOUT; ++O) a[O][q] = out[O];
     }
@@ -231,6 +253,7 @@ __global__ __launch_bounds__(XwCfg<LEN>::TPB, (NIN + NOUT > 3 ? OFDFT_XW_WAVES :
             }
         }
     });
+    if constexpr (mix_has_energy<Mix>::value) xpart_store<Cfg::TPB>(eacc, mix.epart, lds);
 }
 
 }  // namespace ofdft

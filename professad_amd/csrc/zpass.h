@@ -756,6 +756,8 @@ struct ZCombineArgs {
     const cplx* gw[3];
     const cplx* div;
     const cplx* div2;         // split-derivative form: the D_b part of the divergence (added to div)
+    const acc_t* eh_part;     // potential-spectrum form: E_H partials of the divergence x pass (the Hartree potential rides in div)
+    long long eh_rows;        // ... their count (folded into the Hartree energy slot by the workgroups of this kernel)
     real* v_out;
     const real* v_part;     // split form: the WGC99 potential computed by zi_wgc_kernel (then u / gw are not read here)
     int v_part_deferred;    // closure form: v_part is NOT added here (zi_wgc_kernel runs beside this kernel; chi_grad adds it, and
@@ -942,7 +944,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
     };
     request_after(std::integral_constant<int, -1>{});
-    if (a.mask & 2u) {                                   // Hartree  functionals.py:72
+    if ((a.mask & 2u) && a.vh) {                         // Hartree  functionals.py:72  (vh == null: in div, see eh_part)
         take_row(std::integral_constant<int, 0>{}, a.vh);
         real e = 0.0;
 #pragma unroll
@@ -1077,6 +1079,10 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
     if (!z.valid) {
 #pragma unroll
         for (int s = 0; s < kCombineScalars; ++s) acc[s] = 0.0;
+    }
+    if (a.eh_part && g.blk0 + blockIdx.x == 0) {
+        // E_H from the divergence x pass: its partials join the Hartree slot of the first workgroup (the same order in an x-chunked loop)
+        for (long long i = threadIdx.x; i < a.eh_rows; i += blockDim.x) acc[1] += a.eh_part[i];
     }
     if (a.v_out) z_store_real<M, E>(vacc, z, a.v_out);
     block_reduce_store<kCombineScalars>(acc, partial + (long long)g.blk0 * kCombineScalars);
