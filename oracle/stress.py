@@ -156,6 +156,28 @@ def pbe(box, n, do_x=True, do_c=True):
     return np.mean(f - n * dfdn) * np.eye(3) + t2
 
 
+def ggak(box, n, kind='lkt', mu=40 / 27):
+    """Pauli part of a kinetic GGA without q-dependence, f = tau_TF F(s) (LKT or Pauli-Gaussian, closed_form.ggak_pointwise;
+    functionals.py:309-403), derived here (the reference has no closed form).  Same strain rule as pbe (:393-472):
+        sigma_ij = delta_ij mean(f - n f_n - 2 g f_g) - 2 mean(f_g d_i n d_j n),   g = |grad n|^2"""
+    g = Grid(box, n.shape)
+    d = _grad(g, n)
+    gn2 = d[0] ** 2 + d[1] ** 2 + d[2] ** 2
+    f, dfdn, dfdg = Evaluator(g).ggak_pointwise(n, gn2, kind, mu)
+    t2 = _sym([-2 * np.mean(((gn2 if i == j else 0.0) + d[i] * d[j]) * dfdg) for i, j in PAIRS])
+    return np.mean(f - n * dfdn) * np.eye(3) + t2
+
+
+def vwgtf(box, n, kind=1):
+    """GTF part of vWGTF1 / vWGTF2 (functionals.py:251-306), derived here (the reference has no closed form).
+    E = int G(n / n0) tau_TF(n) with n0 = round(N_e) / Omega: under a strain at fixed electron number n and n0 both scale as
+    1/J, so G is invariant and E ~ J^(-2/3) like Thomas-Fermi:  sigma_ij = -(2/3) E / Omega delta_ij"""
+    g = Grid(box, n.shape)
+    ev = Evaluator(g)
+    E = ev.term('vwgtf%d' % kind, n)[0] - ev.vw(n)[0]
+    return -2 / 3 * E / g.vol * np.eye(3)
+
+
 def pauli_gaussian(box, n, mu=40 / 27, beta=0.25, lam=0.0, sigma=0.0):
     """Pauli part of the Pauli-Gaussian family with the q-dependent terms (functionals.py:336-403), derived here (the
     reference has no closed form).  For f(n, g = |grad n|^2, l = lap n) a strain at fixed electron number gives

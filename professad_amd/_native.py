@@ -31,6 +31,8 @@ Q_YFWD_FUSED = 10
 Q_XPASS_KINDS = 11
 # bits of ofdft_query(Q_XPASS_KINDS): the fused x-pass kernel families of the last energy call
 XPASS_GROUP, XPASS_WAVE, XPASS_CROSS1, XPASS_CROSS2, XPASS_CHIRPZ = 1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4
+OPT_BLUESTEIN = 5
+OPT_GGA_SPLIT = 6
 OPT_GRAPH = 7
 OPT_XWAVE = 8
 OPT_MIXED_RADIX = 9

@@ -36,6 +36,10 @@ def test_header_constants_match_python_mirror():
     assert len(set(queries.values())) == len(queries)
     for nm in ('GROUP', 'WAVE', 'CROSS1', 'CROSS2', 'CHIRPZ'):
         assert getattr(N, 'XPASS_' + nm) == 1 << int(bits['XPASS_' + nm]), nm
+    options = {nm: int(v) for nm, v in re.findall(r'#define OFDFT_OPT_([A-Z0-9_]+)\s+(\d+)', header)}
+    for nm in dir(N):
+        if nm.startswith('OPT_'):
+            assert options[nm[4:]] == getattr(N, nm), nm
 
 
 def test_error_paths_without_gpu():

@@ -150,7 +150,10 @@ def test_stress_oracle():
                'wgc99': st.tf(box, den) + st.vw(box, den) + st.wgc99_nl(box, den),
                'pgsl025': st.vw(box, den) + st.pauli_gaussian(box, den),
                'pgslr': st.vw(box, den) + st.pauli_gaussian(box, den, 40 / 27, 0.25, 0.4, 0.2),
-               'wts_exp': st.wang_teter_style(box, den)}
+               'wts_exp': st.wang_teter_style(box, den),
+               'lkt': st.vw(box, den) + st.ggak(box, den, 'lkt'),
+               'pgs': st.vw(box, den) + st.pauli_gaussian(box, den, 40 / 27, beta=0.0),
+               'vwgtf1': st.vw(box, den) + st.vwgtf(box, den, 1), 'vwgtf2': st.vw(box, den) + st.vwgtf(box, den, 2)}
         for k, v in got.items():
             ref = g['%s_%s' % (case, k)]
             assert np.abs(v - ref).max() <= 1e-11 * np.abs(ref).max(), (case, k)

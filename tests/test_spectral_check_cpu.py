@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import spectral_check as sc
+import test_chirpz_matrix_gpu as C
 import test_extent_matrix_gpu as M
+from oracle import ions as oi
 
 SHAPE, CELL = (128, 32, 64), 'ortho'
 REL = {'f64': 1e-6, 'f32': 1e-2}
@@ -57,7 +59,55 @@ def test_probe_points_are_the_locations_they_name():
 
 
 def _shapes():
-    return [(s, c) for s, c in M.MATRIX] + [((256, 256, 256), 'ortho'), ((512, 256, 128), 'tri')]
+    return ([(s, c) for s, c in M.MATRIX] + [((256, 256, 256), 'ortho'), ((512, 256, 128), 'tri')]
+            + [(s, c) for s, c in C.MATRIX] + [((255, 255, 255), 'ortho')])
+
+
+# chirp-z shapes with odd extents on every axis in turn (x odd / y even, n2 odd, n0 small enough that n0 // 2 + 5 wraps)
+ODD = [((15, 17, 19), 'tri'), ((255, 14, 26), 'ortho'), ((10, 383, 14), 'ortho'), ((12, 10, 509), 'tri'), ((515, 6, 8), 'ortho')]
+
+
+@pytest.mark.parametrize('shape', [s for s, _ in ODD] + [(53, 53, 53), (65, 30, 67), (257, 9, 20)])
+def test_probe_points_on_odd_extents(shape):
+    """on an odd extent the 'Nyquist' probes are the highest positive frequency ((n - 1) / 2) and the folded half starts at the
+    most negative one (-(n - 1) / 2); for odd n2 the last kz plane of the half spectrum has full weight (its partner -kz is
+    not stored) and is the z probe.  Every probe lies inside the half spectrum and names the location it stands for."""
+    n0, n1, n2 = shape
+    pts = sc.probe_points(shape)
+    f0, f1 = np.fft.fftfreq(n0, 1.0 / n0), np.fft.fftfreq(n1, 1.0 / n1)
+    for k in pts.values():
+        assert 0 <= k[0] < n0 and 0 <= k[1] < n1 and 0 <= k[2] <= n2 // 2, (shape, pts)
+    assert abs(f0[pts['x_nyquist'][0]]) == n0 // 2                   # the largest |kx| (the Nyquist index when n0 is even)
+    assert f0[pts['x_folded_half'][0]] == -((n0 - 1) // 2)           # the most negative kx that is not the Nyquist index
+    assert abs(f1[pts['y_nyquist'][1]]) == n1 // 2
+    assert pts['z_nyquist_plane'][2] == n2 // 2 == np.fft.rfftfreq(n2).size - 1          # the last stored kz plane
+    assert oi.half_weights(shape)[pts['z_nyquist_plane'][2]] == (1.0 if n2 % 2 == 0 else 2.0)
+    assert pts['kz0_plane_kx_upper_half'][2] == 0 and f0[pts['kz0_plane_kx_upper_half'][0]] < 0
+    assert all(k % 32 for k in pts['off_the_32_tiling'])
+
+
+@pytest.mark.parametrize('shape,cell', ODD, ids=['%dx%dx%d-%s' % (s + (c,)) for s, c in ODD])
+def test_single_k_point_errors_are_rejected_on_odd_extents(shape, cell):
+    """perturb on odd extents: a probe is its own Hermitian partner only at k = 0 along an odd axis, so every probe here gets
+    one partner (kz = 0 plane) or none (kz > 0: the partner is not in the half spectrum, irfftn supplies it) and the change
+    reaches the full spectrum unscaled; the check rejects it at both precisions and accepts round-off"""
+    o = M.oracle(shape, cell, 'wgc99_pbe')
+    for vo, vok in ((o['v'], o['vk']), (o['g'], o['gk'])):
+        for p in ('f64', 'f32'):
+            noisy = vo.astype(np.float32).astype(np.float64) if p == 'f32' else vo * (1 + 4e-16)
+            sc.check(noisy, vo, p, vok=vok)
+            for name, k in sc.probe_points(shape).items():
+                bad = sc.perturb(vo, k, REL[p], sc.TAU[p], vok)
+                dk = sc.spectrum(bad) - vok
+                big = np.abs(dk) > 1e-3 * np.abs(dk).max()
+                partner = ((-k[0]) % shape[0], (-k[1]) % shape[1], k[2])
+                assert big[k] and np.count_nonzero(big) == (2 if k[2] == 0 or 2 * k[2] == shape[2] else 1), (name, k)
+                if k[2] == 0:
+                    assert big[partner] and np.isclose(dk[partner], np.conj(dk[k]))
+                # the measured per-k error is the requested one: the change is neither halved by symmetrisation nor doubled
+                got = sc.kspace_error(bad, vo, sc.TAU[p], vok)
+                assert abs(got - REL[p]) <= 1e-3 * REL[p], (shape, name, p, got)
+                assert _rejected(bad, vo, p, vok), (shape, name, p, sc.errors(bad, vo, p, vok))
 
 
 @pytest.mark.parametrize('shape,cell', _shapes(), ids=['%dx%dx%d-%s' % (s + (c,)) for s, c in _shapes()])
