@@ -73,7 +73,13 @@ typedef struct ofdft_ctx ofdft_ctx;
                                            beta = lambda = sigma = 0 (F = exp(-mu s^2)); the vW part is OFDFT_VW */
 #define OFDFT_VWGTF         (1u << 13)  /* local Pauli term of vWGTF1 / vWGTF2, int tau_TF G(n/n0), functionals.py:251-306;
                                            n0 = round(N_e)/vol; the vW part is OFDFT_VW */
-#define OFDFT_NTERMS        14
+#define OFDFT_NLK           (1u << 14)  /* Wang-Teter-shaped nonlocal term with a tabulated, density-independent kernel:
+                                           sum_{i<=j} int n^(e_i) (K_ij * n^(e_j)), K_ij(|k|) built once per (cell, round(N_e), parameters) into a
+                                           per-k-point table; OFDFT_P_NLK_KIND selects KGAP functionals.py:1106-1171, MiGenovaPavanello :1370-1451
+                                           or XuWangMa :1456-1498 (the vW and TF parts are OFDFT_VW / OFDFT_TF).  Single-GPU contexts; not together
+                                           with OFDFT_WT_NL / OFDFT_WGC99_NL (they share the nonlocal chain's buffers); ofdft_stress serves KGAP and XWM, and
+                                           refuses MGP as the reference's get_stress does */
+#define OFDFT_NTERMS        15
 
 /* params[] slots for ofdft_set_terms (missing trailing slots keep their defaults) */
 #define OFDFT_P_WT_ALPHA    0   /* default 5/6 */
@@ -89,10 +95,14 @@ typedef struct ofdft_ctx ofdft_ctx;
 #define OFDFT_P_GGAK_SIGMA  10  /* PGSLr): one more spectrum each way in the GGA chain; every pipeline, slabs and stress     */
 #define OFDFT_P_VWGTF_KIND  11  /* 1 = vWGTF1 (default), 2 = vWGTF2 */
 #define OFDFT_P_WTS_KIND    12  /* Pauli-positivity stabilisation of WangTeterStyleFunctional (functionals.py:728-782) for a term
-                                   set with OFDFT_TF and OFDFT_WT_NL: T = T_TF f(X), X = T_NL / (f'(0) T_TF).  0 (default): f(x) = 1 + x,
+                                   set with OFDFT_TF and OFDFT_WT_NL (or OFDFT_NLK: KGAP's f argument): T = T_TF f(X), X = T_NL / (f'(0) T_TF).  0 (default): f(x) = 1 + x,
                                    i.e. the plain sum T_TF + T_NL; 1: f(x) = exp(x).  Then E_terms[TF] reports T_TF f(X), E_terms[WT_NL]
                                    zero, the potential and the stress carry the weights f - f' X and f'(X) / f'(0).  Single-GPU contexts. */
-#define OFDFT_NPARAMS       13
+#define OFDFT_P_NLK_KIND    13  /* kernel of OFDFT_NLK: 1 = KGAP, 2 = Mi-Genova-Pavanello, 3 = Xu-Wang-Ma (0, the default, is refused with the bit set) */
+#define OFDFT_P_NLK_P0      14  /* KGAP: E_gap [eV] (0 -> alpha = beta = 1/2 and the Lindhard kernel: Smargiassi-Madden); MGP: a; XWM: kappa */
+#define OFDFT_P_NLK_P1      15  /* MGP: b */
+#define OFDFT_P_NLK_P2      16  /* reserved (0) */
+#define OFDFT_NPARAMS       17
 
 /* ofdft_query selectors */
 #define OFDFT_Q_FFT_COUNT        0  /* 3-D FFTs executed by the last energy call              */

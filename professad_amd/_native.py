@@ -18,12 +18,22 @@ F64, F32 = 0, 1
 TERM_BITS = {
     'ion_electron': 1 << 0, 'hartree': 1 << 1, 'tf': 1 << 2, 'vw': 1 << 3, 'wt_nl': 1 << 4, 'wgc99_nl': 1 << 5,
     'lda_x': 1 << 6, 'pz_c': 1 << 7, 'pw_c': 1 << 8, 'chachiyo_c': 1 << 9, 'pbe_x': 1 << 10, 'pbe_c': 1 << 11,
-    'gga_k': 1 << 12, 'vwgtf': 1 << 13,
+    'gga_k': 1 << 12, 'vwgtf': 1 << 13, 'nlk': 1 << 14,
 }
 TERM_ORDER = ['ion_electron', 'hartree', 'tf', 'vw', 'wt_nl', 'wgc99_nl', 'lda_x', 'pz_c', 'pw_c', 'chachiyo_c',
-              'pbe_x', 'pbe_c', 'gga_k', 'vwgtf']
-NTERMS = 14
-NPARAMS = 13
+              'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk']
+NTERMS = 15
+NPARAMS = 17
+NLK_KGAP, NLK_MGP, NLK_XWM = 1, 2, 3      # OFDFT_P_NLK_KIND
+NTERMS_ALWAYS = 14      # per-term results always carry these terms (zero when not in the set); a later one only while it is set
+
+
+def per_term(values, mask):
+    """E_terms[] / sigma_terms[] of the ABI as the {term name: value} dict the Python layer returns: the first NTERMS_ALWAYS
+    terms always, each later term ('nlk') only when its bit is in `mask` -- so a term set without it gets the entries it
+    always got.  (Consumers compare the per-term arrays of one term set from build to build -- bench.py --dump-outputs writes
+    list(E.values()) -- so the entries of a term set that does not use a new term must not change when one is added.)"""
+    return {nm: values[i] for i, nm in enumerate(TERM_ORDER) if i < NTERMS_ALWAYS or (mask & TERM_BITS[nm])}
 Q_FFT_COUNT, Q_WORKSPACE_BYTES, Q_FAST_PATH, Q_KERNEL_MS, Q_LAUNCH_COUNT, Q_YPASS_COUNT, Q_GRAPH_REPLAYS, Q_RESIDENT_EVALS = 0, 1, 2, 3, 4, 5, 6, 7
 Q_RESIDENT_FALLBACKS = 8
 Q_XCHG_CHUNKS = 9

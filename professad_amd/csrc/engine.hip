@@ -306,6 +306,62 @@ int ensure_wgc_tables(ofdft_ctx* c, long long nel_rounded, hipStream_t st, doubl
     c->wgc_valid = true;
     return 0;
 }
+
+// The kernel columns of OFDFT_NLK (pointwise_kernels.h: nlk_table_kernel) for n0 = round(N_e) / vol.  Rebuilt when the cell, round(N_e)
+// (XWM: N_e itself, whose un-rounded value sets eta), the kind or a parameter changes -- for MGP that is what a FRESH instance of the
+// reference computes (its own instance keeps an earlier 1-D table while it still covers eta_max).  A rebuild bumps the
+// context's version: a captured closure graph reads the table it was captured with.
+// XWM's key holds N_e bit for bit, because its eta is |k| / (2 k_F(N_e / vol)) with the un-rounded count.  ofdft_energy_potential
+// takes N_e from a device sum of the density, the closure from its caller; for one density the two differ in the last bits, so
+// a caller that ALTERNATES the two entry points with XWM rebuilds the table (and re-captures its graph) on every switch.
+// Results are those of the N_e each call was given; an optimisation loop, which stays with one entry point and one N_e, builds once.
+int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st) {
+    const NlPow p = nl_pow(c);
+    const long long nel_r = std::llround(nel);
+    if (c->nlk_valid && c->nlk_key_nel == nel_r && (p.kind != NLK_XWM || c->nlk_key_nel_exact == nel)) return 0;
+    if (nel_r < 1) return fail(c, OFDFT_EINVAL, "OFDFT_NLK: the electron number %g rounds to zero (n0 = round(N_e) / vol)", nel);
+    const double n0 = (double)nel_r / c->vol, kf = std::cbrt(3.0 * kPi * kPi * n0);
+    const double ctf = (double)0.3L * std::pow(3.0 * kPi * kPi, (double)2 / 3);
+    const double x0 = c->params[OFDFT_P_NLK_P0], x1 = c->params[OFDFT_P_NLK_P1];
+    const int ncol = p.kind == NLK_XWM ? 2 : 1;
+    real* tab;
+    if (int rc = get_ws(c, "t:nlk", sizeof(real) * (size_t)c->g.total * ncol, (void**)&tab)) return rc;
+    NlkTab t{};
+    t.kind = p.kind;
+    t.inv2kf = 1.0 / (2.0 * kf);
+    if (p.kind == NLK_KGAP) {
+        const double ev_per_ha = (double)4.3597447222071e-18L / (double)1.602176634e-19L;     // functionals.py:13-14                      // professad's eV_per_Ha
+        t.pref = 5.0 / (9.0 * p.al * p.be * std::pow(n0, p.al + p.be - kFiveThirds));
+        t.p1 = 2.0 * (x0 / ev_per_ha) / (kf * kf);
+    } else if (p.kind == NLK_MGP) {
+        if (!c->d_nlk_w) HIP_TRY(c, hipMalloc((void**)&c->d_nlk_w, sizeof(double) * (kMgpNodes + 1)));
+        unsigned long long* k2max_dev = reinterpret_cast<unsigned long long*>(c->d_nlk_w + kMgpNodes);
+        HIP_TRY(c, hipMemsetAsync(k2max_dev, 0, sizeof(unsigned long long), st));
+        OFDFT_LAUNCH(c, st, "nlk_table", nlk_k2max_kernel, dim3(grid_for(c->g.total, 256, 1024)), dim3(256), 0, c->kg, k2max_dev);
+        double k2max = 0.0;
+        HIP_TRY(c, hipMemcpyAsync(&k2max, k2max_dev, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        t.p3 = (double)1.2L * (std::sqrt(k2max) * t.inv2kf);                      // generate_kernel(1.2 eta_max)
+        OFDFT_LAUNCH(c, st, "nlk_mgp_quad", nlk_mgp_table_kernel, dim3(kMgpNodes), dim3(256), 0, t.p3, 1.0 / ctf, c->d_nlk_w);
+        t.p1 = (double)0.6L * 4.0 * kPi * x0 / ctf;
+        t.p2 = x1;
+        t.w = c->d_nlk_w;
+    } else {
+        const double cx = kPi * kPi / std::cbrt(3.0 * kPi * kPi), n2k = std::pow(n0, 2.0 * x0);
+        t.inv2kf = 1.0 / (2.0 * std::cbrt(3.0 * kPi * kPi * (nel / c->vol)));
+        t.pref = 2.0 * 18.0 / ((6.0 * x0 + 5.0) * (6.0 * x0 + 5.0)) * cx / n2k / ctf;
+        t.p1 = cx / (6.0 * n0) / n2k / ctf;
+        t.p2 = n0 / (p.al * p.al);
+        t.p3 = 1.0 / (p.al * p.be);
+    }
+    OFDFT_LAUNCH(c, st, "nlk_table", nlk_table_kernel, dim3(grid_for(c->g.total, 256, 4096)), dim3(256), 0, tab,
+                 ncol == 2 ? tab + c->g.total : (real*)nullptr, c->kg, t);
+    c->nlk_key_nel = nel_r;
+    c->nlk_key_nel_exact = nel;
+    c->nlk_valid = true;
+    c->version++;
+    return 0;
+}
 }  // namespace eng
 namespace {
 
@@ -369,6 +425,7 @@ int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, do
     if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
     if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
     if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
+    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
     *vn_int = sums[8] * dV;
     return 0;
 }
@@ -390,7 +447,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
 
     defer = defer && !wts_active(c);
     double nsum = 0.0;
-    if (nel_known <= 0.0 && (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF)))
+    if (nel_known <= 0.0 && (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF | OFDFT_NLK)))
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
     const double nel = nel_known > 0.0 ? nel_known : nsum * inv_n * c->vol;       // mean(den) * vol   functionals.py:634,646,952
 
@@ -399,7 +456,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     ca.vext = vext;
     ca.v_out = v_out;
     ca.npts = npts;
-    ca.mask = mask;
+    ca.mask = combine_mask(c);
     ca.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
     ca.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;      // n0 = round(N_e) / vol (functionals.py:268-270)
     double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
@@ -412,9 +469,12 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     // pass for up to kBsBatch arrays -- small odd grids are bound by their launch count).  Phase A: pointwise inputs + forward
     // batch; B: spectral multiplies; C: inverse batches; D: the GGA mid stage and its flux / divergence transforms.
     const bool has_n = mask & (OFDFT_HARTREE | kGgaAny), has_h = mask & OFDFT_HARTREE, has_g = mask & kGgaAny, has_vw = mask & OFDFT_VW,
-               has_wt = mask & OFDFT_WT_NL;
-    const double wal = c->params[OFDFT_P_WT_ALPHA], wbe = c->params[OFDFT_P_WT_BETA];
-    const bool wt2 = has_wt && wal != wbe;
+               has_wt = mask & (OFDFT_WT_NL | OFDFT_NLK);
+    const NlPow nlp = nl_pow(c);
+    const double wal = nlp.e_a, wbe = nlp.e_b;      // powers behind s_wa / s_wb (Wang-Teter: alpha, beta)
+    const bool wt2 = nlp.two;
+    if (nlp.nlk)
+        if (int rc = ensure_nlk_table(c, nel, st)) return rc;
     real *t_sqrt = nullptr, *t_pb = nullptr, *t_pa = nullptr;
     cplx *s_vw = nullptr, *s_wb = nullptr, *s_wa = nullptr, *s4 = nullptr;
     real *vh = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *dfdn = nullptr, *dv = nullptr, *lapn = nullptr, *lap = nullptr,
@@ -548,7 +608,34 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
             const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
             const double pref = 5.0 / (9.0 * wal * wbe * std::pow(nbar, wal + wbe - kFiveThirds));
             if (int rc = real_ws(c, "conv_b", &cb)) return rc;
-            if (!xm)
+            if (nlp.nlk) {                // the kernel comes from the table: one multiply kernel, or one chirp-z x pass over both spectra
+                if (wt2 && !nlp.sym) {    // KGAP: both spectra times the one column
+                    if (!xm) {
+                        OFDFT_LAUNCH(c, st, "spec_nlk_mix", spec_nlk_mix_kernel, dim3(sp_grid), dim3(256), 0, s_wb, (cplx*)nullptr, nlk_col(c, 0), (const real*)nullptr, c->g.total);
+                        OFDFT_LAUNCH(c, st, "spec_nlk_mix", spec_nlk_mix_kernel, dim3(sp_grid), dim3(256), 0, s_wa, (cplx*)nullptr, nlk_col(c, 0), (const real*)nullptr, c->g.total);
+                    } else {
+                        for (cplx* sp : {s_wb, s_wa}) {
+                            const cplx* xi[1] = {sp};
+                            cplx* xo[1] = {sp};
+                            if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixNlk<1>{nlk_col(c, 0), nullptr}, st)) return rc;
+                        }
+                    }
+                } else if (wt2) {         // XWM
+                    if (!xm)
+                        OFDFT_LAUNCH(c, st, "spec_nlk_mix", spec_nlk_mix_kernel, dim3(sp_grid), dim3(256), 0, s_wb, s_wa, nlk_col(c, 0), nlk_col(c, 1), c->g.total);
+                    else {
+                        const cplx* xi[2] = {s_wb, s_wa};
+                        cplx* xo[2] = {s_wb, s_wa};
+                        if (int rc = bluestein_xmix<2, 2>(c, xi, xo, MixNlk<2>{nlk_col(c, 0), nlk_col(c, 1)}, st)) return rc;
+                    }
+                } else if (!xm) {
+                    OFDFT_LAUNCH(c, st, "spec_nlk_mix", spec_nlk_mix_kernel, dim3(sp_grid), dim3(256), 0, s_wb, (cplx*)nullptr, nlk_col(c, 0), (const real*)nullptr, c->g.total);
+                } else {
+                    const cplx* xi[1] = {s_wb};
+                    cplx* xo[1] = {s_wb};
+                    if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixNlk<1>{nlk_col(c, 0), nullptr}, st)) return rc;
+                }
+            } else if (!xm)
                 OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_LINDHARD>), dim3(sp_grid), dim3(256), 0, s_wb, s_wb, c->kg, pref,
                                    1.0 / (2.0 * kf));
             else {
@@ -561,7 +648,9 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
             ca.conv_a = nullptr;
             if (wt2) {
                 if (int rc = real_ws(c, "conv_a", &cva)) return rc;
-                if (!xm)
+                if (nlp.nlk) {
+                    // (mixed above)
+                } else if (!xm)
                     OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_LINDHARD>), dim3(sp_grid), dim3(256), 0, s_wa, s_wa, c->kg, pref,
                                        1.0 / (2.0 * kf));
                 else {
@@ -572,10 +661,11 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
                 iin[ni] = s_wa; iout[ni++] = cva;
                 ca.conv_a = cva;
             }
-            ca.wt_alpha = wal;
-            ca.wt_beta = wbe;
-            ca.wt_nbar_pa = std::pow(nbar, wal);
-            ca.wt_is_56 = (wal == kFiveSixths && wbe == kFiveSixths) ? 1 : 0;
+            ca.wt_alpha = nlp.al;
+            ca.wt_beta = nlp.be;
+            ca.wt_nbar_pa = nlp.nlk ? 0.0 : std::pow(nbar, nlp.al);     // (the tabulated kernels are 0 at k = 0 and the reference subtracts nothing)
+            ca.wt_is_56 = (nlp.al == kFiveSixths && nlp.be == kFiveSixths) ? 1 : 0;
+            ca.wt_sym = nlp.sym;
         }
         for (int b0 = 0; b0 < ni; b0 += 4)
             if (int rc = (xm ? bluestein_inv_yz_multi(c, iin + b0, iout + b0, std::min(4, ni - b0), inv_n, st)
@@ -672,7 +762,7 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
     if ((mask & OFDFT_ION_ELECTRON) && !vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
 
     double nsum = 0.0;
-    if (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF))
+    if (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF | OFDFT_NLK))
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
     const double nel = nsum * inv_n * c->vol;
 
@@ -681,7 +771,7 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
     ca.vext = vext;
     ca.v_out = v_out;
     ca.npts = npts;
-    ca.mask = mask;
+    ca.mask = combine_mask(c);
     ca.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
     ca.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;      // n0 = round(N_e) / vol (functionals.py:268-270)
     double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
@@ -782,6 +872,43 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
         ca.wt_beta = be;
         ca.wt_nbar_pa = std::pow(nbar, al);
         ca.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
+    }
+    if (mask & OFDFT_NLK) {          // the Wang-Teter stages above with the kernel from the table (one pass over both spectra for XWM)
+        const NlPow nlp = nl_pow(c);
+        if (int rc = ensure_nlk_table(c, nel, st)) return rc;
+        real *tmp, *cb, *cva = nullptr;
+        if (int rc = real_ws(c, "t0", &tmp)) return rc;
+        if (int rc = real_ws(c, "conv_b", &cb)) return rc;
+        if (int rc = spec_ws(c, sn[1], &s[1])) return rc;
+        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.e_b);
+        if (int rc = fwd_zy(c, tmp, s[0], st)) return rc;
+        if (nlp.two) {
+            if (int rc = real_ws(c, "conv_a", &cva)) return rc;
+            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.e_a);
+            if (int rc = fwd_zy(c, tmp, s[1], st)) return rc;
+        }
+        if (nlp.sym) {
+            XfIo io{};
+            io.in[0] = io.out[0] = s[0];
+            io.in[1] = io.out[1] = s[1];
+            if (int rc = xfused<2, 2>(c, io, MixNlk<2>{nlk_col(c, 0), nlk_col(c, 1)}, st, "xfused_nlk")) return rc;
+        } else {
+            for (int k = 0; k < (nlp.two ? 2 : 1); ++k) {
+                XfIo io{};
+                io.in[0] = io.out[0] = s[k];
+                if (int rc = xfused<1, 1>(c, io, MixNlk<1>{nlk_col(c, 0), nullptr}, st, "xfused_nlk")) return rc;
+            }
+        }
+        if (int rc = inv_yz(c, s[0], cb, inv_n, st)) return rc;
+        if (nlp.two)
+            if (int rc = inv_yz(c, s[1], cva, inv_n, st)) return rc;
+        ca.conv_b = cb;
+        ca.conv_a = cva;
+        ca.wt_alpha = nlp.al;
+        ca.wt_beta = nlp.be;
+        ca.wt_nbar_pa = 0.0;
+        ca.wt_is_56 = (nlp.al == kFiveSixths && nlp.be == kFiveSixths) ? 1 : 0;
+        ca.wt_sym = nlp.sym;
     }
     if (mask & OFDFT_WGC99_NL) {
         const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
@@ -889,7 +1016,7 @@ int ofdft_create_dist(ofdft_ctx** out, int n0g, int n1g, int n2, int dtype, int 
     xchg_chunks_set(c, 0);
     const double s5 = std::sqrt(5.0);
     const double defaults[OFDFT_NPARAMS] = {kFiveSixths, kFiveSixths, (5.0 + s5) / 6.0, (5.0 - s5) / 6.0, (double)27 / 10, 1.0, 0.0, (double)40 / 27,
-                                            0.0, 0.0, 0.0, 1.0, 0.0};
+                                            0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     std::memcpy(c->params, defaults, sizeof(defaults));
     DeviceScope device_scope_(device_id);
     hipError_t e = device_scope_.err;
@@ -942,6 +1069,7 @@ void ofdft_destroy(ofdft_ctx* c) {
     if (c->d_scal) (void)hipFree(c->d_scal);
     if (c->h_partial) (void)hipHostFree(c->h_partial);
     if (c->d_wgc_coef) (void)hipFree(c->d_wgc_coef);
+    if (c->d_nlk_w) (void)hipFree(c->d_nlk_w);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     delete c->zr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -990,6 +1118,7 @@ int ofdft_set_cell(ofdft_ctx* c, const double box[9]) {
     c->dV = c->vol / (double)c->npts_g;
     c->cell_set = true;
     c->wgc_valid = false;
+    c->nlk_valid = false;
     return OFDFT_OK;
 }
 
@@ -997,8 +1126,21 @@ int ofdft_set_terms(ofdft_ctx* c, uint32_t mask, const double* params, int npara
     if (!c) return OFDFT_EINVAL;
     if (mask == 0 || (mask >> OFDFT_NTERMS)) return fail(c, OFDFT_EINVAL, "bad term mask 0x%x", mask);
     if (nparams < 0 || nparams > OFDFT_NPARAMS || (nparams > 0 && !params)) return fail(c, OFDFT_EINVAL, "bad params");
+    if (mask & OFDFT_NLK) {        // checked before anything is stored: a refused call leaves the context as it was
+        const double kind = nparams > OFDFT_P_NLK_KIND ? params[OFDFT_P_NLK_KIND] : c->params[OFDFT_P_NLK_KIND];
+        const double p0 = nparams > OFDFT_P_NLK_P0 ? params[OFDFT_P_NLK_P0] : c->params[OFDFT_P_NLK_P0];
+        if (c->nranks > 1)
+            return fail(c, OFDFT_EINVAL, "OFDFT_NLK (KGAP / MGP / XWM) is served by single-GPU contexts: the slab-decomposed path has no tabulated-kernel term yet");
+        if (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL))
+            return fail(c, OFDFT_EINVAL, "OFDFT_NLK cannot be combined with OFDFT_WT_NL / OFDFT_WGC99_NL: they share the nonlocal chain's buffers");
+        if (kind != 1.0 && kind != 2.0 && kind != 3.0)
+            return fail(c, OFDFT_EINVAL, "OFDFT_NLK needs OFDFT_P_NLK_KIND = 1 (KGAP), 2 (MGP) or 3 (XWM), got %g", kind);
+        if (kind == 1.0 && !(p0 >= 0.0)) return fail(c, OFDFT_EINVAL, "KGAP: E_gap must be >= 0 eV, got %g", p0);
+        if (kind == 3.0 && !(p0 > -5.0 / 6.0)) return fail(c, OFDFT_EINVAL, "XWM: kappa must exceed -5/6, got %g", p0);
+    }
     for (int i = 0; i < nparams; ++i) {
         if (i >= OFDFT_P_WGC_ALPHA && i <= OFDFT_P_WGC_KAPPA && c->params[i] != params[i]) c->wgc_valid = false;
+        if (i >= OFDFT_P_NLK_KIND && i <= OFDFT_P_NLK_P2 && c->params[i] != params[i]) c->nlk_valid = false;
         c->params[i] = params[i];
     }
     c->mask = mask;
@@ -1017,7 +1159,7 @@ int ofdft_energy_potential(ofdft_ctx* c, const void* den, const void* vext, doub
     double vn;
     if (zfused_serves(c)) {
         double nel = 0.0;
-        if (c->mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF)) {
+        if (c->mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_VWGTF | OFDFT_NLK)) {
             double nsum;
             if (int rc = device_sum(c, (const real*)den, false, &nsum, st)) return rc;
             nel = nsum / (double)c->npts * c->vol;

@@ -77,6 +77,11 @@ struct ofdft_ctx {
     int yfwd_fused = 0;            // ... of the last energy call (OFDFT_Q_YFWD_FUSED: the byte model of bench.py)
     bool wgc_valid = false;
     double wgc_ck = 0.0;           // K3 = K2 + wgc_ck K1 for the tables in "t:wgc" ((3 - gamma) / (3 n_ref))
+    // OFDFT_NLK kernel table ("t:nlk"): valid for this key (the cell and the parameters invalidate it: set_cell / set_terms)
+    bool nlk_valid = false;
+    long long nlk_key_nel = -1;    // round(N_e)
+    double nlk_key_nel_exact = 0.0;  // XWM: eta comes from the un-rounded count (functionals.py:631-639)
+    double* d_nlk_w = nullptr;     // MGP: the 1-D table (kMgpNodes doubles) + one word for max |k|^2
     bool wgc_fold = true;          // orthogonal cells: the cross-wave x pass reads the table entry of x > n0 / 2 at n0 - x (OFDFT_OPT_WGC_FOLD)
     // stats
     int fft_count = 0, launch_count = 0;
@@ -173,7 +178,51 @@ inline bool gga_needs_laplacian(const ofdft_ctx* c) {
 // Pauli-positivity stabilised Wang-Teter style functional (functionals.py:728-782) with f = exp: two combine passes (energies
 // first, then the potential with the weights f - f' X, f' they determine)
 inline bool wts_active(const ofdft_ctx* c) {
-    return (int)c->params[OFDFT_P_WTS_KIND] == 1 && (c->mask & OFDFT_TF) && (c->mask & OFDFT_WT_NL);
+    return (int)c->params[OFDFT_P_WTS_KIND] == 1 && (c->mask & OFDFT_TF) && (c->mask & (OFDFT_WT_NL | OFDFT_NLK));
+}
+// The two-power nonlocal term of an evaluation: the Wang-Teter family (kernel on the fly) or OFDFT_NLK (kernel from "t:nlk").  Both
+// ride the same z stages, buffers and combine section: n^e_b goes through s_b into conv_b, n^e_a (when the exponents differ)
+// through s_a into conv_a, the combine forms E = n^alpha conv_b and v = alpha n^(alpha-1) conv_b + beta n^(beta-1) conv_a.
+//   WT, KGAP: e_b = beta, e_a = alpha, both spectra times the one kernel;  MGP, KGAP(0): one power;
+//   XWM: e_b = alpha = kappa + 5/6, e_a = beta = kappa + 11/6, (s_b, s_a) <- (2 K_00 s_b + K_01 s_a, K_01 s_b), E = half the symmetric sum
+struct NlPow {
+    bool on = false, nlk = false, two = false;
+    int kind = 0, sym = 0;
+    double al = 0.0, be = 0.0;      // the combine's alpha, beta
+    double e_b = 0.0, e_a = 0.0;    // powers transformed into s_b / s_a
+};
+inline NlPow nl_pow(const ofdft_ctx* c) {
+    NlPow p;
+    if (c->mask & OFDFT_WT_NL) {
+        p.on = true;
+        p.al = c->params[OFDFT_P_WT_ALPHA];
+        p.be = c->params[OFDFT_P_WT_BETA];
+        p.e_b = p.be;
+        p.e_a = p.al;
+    } else if (c->mask & OFDFT_NLK) {
+        p.on = p.nlk = true;
+        p.kind = (int)c->params[OFDFT_P_NLK_KIND];
+        const double x = c->params[OFDFT_P_NLK_P0];
+        if (p.kind == NLK_KGAP) {               // functionals.py:1151-1154
+            const double fr = x * x / (5.0 + x * x), s5 = std::sqrt(5.0);
+            p.al = 0.5 + ((5.0 + s5) / 6.0 - 0.5) * fr;
+            p.be = 0.5 + ((5.0 - s5) / 6.0 - 0.5) * fr;
+            p.e_b = p.be;
+            p.e_a = p.al;
+        } else if (p.kind == NLK_MGP) {
+            p.al = p.be = p.e_b = p.e_a = kFiveSixths;
+        } else {                                 // XWM functionals.py:1480,1492
+            p.al = p.e_b = x + kFiveSixths;
+            p.be = p.e_a = x + (double)11 / 6;
+            p.sym = 1;
+        }
+    }
+    p.two = p.on && p.al != p.be;
+    return p;
+}
+// the term mask as the combine kernels read it: OFDFT_NLK rides the Wang-Teter family's section (bit 4)
+inline unsigned combine_mask(const ofdft_ctx* c) {
+    return (c->mask & OFDFT_NLK) ? ((c->mask & ~OFDFT_NLK) | OFDFT_WT_NL) : c->mask;
 }
 inline bool zfused_serves(const ofdft_ctx* c) {
     return c->fast && c->pipeline == 0 && c->n2 / 2 <= 512 && (!gga_needs_laplacian(c) || c->gga_split);
@@ -374,6 +423,9 @@ inline MixWgc wgc_tab(ofdft_ctx* c, long long off = 0) {
     const cplx* t01 = (const cplx*)c->ws["t:wgc"].p;
     return MixWgc{t01 + off, reinterpret_cast<const real*>(t01 + c->g.total) + off, (real)c->wgc_ck};
 }
+// OFDFT_NLK: build "t:nlk" for (cell, round(N_e) [, N_e], kind, parameters) if the key changed; the mix functors over its columns
+int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st);
+inline const real* nlk_col(ofdft_ctx* c, int col) { return (const real*)c->ws["t:nlk"].p + (size_t)col * c->g.total; }
 bool resident_serves(const ofdft_ctx* c);
 constexpr int kResidentDeclined = 1;       // resident_closure: not an error -- the caller takes the graph / staged path instead
 // chi -> (sums, v, chi.grad) -- or, with from_den, density -> (sums, v) -- by the persistent small-grid kernel (resident.hip)

@@ -217,6 +217,8 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         return fail(c, OFDFT_ESTATE, "slab-decomposed context: ofdft_stress needs ofdft_set_collectives");
     if (wts_active(c) && c->nranks > 1)
         return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND) is served by single-GPU contexts");
+    if ((c->mask & OFDFT_NLK) && c->params[OFDFT_P_NLK_KIND] == 2.0)
+        return fail(c, OFDFT_EINVAL, "MiGenovaPavanello has no stress: the reference's own get_stress raises on it (torch.unique has no derivative)");
     const double* den = (const double*)den_dev;
     const unsigned mask = c->mask;
     const long long npts = c->npts;
@@ -334,14 +336,49 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         for (int k = 0; k < 6; ++k) c6[k] = pref * s7[k];
         sym_store(sig + 9 * 4, c6, -2.0 / 3.0 * pref * s7[6]);                                  // -2/3 T_NL / vol
     }
+    if (mask & OFDFT_NLK) {          // KGAP / XWM (stress_kernels.h: stress_nlk_kernel); n0 = round(N_e) / vol
+        const NlPow nlp = nl_pow(c);
+        const double nel = nsum * c->dV, n0 = (double)std::llround(nel) / c->vol, x0 = c->params[OFDFT_P_NLK_P0];
+        const double kf = std::cbrt(3.0 * kPi * kPi * n0), ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
+        NlkStress t{};
+        t.kind = nlp.kind;
+        t.inv2kf = 1.0 / (2.0 * kf);
+        if (nlp.kind == NLK_KGAP) {
+            t.c0 = ctf * 5.0 / (9.0 * nlp.al * nlp.be * std::pow(n0, nlp.al + nlp.be - 5.0 / 3.0));
+            t.delta = 2.0 * (x0 / (4.3597447222071e-18 / 1.602176634e-19)) / (kf * kf);       // functionals.py:13-14,1117
+        } else {
+            const double cx = kPi * kPi / std::cbrt(3.0 * kPi * kPi), n2k = std::pow(n0, 2.0 * x0), k1 = cx / (6.0 * n0) / n2k;
+            t.inv2kf = 1.0 / (2.0 * std::cbrt(3.0 * kPi * kPi * nbar));                         // un-rounded (functionals.py:631-639)
+            t.c0 = 18.0 / ((6.0 * x0 + 5.0) * (6.0 * x0 + 5.0)) * cx / n2k;
+            t.c1 = -n0 / (nlp.al * nlp.al) * k1;
+            t.c2 = k1 / (nlp.al * nlp.be);
+        }
+        double* tmp;
+        if (int rc = real_ws(c, "t0", &tmp)) return rc;
+        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.al);
+        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        cplx* sb = s0;
+        if (nlp.two) {
+            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.be);
+            if (int rc = rfftn_internal(c, tmp, s1, st)) return rc;
+            sb = s1;
+        }
+        OFDFT_LAUNCH(c, st, "stress_spec", stress_nlk_kernel, dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0, (const cplx*)sb,
+                     c->kg, invN2, t, c->d_partial);
+        if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
+        sym_store(sig + 9 * 14, s7, -2.0 / 3.0 * s7[6]);                                         // -2/3 T_NL / vol
+    }
     if (wts_active(c)) {      // T = T_TF f(X): sigma = sigma_TF (f - f' X) + sigma_NL f'(X) / f'(0)   (tools_for_tests.py:310-364), f = exp
         // both stresses carry -2/3 E / vol on their diagonals: T_TF / vol = -3/2 sig_TF[0] exactly; T_NL / vol from the trace
         // of the Wang-Teter tensor (its k-dependent part is traceless)
-        const double tf_over_vol = -1.5 * sig[9 * 2], nl_over_vol = -0.5 * (sig[9 * 4] + sig[9 * 4 + 4] + sig[9 * 4 + 8]);
+        // (KGAP's tensor has a delta-derivative on its diagonal too, so its T_NL / vol is the kernel's own energy sum)
+        const int nl = (mask & OFDFT_NLK) ? 14 : 4;
+        const double tf_over_vol = -1.5 * sig[9 * 2];
+        const double nl_over_vol = (mask & OFDFT_NLK) ? s7[6] : -0.5 * (sig[9 * 4] + sig[9 * 4 + 4] + sig[9 * 4 + 8]);
         const double X = nl_over_vol / tf_over_vol, fx = std::exp(X);
         for (int k = 0; k < 9; ++k) {
             sig[9 * 2 + k] *= fx * (1.0 - X);
-            sig[9 * 4 + k] *= fx;
+            sig[9 * nl + k] *= fx;
         }
     }
     if (mask & OFDFT_WGC99_NL) {

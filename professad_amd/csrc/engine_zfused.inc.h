@@ -19,6 +19,7 @@ void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pb
     if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
     if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
     if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
+    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
     *vn_int = sums[8] * dV;
 }
 
@@ -112,13 +113,13 @@ int zsetup(ofdft_ctx* c) {
     r.has_h = mask & OFDFT_HARTREE;
     r.has_g = mask & kGgaAny;
     r.has_vw = mask & OFDFT_VW;
-    r.has_wt = mask & OFDFT_WT_NL;
+    r.has_wt = mask & (OFDFT_WT_NL | OFDFT_NLK);       // (OFDFT_NLK rides the Wang-Teter stages: nl_pow, engine_ctx.h)
     r.has_wgc = mask & OFDFT_WGC99_NL;
     r.za = ZCombineArgs{};
     r.za.ds = r.ds;
     r.za.vext = r.vext;
     r.za.v_out = r.v_out;
-    r.za.mask = mask;
+    r.za.mask = combine_mask(c);
     r.za.inv_n = 1.0 / (double)c->npts_g;
     r.za.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
     r.za.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(r.nel) : 0.0;   // functionals.py:268-270
@@ -187,17 +188,19 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         }
     } else {
         if (r.has_wt) {
-            const double al = c->params[OFDFT_P_WT_ALPHA], be = c->params[OFDFT_P_WT_BETA];
+            const NlPow nlp = nl_pow(c);
+            const double al = nlp.al, be = nlp.be;
             const double nbar = r.nel / c->vol;                                  // functionals.py:646-647
             r.wt_kf = std::cbrt(3.0 * kPi * kPi * nbar);
             r.wt_pref = 5.0 / (9.0 * al * be * std::pow(nbar, al + be - kFiveThirds));
+            if (nlp.nlk && (rc = ensure_nlk_table(c, r.nel, sb))) return rc;
             if ((rc = spec_ws(c, "zwb", &r.s_b))) return rc;
             if (al != be && (rc = spec_ws(c, "zwa", &r.s_a))) return rc;
             PowersArgs pa{};
             pa.out[0] = r.s_b;
             pa.out[3] = r.s_a;
-            pa.e0 = be;
-            pa.e1 = al;
+            pa.e0 = nlp.e_b;
+            pa.e1 = nlp.e_a;
             if ((rc = launch_zf_powers(c, r.ds, pa, sb))) return rc;
             for (cplx* sp : {r.s_b, r.s_a}) {
                 if (!sp) continue;
@@ -206,8 +209,9 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             }
             r.za.wt_alpha = al;
             r.za.wt_beta = be;
-            r.za.wt_nbar_pa = std::pow(nbar, al);
+            r.za.wt_nbar_pa = nlp.nlk ? 0.0 : std::pow(nbar, al);     // (tabulated kernels: 0 at k = 0, nothing subtracted)
             r.za.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
+            r.za.wt_sym = nlp.sym;
         }
         if (r.has_wgc) {
             const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
@@ -338,7 +342,26 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             if ((rc = xfused<1, 1>(c, io, MixScale<SPEC_LAPLACE>{c->kg, 0.0, 0.0}, sc, "xfused_lap", lay))) return rc;
         }
     } else {
-        if (r.has_wt) {
+        if (r.has_wt && (c->mask & OFDFT_NLK)) {
+            // the same stage with the kernel from "t:nlk": XWM mixes its two spectra in one 2 -> 2 pass, the others scale each
+            // spectrum by the one column
+            if (nl_pow(c).sym) {
+                XfIo io{};
+                io.in[0] = in_of(r.s_b);
+                io.in[1] = in_of(r.s_a);
+                io.out[0] = out_of(r.s_b);
+                io.out[1] = out_of(r.s_a);
+                if ((rc = xfused<2, 2>(c, io, MixNlk<2>{nlk_col(c, 0), nlk_col(c, 1)}, sb, "xfused_nlk", lay))) return rc;
+            } else {
+                for (cplx* sp : {r.s_b, r.s_a}) {
+                    if (!sp) continue;
+                    XfIo io{};
+                    io.in[0] = in_of(sp);
+                    io.out[0] = out_of(sp);
+                    if ((rc = xfused<1, 1>(c, io, MixNlk<1>{nlk_col(c, 0), nullptr}, sb, "xfused_nlk", lay))) return rc;
+                }
+            }
+        } else if (r.has_wt) {
             const MixScale<SPEC_LINDHARD> lind{c->kg, (real)r.wt_pref, (real)(1.0 / (2.0 * r.wt_kf))};
             for (cplx* sp : {r.s_b, r.s_a}) {
                 if (!sp) continue;
@@ -710,7 +733,7 @@ int zfused_enqueue(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext,
     int rc;
     // Forking the nonlocal-KEDF chain (and the vW / second WGC99 half) onto their own streams lets their
     // latency-bound fused kernels overlap the other chain's bandwidth-bound passes.
-    r.forked = c->use_side_stream && c->side_stream && c->side_stream2 && (c->mask & (OFDFT_WT_NL | OFDFT_WGC99_NL)) &&
+    r.forked = c->use_side_stream && c->side_stream && c->side_stream2 && (c->mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_NLK)) &&
                (c->mask & (OFDFT_HARTREE | OFDFT_VW | kGgaAny));
     if (r.forked) {
         r.sb = c->side_stream;

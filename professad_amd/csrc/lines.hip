@@ -337,6 +337,8 @@ template int bluestein_xmix<1, 1, MixScale<SPEC_LINDHARD>>(ofdft_ctx*, const cpl
 template int bluestein_xmix<1, 3, MixDensity<false, true>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDensity<false, true>&, hipStream_t);
 template int bluestein_xmix<1, 4, MixDensity<true, true>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDensity<true, true>&, hipStream_t);
 template int bluestein_xmix<3, 1, MixDiv>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDiv&, hipStream_t);
+template int bluestein_xmix<1, 1, MixNlk<1>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixNlk<1>&, hipStream_t);
+template int bluestein_xmix<2, 2, MixNlk<2>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixNlk<2>&, hipStream_t);
 template int bluestein_xmix<3, 3, MixWgc>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixWgc&, hipStream_t);
 
 // small grids: z rows and y lines of an x plane in one kernel (bluestein.h: bluestein_zy_kernel) -- both padded lengths equal and

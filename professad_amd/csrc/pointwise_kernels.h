@@ -437,6 +437,140 @@ static __global__ void wgc_table_kernel(cplx* __restrict__ t01, real* __restrict
     }
 }
 
+// ---- tabulated, density-independent nonlocal kernels (OFDFT_NLK: KGAP, Mi-Genova-Pavanello, Xu-Wang-Ma) -----------------------
+// The kernels depend on the cell, round(N_e) and the functional's parameters only, so they are built once per such key into
+// per-k-point columns in spectrum order ("t:nlk", laid out like "t:wgc") and the x passes read them (MixNlk).  Built in fp64 with the
+// library log / atan / erf in both builds (not on the per-evaluation path); stored in the grid precision.  Every column is
+// divided by C_TF: the combine kernels multiply the Wang-Teter family's convolutions by it.
+enum { NLK_KGAP = 1, NLK_MGP = 2, NLK_XWM = 3 };
+constexpr int kMgpNodes = 2000, kMgpQuad = 10000;      // generate_kernel's N_eta, N_int (functionals.py:1390)
+struct NlkTab {
+    int kind;
+    double inv2kf;        // eta = |k| inv2kf (k_F of round(N_e) / vol; XWM: of the un-rounded count, functionals.py:631-639)
+    double pref;          // KGAP: 5 / (9 alpha beta n0^(alpha + beta - 5/3)) ; XWM: 2 * 18 / (6 kappa + 5)^2 c / n0^(2 kappa) / C_TF
+    double p1, p2;        // KGAP: delta; XWM: p1 = c / (6 n0^(1 + 2 kappa)) / C_TF, p2 = n0 / p^2 (K_00 = kernel0 - p2 kernel1), and
+    double p3;            //       p3 = 1 / (p r) (K_01 = p3 kernel1);  MGP: p1 = 4 pi a (3/5) / C_TF, p2 = b, p3 = eta_max of the table
+    const double* w;      // MGP: the 1-D table w(eta_i) / C_TF, kMgpNodes nodes on [0, p3]
+};
+// the reference's G^-1 of the Lindhard function with its patches at eta = 0 and 1 (functionals.py:617-628), library log
+__device__ __forceinline__ double nlk_ginv_lind(double eta) {
+    if (eta == 0.0) return 1.0;
+    if (eta == 1.0) return 0.5;
+    return 0.5 + ((1.0 - eta * eta) / (4.0 * eta)) * log(fabs((1.0 + eta) / (1.0 - eta)));
+}
+// G^-1 of the gapped jellium (functionals.py:1119-1125), eta != 0.  delta = 0 is the Lindhard function: delta atan(x / delta) -> 0
+// and the delta^2 terms vanish, so that branch never divides by delta.
+__device__ __forceinline__ double nlk_ginv_gap(double eta, double delta) {
+    if (delta == 0.0) return nlk_ginv_lind(eta);
+    const double ap = 4.0 * (eta + eta * eta), am = 4.0 * (eta - eta * eta), d2 = delta * delta;
+    return 0.5 - delta * (atan(ap / delta) + atan(am / delta)) / (8.0 * eta) +
+           (d2 / 128.0 / (eta * eta * eta) + 1.0 / 8.0 / eta - eta / 8.0) * log((d2 + ap * ap) / (d2 + am * am));
+}
+// torch.linspace(lo, hi, n)[i] in fp64: from the low end in the first half, from the high end in the second
+__device__ __forceinline__ double nlk_linspace(double lo, double hi, int n, int i) {
+    const double step = (hi - lo) / (double)(n - 1);
+    return i < n / 2 ? lo + step * i : hi - step * (n - 1 - i);
+}
+// largest |k|^2 of the grid (MGP: the 1-D table reaches 1.2 eta_max, functionals.py:1428,1437); bits of a non-negative double
+// order like the unsigned integer
+static __global__ void nlk_k2max_kernel(KGeom kg, unsigned long long* __restrict__ out) {
+    double m = 0.0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
+        real kx, ky, kz, k2;
+        kvec(kg, i, kx, ky, kz, k2);
+        m = fmax(m, (double)k2);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(m));
+}
+// MGP 1-D table (functionals.py:1401-1409): w(eta_i) = 0.2 (3 pi^2)^(2/3) dt sum_t G_NL(eta_i / t^(1/3)) / t^(1/6), one workgroup
+// per node, the kMgpQuad points t over its threads, partial sums added in a fixed order.  The formula is the reference's own
+// (it cancels about eleven digits at eta / t^(1/3) ~ 300; another log / pow reproduces its table to ~1e-8 of the largest entry).
+static __global__ __launch_bounds__(256) void nlk_mgp_table_kernel(double eta_hi, double inv_ctf, double* __restrict__ w) {
+    __shared__ double red[256];
+    const int node = blockIdx.x;
+    const double eta = nlk_linspace(0.0, eta_hi, kMgpNodes, node);
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < kMgpQuad; j += 256) {
+        const double t = nlk_linspace((double)1e-4L, 1.0, kMgpQuad, j);
+        const double e = eta / pow(t, (double)1 / 3);
+        acc += (1.0 / nlk_ginv_lind(e) - 3.0 * e * e - 1.0) / pow(t, (double)1 / 6);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double dt = nlk_linspace((double)1e-4L, 1.0, kMgpQuad, 1) - nlk_linspace((double)1e-4L, 1.0, kMgpQuad, 0);
+        w[node] = (double)0.2L * pow(3.0 * kPi * kPi, (double)2 / 3) * red[0] * dt * inv_ctf;
+    }
+}
+// the reference's cubic Hermite rule on the uniform table (functional_tools.py:292-334): finite-difference slopes, averaged at the
+// interior nodes; the interval index is arithmetic (x_idx < eta <= x_idx+1, as searchsorted on x[1:] gives it)
+__device__ __forceinline__ double nlk_mgp_interp(const double* __restrict__ w, double eta_hi, double eta) {
+    const double h = eta_hi / (double)(kMgpNodes - 1);
+    int idx = (int)ceil(eta / h) - 1;
+    idx = idx < 0 ? 0 : (idx > kMgpNodes - 2 ? kMgpNodes - 2 : idx);
+    if (idx > 0 && eta <= nlk_linspace(0.0, eta_hi, kMgpNodes, idx)) --idx;               // rounding of eta / h at a node
+    if (idx < kMgpNodes - 2 && eta > nlk_linspace(0.0, eta_hi, kMgpNodes, idx + 1)) ++idx;
+    const double x0 = nlk_linspace(0.0, eta_hi, kMgpNodes, idx), x1 = nlk_linspace(0.0, eta_hi, kMgpNodes, idx + 1), dx = x1 - x0;
+    auto seg = [&](int j) { return (w[j + 1] - w[j]) / (nlk_linspace(0.0, eta_hi, kMgpNodes, j + 1) - nlk_linspace(0.0, eta_hi, kMgpNodes, j)); };
+    const double s = seg(idx);
+    const double m0 = idx == 0 ? s : 0.5 * (s + seg(idx - 1));
+    const double m1 = idx == kMgpNodes - 2 ? s : 0.5 * (seg(idx + 1) + s);
+    const double t = (eta - x0) / dx, t2 = t * t, t3 = t2 * t;
+    return (1.0 - 3.0 * t2 + 2.0 * t3) * w[idx] + (t - 2.0 * t2 + t3) * m0 * dx + (3.0 * t2 - 2.0 * t3) * w[idx + 1] + (t3 - t2) * m1 * dx;
+}
+// the per-k-point columns: c0 (every kind), c1 (XWM).  All kernels are 0 at k = 0.
+//   KGAP  c0 = pref (1 / G_gap - 3 eta^2 - 1)                                  K_01 / C_TF (K_00 / C_TF when alpha = beta)
+//   MGP   c0 = interp(eta) + (3/5) erf(|k|)^2 (4 pi a / k^2) exp(-b k^2)       K_00 / C_TF
+//   XWM   c0 = 2 (kernel0 - kernel1b), c1 = kernel1a                           2 K_00 / C_TF, K_01 / C_TF (functionals.py:1478-1496)
+static __global__ void nlk_table_kernel(real* __restrict__ c0, real* __restrict__ c1, KGeom kg, NlkTab t) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
+        real kx, ky, kz, k2r;
+        kvec(kg, i, kx, ky, kz, k2r);
+        const double k2 = (double)k2r;
+        double a0 = 0.0, a1 = 0.0;
+        if (k2 != 0.0) {
+            const double k = sqrt(k2), eta = k * t.inv2kf;
+            if (t.kind == NLK_KGAP) {
+                a0 = t.pref * (1.0 / nlk_ginv_gap(eta, t.p1) - 3.0 * eta * eta - 1.0);
+            } else if (t.kind == NLK_MGP) {
+                const double er = erf(k);
+                a0 = nlk_mgp_interp(t.w, t.p3, fmin(eta, t.p3)) + t.p1 * er * er / k2 * exp(-t.p2 * k2);
+            } else {
+                const double g = nlk_ginv_lind(eta);
+                const double f = 1.0 / g - 3.0 * eta * eta - 1.0;
+                const double gder = 0.5 - 0.25 * (eta + 1.0 / eta) * log(fabs((1.0 + eta) / (1.0 - eta)));
+                const double k1 = t.p1 * (gder / (g * g) + 6.0 * eta * eta);
+                a0 = t.pref * f - 2.0 * t.p2 * k1;
+                a1 = t.p3 * k1;
+            }
+        }
+        c0[i] = (real)a0;
+        if (c1) c1[i] = (real)a1;
+    }
+}
+// the table mix of the unfused pipeline, in place: A <- c0 A [+ c1 B], B <- c1 A
+static __global__ void spec_nlk_mix_kernel(cplx* __restrict__ A, cplx* __restrict__ B, const real* __restrict__ c0,
+                                           const real* __restrict__ c1, long long total) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const cplx a = A[i];
+        const real t0 = c0[i];
+        if (B) {
+            const cplx b = B[i];
+            const real t1 = c1[i];
+            A[i] = mkc(t0 * a.x + t1 * b.x, t0 * a.y + t1 * b.y);
+            B[i] = mkc(t1 * a.x, t1 * a.y);
+        } else {
+            A[i] = mkc(t0 * a.x, t0 * a.y);
+        }
+    }
+}
+
 // ---- mixing functors of the fused x pass (see xfused_kernel in fft_kernels.h) ----------------------
 __device__ __forceinline__ void kvec_xyz(const KGeom& kg, int x, int y, int z, real& kx, real& ky, real& kz,
                                          real& k2) {
@@ -638,6 +772,34 @@ struct MixWgc {
 // Its own type: the kernels that do not fold -- and cells with skewed axes -- keep the plain form and its wave-uniform addressing.
 struct MixWgcFold : MixWgc {
     int fold_n0;         // n0
+};
+
+// OFDFT_NLK: NS = 1: A^ -> c0 A^;  NS = 2: (A^, B^) -> (c0 A^ + c1 B^, c1 A^), c0 = 2 K_00, c1 = K_01 (no kind has a K_11); columns of
+// "t:nlk" in the spectrum layout (nlk_table_kernel)
+template <int NS> struct MixNlk {
+    static constexpr bool kTables = true;
+    const real* c0;
+    const real* c1;
+    static __device__ __forceinline__ constexpr bool imag(int) { return false; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool present() { return O + I <= 1; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool imag_oi() { return false; }
+    template <int O, int I>
+    __device__ __forceinline__ real coef(int, int, int, long long uoff, unsigned loff) const {
+        return buf_load_d((O + I == 0 ? c0 : c1) + uoff, loff * (unsigned)sizeof(real));
+    }
+    static constexpr int kTableReals = NS;
+    __device__ __forceinline__ void fetch(real (&cf)[NS], long long uoff, unsigned loff, bool valid) const {
+        cf[0] = valid ? buf_load_d(c0 + uoff, loff * (unsigned)sizeof(real)) : (real)0.0;
+        if constexpr (NS == 2) cf[1] = valid ? buf_load_d(c1 + uoff, loff * (unsigned)sizeof(real)) : (real)0.0;
+    }
+    __device__ __forceinline__ void apply(cplx (&o)[NS], const cplx (&in)[NS], const real (&cf)[NS]) const {
+        if constexpr (NS == 1) {
+            o[0] = mkc(cf[0] * in[0].x, cf[0] * in[0].y);
+        } else {
+            o[0] = mkc(cf[0] * in[0].x + cf[1] * in[1].x, cf[0] * in[0].y + cf[1] * in[1].y);
+            o[1] = mkc(cf[1] * in[0].x, cf[1] * in[0].y);
+        }
+    }
 };
 
 // ---- XC pointwise math -------------------------------------------------------------------------
@@ -896,6 +1058,7 @@ struct CombineArgs {
     int wt_is_56;        // alpha = beta = 5/6: n^(-1/6) = 1/sqrt(cbrt n), no pow
     int wgc_sum_53;      // alpha + beta = 5/3: n^(alpha-1) = 1/(cbrt(n) n^(beta-1)), one pow instead of two
     real w_tf = 1.0, w_nl = 1.0;   // weights of the TF / Wang-Teter potentials (stabilised WT-style functional, OFDFT_P_WTS_KIND)
+    int wt_sym = 0;      // OFDFT_NLK with a 2 x 2 kernel (XWM): conv_b / conv_a are the symmetric mix' outputs, E = (n^alpha conv_b + n^beta conv_a) / 2
 };
 // partial scalars: 0 ion-electron, 1 hartree, 2 tf, 3 vw, 4 wt-nl, 5 wgc-nl, 6 lda-x, 7 local-c, 8 sum(v*n), 9 vWGTF
 constexpr int kCombineScalars = 10;
@@ -952,11 +1115,13 @@ __device__ __forceinline__ real combine_point(const CombineArgs& a, const Combin
     }
     if (a.mask & 16u) {                                 // WT-family NL  functionals.py:650-651; tools_for_tests.py:29-39
         const real pa1 = a.wt_is_56 ? 1.0 / sqrt(n13) : pow(n, a.wt_alpha - 1.0);
-        acc[4] += ctf * (pa1 * n - a.wt_nbar_pa) * p.cb;
+        const real ewt = ctf * (pa1 * n - a.wt_nbar_pa) * p.cb;
         if (a.conv_a) {
             const real pb1 = pow(n, a.wt_beta - 1.0);
+            acc[4] += a.wt_sym ? (real)0.5 * (ewt + ctf * pb1 * n * p.cva) : ewt;
             v += a.w_nl * ctf * (a.wt_alpha * pa1 * p.cb + a.wt_beta * pb1 * p.cva);
         } else {
+            acc[4] += ewt;
             v += a.w_nl * ctf * 2.0 * a.wt_alpha * pa1 * p.cb;
         }
     }

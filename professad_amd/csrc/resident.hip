@@ -661,6 +661,7 @@ bool resident_serves(const ofdft_ctx* c) {
     if ((c->mask & kGgaAny) && (gga_needs_laplacian(c) || (c->n0 > 32 && sizeof(real) == 8))) return false;      // (64^3 fp64 with a GGA term: five phases of
                                                                                           //  4096-point planes per workgroup measured slower than the graph replay, 0.160 vs 0.153 ms; fp32: 0.118 vs 0.150)
     if (wts_active(c)) return false;
+    if (c->mask & OFDFT_NLK) return false;        // (the tabulated kernels live in device memory: the staged path serves them)
     return c->mask != 0;
 }
 

@@ -72,6 +72,81 @@ __global__ __launch_bounds__(kRedThreads) void stress_spec_kernel(const cplx* __
     block_reduce_store<kStressSpecScalars>(acc, partial);
 }
 
+// Tabulated-kernel nonlocal term (OFDFT_NLK), kinds KGAP and XWM.  Derived as oracle/stress.py documents the Wang-Teter and WGC99
+// forms.  With unnormalised spectra a~, b~ of the powers n^(e_a), n^(e_b), one pair term is
+//     T = vol / N^2  sum_k w K(k; vol) Re(a~ b~*),
+// and under a homogeneous strain eps at fixed N_e the grid values scale as n -> n / J, the wave vectors as
+// d ln|k| / d eps_ij = -k_i k_j / k^2, and vol -> J vol.  Hence
+//     (1 / vol) dT / d eps_ij = delta_ij (1 - e_a - e_b) T / vol
+//                               + 1 / N^2 sum_k w Re(a~ b~*) [ dK/dln|k| (-k_i k_j / k^2) + dK/dln vol |_k delta_ij ].
+// Every kernel here is K = c vol^q F(eta [, delta]) with eta = |k| / (2 k_F), k_F ~ vol^(-1/3) (n0 = round(N_e) / vol, and the
+// un-rounded N_e / vol of XWM's eta, scale alike at fixed N_e) and, for KGAP, delta = 2 E_gap / k_F^2 ~ vol^(2/3):
+//     dK/dln|k| = eta K_eta,     dK/dln vol |_k = q K + eta K_eta / 3 + (2/3) delta K_delta,
+// and q = e_a + e_b - 5/3 for each pair (KGAP: c ~ n0^-(alpha+beta-5/3); XWM: kernel0, kernel1b ~ n0^(-2 kappa) with powers
+// 2 kappa + 5/3, kernel1a ~ n0^(-1 - 2 kappa) with powers 2 kappa + 8/3), so the diagonal collects to -2/3 T / vol:
+//     sigma_ij = sum_pairs 1 / N^2 sum_k w Re(a~ b~*) [ eta K_eta (delta_ij / 3 - k_i k_j / k^2) + (2/3) delta K_delta delta_ij ]
+//                - (2/3) T / vol delta_ij.
+// Closed forms: F = 1/G - 3 eta^2 - 1, F_eta = -G_eta / G^2 - 6 eta, F_delta = -G_delta / G^2, with G the gapped response
+// (nlk_ginv_gap; its eta and delta derivatives below) or the Lindhard one, for which eta G_eta = D = 1/2 - (eta + 1/eta) lg / 4;
+// XWM's kernel1 shape is H = D / G^2 + 6 eta^2 (= -eta F_eta), H_eta = D_eta / G^2 - 2 D^2 / (eta G^3) + 12 eta.
+//   KGAP: K = c0 F(eta, delta) on Re(a~ b~*), a = n^alpha, b = n^beta
+//   XWM:  K_AA = c0 F + c1 H on |A~|^2, K_AB = c2 H on Re(A~ B~*)  (c1 = -(n0 / p^2) k1, c2 = k1 / (p r): functionals.py:1478-1496)
+// acc_ij: the bracket; acc[6]: sum_k w K Re(.) = T / vol.
+struct NlkStress { int kind; double inv2kf, c0, c1, c2, delta; };
+__device__ __forceinline__ void nlk_gap_derivs(double e, double d, double& G, double& Ge, double& Gd) {
+    const double lg0 = log(fabs((1.0 + e) / (1.0 - e)));
+    if (d == 0.0) {
+        G = e == 1.0 ? 0.5 : 0.5 + (1.0 - e * e) / (4.0 * e) * lg0;
+        Ge = 0.5 / e - 0.25 * (1.0 + 1.0 / (e * e)) * lg0;
+        Gd = 0.0;
+        return;
+    }
+    const double p = 4.0 * (e + e * e), m = 4.0 * (e - e * e), pp = 4.0 * (1.0 + 2.0 * e), mp = 4.0 * (1.0 - 2.0 * e), d2 = d * d;
+    const double at = atan(p / d) + atan(m / d), dp = d2 + p * p, dm = d2 + m * m;
+    const double Q = d2 / (128.0 * e * e * e) + 1.0 / (8.0 * e) - e / 8.0, L = log(dp / dm);
+    const double Qe = -3.0 * d2 / (128.0 * e * e * e * e) - 1.0 / (8.0 * e * e) - 0.125, Le = 2.0 * p * pp / dp - 2.0 * m * mp / dm;
+    G = 0.5 - d * at / (8.0 * e) + Q * L;
+    Ge = -d * (d * pp / dp + d * mp / dm) / (8.0 * e) + d * at / (8.0 * e * e) + Qe * L + Q * Le;
+    Gd = -(at - d * p / dp - d * m / dm) / (8.0 * e) + (2.0 * d / (128.0 * e * e * e)) * L + Q * (2.0 * d / dp - 2.0 * d / dm);
+}
+__global__ __launch_bounds__(kRedThreads) void stress_nlk_kernel(const cplx* __restrict__ a, const cplx* __restrict__ b, KGeom kg,
+                                                                 double scale, NlkStress t, double* __restrict__ partial) {
+    double acc[kStressSpecScalars] = {0, 0, 0, 0, 0, 0, 0};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
+        int x, y, z;
+        spec_decode(kg.g, i, x, y, z);
+        double kx, ky, kz, k2;
+        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
+        if (k2 == 0.0) continue;
+        const double w = half_weight(kg.g, z) * scale;
+        const cplx av = a[i], bv = b[i];
+        const double eta = sqrt(k2) * t.inv2kf;
+        double G, Ge, Gd;
+        nlk_gap_derivs(eta, t.kind == NLK_KGAP ? t.delta : 0.0, G, Ge, Gd);
+        const double F = 1.0 / G - 3.0 * eta * eta - 1.0, Fe = -Ge / (G * G) - 6.0 * eta;
+        double g, diag = 0.0, en;          // g = sum X eta K_eta, diag = sum X (2/3) delta K_delta, en = sum X K
+        if (t.kind == NLK_KGAP) {
+            const double X = w * (av.x * bv.x + av.y * bv.y);
+            g = X * t.c0 * eta * Fe;
+            diag = X * t.c0 * (2.0 / 3.0) * t.delta * (-Gd / (G * G));
+            en = X * t.c0 * F;
+        } else {
+            const double Xaa = w * (av.x * av.x + av.y * av.y), Xab = w * (av.x * bv.x + av.y * bv.y);
+            const double lg = log(fabs((1.0 + eta) / (1.0 - eta)));
+            const double D = eta * Ge, De = -0.25 * (1.0 - 1.0 / (eta * eta)) * lg - 0.5 * (eta + 1.0 / eta) / (1.0 - eta * eta);
+            const double H = D / (G * G) + 6.0 * eta * eta, He = De / (G * G) - 2.0 * D * D / (eta * G * G * G) + 12.0 * eta;
+            g = eta * (Xaa * (t.c0 * Fe + t.c1 * He) + Xab * t.c2 * He);
+            en = Xaa * (t.c0 * F + t.c1 * H) + Xab * t.c2 * H;
+        }
+        add_kk(acc, -g / k2, kx, ky, kz);
+        acc[0] += g / 3.0 + diag;
+        acc[1] += g / 3.0 + diag;
+        acc[2] += g / 3.0 + diag;
+        acc[6] += en;
+    }
+    block_reduce_store<kStressSpecScalars>(acc, partial);
+}
+
 // WGC99 nonlocal part (oracle/stress.py::wgc99_nl): spectra of A, B, C, P, Q, S (unnormalised), scale = 1/N^2
 //   acc_ij += G (delta_ij / 3 - k_i k_j / k^2),  G = (w0' X0 + K1' X1 + K2' X2 + K3' X3) eta;   acc[6] += w0 X0 + K1 X1 + K2 X2 + K3 X3
 struct WgcSpectra { const cplx* s[6]; };

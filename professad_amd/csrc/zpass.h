@@ -770,6 +770,7 @@ struct ZCombineArgs {
     int gtf_kind;
     int wt_is_56, wgc_sum_53;
     const acc_t* wts_w;     // device weights (w_tf, w_nl) of the stabilised WT-style functional, or null
+    int wt_sym;             // OFDFT_NLK with a 2 x 2 kernel: E = (n^alpha conv_b + n^beta conv_a) / 2 (CombineArgs::wt_sym)
 };
 
 // WGC99 nonlocal part of one row (SURVEY §8a-8 closed form): adds the potential to vacc, returns the thread's energy sum
@@ -989,10 +990,22 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         park[kParkWt * 256] = e;
         if (a.conv_a) {
             take_row(std::integral_constant<int, 3>{}, a.conv_a);
+            if (a.wt_sym) {                              // (its own loop: the Wang-Teter family's stays as it was)
+                real e2 = 0.0;
 #pragma unroll
-            for (int q = 0; q < E; ++q) {
-                vacc[q].x += w_nl * ctf * a.wt_beta * pow_pos(n[q].x, a.wt_beta - 1.0) * w[q].x * sc;
-                vacc[q].y += w_nl * ctf * a.wt_beta * pow_pos(n[q].y, a.wt_beta - 1.0) * w[q].y * sc;
+                for (int q = 0; q < E; ++q) {
+                    const real p0 = ctf * pow_pos(n[q].x, a.wt_beta - 1.0) * w[q].x * sc, p1 = ctf * pow_pos(n[q].y, a.wt_beta - 1.0) * w[q].y * sc;
+                    e2 += p0 * n[q].x + p1 * n[q].y;
+                    vacc[q].x += w_nl * a.wt_beta * p0;
+                    vacc[q].y += w_nl * a.wt_beta * p1;
+                }
+                park[kParkWt * 256] = (real)0.5 * (park[kParkWt * 256] + e2);
+            } else {
+#pragma unroll
+                for (int q = 0; q < E; ++q) {
+                    vacc[q].x += w_nl * ctf * a.wt_beta * pow_pos(n[q].x, a.wt_beta - 1.0) * w[q].x * sc;
+                    vacc[q].y += w_nl * ctf * a.wt_beta * pow_pos(n[q].y, a.wt_beta - 1.0) * w[q].y * sc;
+                }
             }
         }
     }

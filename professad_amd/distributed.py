@@ -301,7 +301,7 @@ class HipStages(Engine):
         self._check(self.lib.ofdft_dist_closure(self._ctx, C.c_void_p(chi.data_ptr()), C.c_void_p(vext.data_ptr() if vext is not None else 0),
                                                 float(n_elec), E, C.byref(mu), C.c_void_p(out.data_ptr()), C.c_void_p(v.data_ptr()),
                                                 self._stream()), 'ofdft_dist_closure')
-        return {nm: E[i] for i, nm in enumerate(N.TERM_ORDER)}, mu.value, out
+        return N.per_term(E, 0), mu.value, out        # (slab contexts serve the first NTERMS_ALWAYS terms only)
 
     def sumsq(self, x, square=True, on_device=False):
         """local sum of x^2 (or x): returned as a float, or left in device_scalars[15] without a host sync"""
@@ -377,7 +377,7 @@ class HipStages(Engine):
         vn = C.c_double(0.0)
         g = (C.c_double * NSUMS)(*[float(x) for x in global_sums])
         self._check(self.lib.ofdft_dist_energies(self._ctx, g, E, C.byref(vn)), 'ofdft_dist_energies')
-        return {nm: E[i] for i, nm in enumerate(N.TERM_ORDER)}, vn.value
+        return N.per_term(E, 0), vn.value
 
     def chi_grad(self, chi, v, cscale, mu):
         out = torch.empty_like(chi)

@@ -110,7 +110,7 @@ class Engine:
     def set_terms(self, names, params=None):
         """names: iterable of keys of _native.TERM_BITS; params: dict slot->value
         (wt_alpha, wt_beta, wgc_alpha, wgc_beta, wgc_gamma, wgc_kappa, ggak_kind, ggak_mu, ggak_beta, ggak_lambda, ggak_sigma, vwgtf_kind,
-        wts_kind)."""
+        wts_kind, nlk_kind, nlk_p0, nlk_p1, nlk_p2)."""
         memo = None
         if isinstance(names, tuple) and (params is None or isinstance(params, tuple)):      # hashable call (the drop-in terms): memoised
             memo = (names, params)
@@ -127,9 +127,10 @@ class Engine:
         for nm in names:
             mask |= N.TERM_BITS[nm]
         slots = ['wt_alpha', 'wt_beta', 'wgc_alpha', 'wgc_beta', 'wgc_gamma', 'wgc_kappa', 'ggak_kind', 'ggak_mu', 'ggak_beta',
-                 'ggak_lambda', 'ggak_sigma', 'vwgtf_kind', 'wts_kind']
+                 'ggak_lambda', 'ggak_sigma', 'vwgtf_kind', 'wts_kind', 'nlk_kind', 'nlk_p0', 'nlk_p1', 'nlk_p2']
         s5 = np.sqrt(5.0)
-        vals = np.array([5 / 6, 5 / 6, (5 + s5) / 6, (5 - s5) / 6, 2.7, 1.0, 0.0, 40 / 27, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=np.float64)
+        vals = np.array([5 / 6, 5 / 6, (5 + s5) / 6, (5 - s5) / 6, 2.7, 1.0, 0.0, 40 / 27, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+                        dtype=np.float64)
         for k, v in (params or {}).items():
             vals[slots.index(k)] = float(v)
         key = (mask, vals.tobytes())
@@ -141,6 +142,10 @@ class Engine:
             self._terms_memo[memo] = key
         return self
 
+    def _mask(self):
+        """term mask of the last set_terms (0 before the first)"""
+        return self._terms_key[0] if self._terms_key is not None else 0
+
     # -- hot path
     def energy_potential(self, den, vext=None, want_potential=True):
         """-> (dict term -> E [Ha], dE/dn tensor or None)."""
@@ -150,7 +155,7 @@ class Engine:
         E = (C.c_double * N.NTERMS)()
         self._check(self.lib.ofdft_energy_potential(self._ctx, _ptr(den), _ptr(vext), E, _ptr(out), self._stream()),
                     'ofdft_energy_potential')
-        return {nm: E[i] for i, nm in enumerate(N.TERM_ORDER)}, out
+        return N.per_term(E, self._mask()), out
 
     def energy_grad_chi(self, chi, n_elec, vext=None, want_grad=True):
         """The optimize_density closure: -> (dict term -> E, mu, chi.grad tensor or None)."""
@@ -161,7 +166,7 @@ class Engine:
         mu = C.c_double(0.0)
         self._check(self.lib.ofdft_energy_grad_chi(self._ctx, _ptr(chi), _ptr(vext), float(n_elec), E, C.byref(mu),
                                                    _ptr(out), self._stream()), 'ofdft_energy_grad_chi')
-        return dict(zip(N.TERM_ORDER, E[:])), mu.value, out
+        return N.per_term(E, self._mask()), mu.value, out
 
     # -- validation entry points
     def rfftn(self, x):
@@ -216,7 +221,7 @@ class Engine:
         buf = (C.c_double * (N.NTERMS * 9))()
         self._check(self.lib.ofdft_stress(self._ctx, C.c_void_p(den.data_ptr()), buf, self._stream()), 'ofdft_stress')
         a = np.array(list(buf), dtype=np.float64).reshape(N.NTERMS, 3, 3)
-        return {nm: a[i] for i, nm in enumerate(N.TERM_ORDER)}
+        return N.per_term(a, self._mask())
 
     def set_profiling(self, on):
         self._check(self.lib.ofdft_set_profiling(self._ctx, 1 if on else 0), 'ofdft_set_profiling')

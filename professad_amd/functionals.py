@@ -314,6 +314,23 @@ class PauliGaussian:
     __call__ = forward
 
 
+def _stabiliser(f):
+    """(f'(0), OFDFT_P_WTS_KIND or None) of a Pauli-positivity stabilisation function f (f(0) = 1): kind 0.0 for f(x) = 1 + x,
+    1.0 for exp -- the two the engine evaluates itself -- else None (the caller composes the native energies in torch)."""
+    zero = torch.zeros((1,), dtype=torch.double, requires_grad=True)
+    if float(f(zero).detach()) != 1.0:
+        raise ValueError('Requires f(0) = 1')
+    fprime0 = float(torch.autograd.grad(f(zero), zero)[0])
+    probe = torch.tensor([-0.7, 0.25, 1.0], dtype=torch.double)
+    got = f(probe)
+    kind = None
+    if torch.allclose(got, 1 + probe, rtol=1e-14, atol=0):
+        kind = 0.0
+    elif torch.allclose(got, torch.exp(probe), rtol=1e-14, atol=0):
+        kind = 1.0
+    return fprime0, kind
+
+
 class WangTeterStyleFunctional:
     """functionals.py:728-782: T = vW + T_TF f(T_NL / (f'(0) T_TF)) with a Pauli-positivity stabilisation function f
     (f(0) = 1; default f(x) = 1 + x, i.e. a plain Wang-Teter style functional).
@@ -326,17 +343,7 @@ class WangTeterStyleFunctional:
 
     def __init__(self, init_args=None):
         self.alpha, self.beta, self.f = (5 / 6, 5 / 6, (lambda t: 1 + t)) if init_args is None else init_args
-        zero = torch.zeros((1,), dtype=torch.double, requires_grad=True)
-        if float(self.f(zero).detach()) != 1.0:
-            raise ValueError('Requires f(0) = 1')
-        self.fprime0 = float(torch.autograd.grad(self.f(zero), zero)[0])
-        probe = torch.tensor([-0.7, 0.25, 1.0], dtype=torch.double)
-        got = self.f(probe)
-        self._kind = None
-        if torch.allclose(got, 1 + probe, rtol=1e-14, atol=0):
-            self._kind = 0.0
-        elif torch.allclose(got, torch.exp(probe), rtol=1e-14, atol=0):
-            self._kind = 1.0
+        self.fprime0, self._kind = _stabiliser(self.f)
         self.__name__ = self.__qualname__ = 'WangTeterStyleFunctional'
 
     def forward(self, box_vecs, den):
@@ -348,3 +355,59 @@ class WangTeterStyleFunctional:
         return vW + TF * self.f(T_NL / TF)
 
     __call__ = forward
+
+
+# ------------------------------------------- nonlocal functionals with a tabulated, density-independent kernel (OFDFT_NLK)
+def _nlk_params(kind, p0=0.0, p1=0.0):
+    return (('nlk_kind', float(kind)), ('nlk_p0', float(p0)), ('nlk_p1', float(p1)))
+
+
+def _linear(x):
+    return 1 + x
+
+
+_STABILISERS = {_linear: (1.0, 0.0), torch.exp: (1.0, 1.0)}      # f -> _stabiliser(f)
+
+
+def KGAP(box_vecs, den, E_gap, f=_linear):
+    """functionals.py:1106-1171: vW + T_TF f(T_NL / (f'(0) T_TF)) with the gapped-jellium kernel for a band gap ``E_gap`` [eV].
+    The kernel is tabulated on the device once per (cell, round(N_e), E_gap); f(x) = 1 + x (the default) and exp are ONE engine
+    evaluation, any other f composes the native vW, TF and nonlocal energies in torch (as WangTeterStyleFunctional does).
+    ``get_stress`` works on it (analytic stress of the tabulated kernel, f = exp included)."""
+    hit = _STABILISERS.get(f)               # (detected once per function object: KGAP sits inside optimisation loops)
+    if hit is None:
+        if len(_STABILISERS) >= 16:
+            _STABILISERS.clear()
+        hit = _STABILISERS[f] = _stabiliser(f)
+    fprime0, kind = hit
+    p = _nlk_params(N.NLK_KGAP, E_gap)
+    if kind is not None:
+        return _evaluate(box_vecs, den, ('tf', 'vw', 'nlk'), p + (('wts_kind', kind),))
+    vW, TF = Weizsaecker(box_vecs, den), ThomasFermi(box_vecs, den)
+    T_NL = _evaluate(box_vecs, den, ('nlk',), p)
+    return vW + TF * f(T_NL / fprime0 / TF)
+
+
+class MiGenovaPavanello:
+    """functionals.py:1370-1451.  ``init_args=(a, b)``; call the instance or its ``forward``.  The 1-D line-integral table
+    (2000 nodes x 10000 quadrature points) and the per-k-point kernel are built on the device and rebuilt when the cell,
+    round(N_e) or (a, b) change -- which is what a FRESH instance of the reference computes (a reference instance keeps the
+    table of an earlier call while it still covers eta_max)."""
+
+    def __init__(self, init_args):
+        self.a, self.b = (float(x) for x in init_args)
+        self.__name__ = self.__qualname__ = 'MiGenovaPavanello'
+
+    def forward(self, box_vecs, den):
+        if box_vecs.requires_grad:
+            raise NotImplementedError("MiGenovaPavanello has no stress: the reference's own get_stress raises on it "
+                                      "(torch.unique, which builds its kernel, has no derivative)")
+        return _evaluate(box_vecs, den, ('tf', 'vw', 'nlk'), _nlk_params(N.NLK_MGP, self.a, self.b))
+
+    __call__ = forward
+
+
+def XuWangMa(box_vecs, den, kappa=0):
+    """functionals.py:1456-1498: vW + TF + the Taylor-expanded line-integral kernel (two powers of the density, a 2 x 2 kernel
+    matrix mixed inside one x pass); ``get_stress`` works on it."""
+    return _evaluate(box_vecs, den, ('tf', 'vw', 'nlk'), _nlk_params(N.NLK_XWM, kappa))
