@@ -268,6 +268,20 @@ int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double
 int  ofdft_ion_ion(ofdft_ctx* ctx, const double* frac_coords_host, const double* charges_host, int nions, double Rc,
                    double* E_host, double* forces_host, double* stress_host, void* stream);
 
+/* The same sum through a cell list, for supercells (ion_utils.py:293-333, whose pairs come from a cell-list neighbour list,
+ * :313-316; parameters system.py:733-754; forces and stress as autograd gives them, system.py:913-935).  Ions are wrapped into
+ * the cell, sorted into m0 x m1 x m2 cells along the lattice axes, and each target cell scans the cells that can hold an ion
+ * within Rc of it, with the lattice shift of every wrap: the pair set is that of the entry above, at a cost proportional to
+ * the pairs instead of nions^2 x shifts.  Rc <= 0: the reference's default (Rd = 2 h_max, Rc = 3 Rd^2 / h_max); Rc > 0 and
+ * Rd <= 0: Rd = sqrt(h_max Rc / 3) as above; Rc > 0 and Rd > 0: both as given (what ion_interaction_sum itself accepts).
+ * part / nparts: the call does the work of the target cells [part ncells / nparts, (part + 1) ncells / nparts) of the cell
+ * order and returns that share: the energy and stress terms of their ions, and force rows for those ions only (zero
+ * elsewhere); the sum over parts is the whole result, and 0, 1 is the whole sum.  Only sorted coordinates, charges and cell
+ * offsets go to the device; eight numbers and the owned force rows come back.  No atomics: bitwise reproducible. */
+int  ofdft_ion_ion_cells(ofdft_ctx* ctx, const double* frac_coords_host, const double* charges_host, int nions, double Rc,
+                         double Rd, int part, int nparts, double* E_host, double* forces_host /* [nions][3] or NULL */,
+                         double* stress_host /* [9] or NULL */, void* stream);
+
 /* ---- limited-memory BFGS building blocks (the consumer of the closure) ----------------
  * The reference's fixed-step optimiser (_optimizers/lbfgs/lbfgsnew.py:594-663) forms y = g - g_prev and s = t d, keeps
  * the pair if y.s > 1e-10 |s|^2, and gets the direction from the two-loop recursion: 2m dependent dot / axpy pairs over

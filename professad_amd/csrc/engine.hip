@@ -5,6 +5,7 @@
 #include <chrono>
 #ifndef OFDFT_REAL_F32
 #include "ion_kernels.h"
+#include "ion_cells.h"
 #include "stress_kernels.h"
 #endif
 
@@ -1707,6 +1708,7 @@ int ofdft_dist_chi_grad(ofdft_ctx* c, const void* chi_local, const void* v_local
 
 #ifndef OFDFT_REAL_F32
 #include "engine_ions_stress.inc.h"
+#include "engine_ion_cells.inc.h"
 #else
 // The fp32 build serves the density-optimisation hot path only.  The once-per-geometry-step quantities (ionic potential,
 // forces, stress, ion-ion sum) are fp64 work: callers run them on the fp64 library (professad_amd.ions does).
@@ -1725,6 +1727,9 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void*, const double*, int, con
     return OFDFT_F64_ONLY(c);
 }
 int ofdft_ion_ion(ofdft_ctx* c, const double*, const double*, int, double, double*, double*, double*, void*) {
+    return OFDFT_F64_ONLY(c);
+}
+int ofdft_ion_ion_cells(ofdft_ctx* c, const double*, const double*, int, double, double, int, int, double*, double*, double*, void*) {
     return OFDFT_F64_ONLY(c);
 }
 }

@@ -600,6 +600,16 @@ class DistEngine:
         return ionic_potential(self._f64_stages(), self._box_np.reshape(3, 3), species,
                                pme_order).to(self.stages.dtype).contiguous()
 
+    def ion_ion(self, frac, charges, Rc=None, Rd=None):
+        """ion-ion energy, forces [n,3] and stress [3,3] of the full system through the cell list (see ions.ion_ion,
+        method='cells'): the ions are replicated, rank r does the target cells of part r of `world`, and one all-reduce
+        of [E, stress(9), forces(3 n)] gives every rank the whole result"""
+        from .ions import ion_ion
+        E, F, S = ion_ion(self._f64_stages(), self._box_np.reshape(3, 3), frac, charges, Rc=Rc, Rd=Rd, method='cells',
+                          part=self.comm.rank, nparts=self.comm.nranks)
+        v = self.comm.all_reduce_sum(np.concatenate([[E], S.reshape(9), F.reshape(-1)]), self.stages.device)
+        return float(v[0]), v[10:].reshape(-1, 3), v[1:10].reshape(3, 3)
+
     def close(self, sync_peers=False):
         """sync_peers=True (every rank must then call close, in the same order): with the ipc transport attached, every rank first
         lets go of the peers' arenas, the ranks meet, and only then is any arena freed (ofdft_ipc_detach) -- for jobs that go on to

@@ -125,19 +125,92 @@ def ion_electron_stress(engine, box_vecs, den, species, pme_order=None):
     return total
 
 
-def ion_ion(engine, box_vecs, frac, charges, Rc=None):
+# Bounds of ion_ion(method=...).  tools/ionion_probe.py measures the rates they stand for (profiles/ionion_cells.jsonl); NOT
+# MEASURED yet, so both are set from estimates and are to be replaced by the probe's figures.
+# MAX_PAIRS: the pair estimate above which method='cells' / 'auto' refuse to start, meant as about a minute of the cell-list
+# kernel.  Estimate: the kernel's listing holds 534 fp64 vector instructions, about 350 of them in the pair loop (erfc, exp,
+# sqrt, two divisions, eleven sums); fp64 vector issue on gfx950 is 16 lanes per cycle per SIMD, 256 CUs x 4 SIMDs x 16 x
+# 2.4 GHz = 3.9e13 lane-instructions/s, so at most 1.1e11 pairs/s; half of that for a minute: 60 s x 5e10 = 3e12 pairs.
+# AUTO_DIRECT_CANDIDATES: below this many (i, j, shift) candidates 'auto' takes the direct kernel (one short launch; the cell
+# list first sorts the ions and tests the neighbour cells on the host).
+MAX_PAIRS = 3.0e12
+AUTO_DIRECT_CANDIDATES = 1.0e7
+
+
+def _spacings(box):
+    """interplanar spacings h_d of the lattice (rows of `box` = lattice vectors)"""
+    return 1.0 / np.sqrt(np.sum(np.linalg.inv(box.T) ** 2, axis=1))
+
+
+def ion_ion_cost(box_vecs, nions, Rc=None, frac=None):
+    """What an ion-ion call would cost, without an engine: Rc and Rd as System.__ion_ion_interaction sets them
+    (system.py:744-750), `pairs_estimate` = nions^2 (4/3) pi Rc^3 / vol ordered pairs within Rc (each pair counted from both
+    ends, as both kernels visit it), and `direct_candidates` = nions^2 prod(2 nmax_d + 1), the (i, j, lattice shift)
+    combinations the direct kernel scans, nmax_d = ceil(Rc / h_d + span_d).  span_d is the spread of the fractional
+    coordinates along axis d: taken from `frac` when given, 1 (the bound for wrapped coordinates) otherwise."""
+    box = np.asarray(torch.as_tensor(box_vecs).detach().cpu().numpy(), dtype=np.float64).reshape(3, 3)
+    h = _spacings(box)
+    h_max = float(h.max())
+    if Rc:
+        Rc = float(Rc)
+        Rd = math.sqrt(h_max * Rc / 3.0)
+    else:
+        Rd = 2.0 * h_max
+        Rc = 3.0 * Rd * Rd / h_max
+    if frac is None:
+        span = np.ones(3)
+    else:
+        f = np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3)
+        span = f.max(0) - f.min(0)
+    nmax = np.ceil(Rc / h + span).astype(np.int64)
+    vol = abs(float(np.linalg.det(box)))
+    n = int(nions)
+    return {'Rc': Rc, 'Rd': Rd, 'pairs_estimate': float(n) * n * 4.0 / 3.0 * math.pi * Rc ** 3 / vol,
+            'direct_candidates': float(n) * n * float(np.prod(2 * nmax + 1))}
+
+
+def ion_ion(engine, box_vecs, frac, charges, Rc=None, Rd=None, method='direct', part=0, nparts=1, max_pairs=None):
     """Ion-ion energy [Ha], forces [n,3] (Ha/bohr) and stress [3,3] (Ha/bohr^3): ion_interaction_sum with System's
-    parameter heuristics (ion_utils.py:293-333, system.py:733-754) and its autograd derivatives (system.py:913-935)."""
-    engine = _f64(engine)
-    engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
+    parameter heuristics (ion_utils.py:293-333, system.py:733-754) and its autograd derivatives (system.py:913-935).
+
+    method='direct' (default): every (i, j, lattice shift) is scanned (`ofdft_ion_ion`): right for primitive cells, cost
+    nions^2 x shifts.  method='cells': the cell list (`ofdft_ion_ion_cells`), for supercells; it also takes an explicit damping
+    radius `Rd` (with `Rc`), and `part` / `nparts`: the share of part `part` of `nparts` contiguous ranges of target cells
+    (force rows of its own ions only; the sum over parts is the whole result).  method='auto': the direct kernel below
+    AUTO_DIRECT_CANDIDATES candidates, the cell list otherwise.  'cells' and 'auto' raise ValueError when `ion_ion_cost`
+    estimates more than `max_pairs` (default MAX_PAIRS) pairs, before any engine work."""
+    if method not in ('direct', 'cells', 'auto'):
+        raise ValueError("method must be 'direct', 'cells' or 'auto'")
+    if Rd is not None and not Rc:
+        raise ValueError('Rd needs an explicit Rc')
     frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
     z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
     if z.size != frac.shape[0]:
         raise ValueError('one charge per ion')
+    if method == 'direct':
+        if Rd is not None or part != 0 or nparts != 1:
+            raise ValueError("method='direct' derives Rd from Rc and computes the whole sum: Rd, part and nparts need method='cells'")
+    else:
+        cost = ion_ion_cost(box_vecs, frac.shape[0], Rc, frac)
+        if method == 'auto':
+            method = 'direct' if (cost['direct_candidates'] < AUTO_DIRECT_CANDIDATES and Rd is None and nparts == 1) else 'cells'
+        limit = MAX_PAIRS if max_pairs is None else max_pairs
+        if method == 'cells' and cost['pairs_estimate'] > limit:
+            raise ValueError('ion_ion: about %.3g pairs within Rc = %.6g bohr (pairs_estimate) exceed max_pairs = %.3g; the direct '
+                             'kernel would scan %.3g candidates (direct_candidates).  Pass a smaller Rc or raise max_pairs.'
+                             % (cost['pairs_estimate'], cost['Rc'], limit, cost['direct_candidates']))
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    dp = C.POINTER(C.c_double)
     E = C.c_double(0.0)
     F = np.zeros_like(frac)
     S = np.zeros(9)
+    if method == 'cells':
+        rc = engine.lib.ofdft_ion_ion_cells(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
+                                            float(Rc) if Rc else 0.0, float(Rd) if Rd else 0.0, int(part), int(nparts),
+                                            C.byref(E), F.ctypes.data_as(dp), S.ctypes.data_as(dp), engine._stream())
+        engine._check(rc, 'ofdft_ion_ion_cells')
+        return E.value, F, S.reshape(3, 3)
     rc = engine.lib.ofdft_ion_ion(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
                                   float(Rc) if Rc else 0.0, C.byref(E), F.ctypes.data_as(dp), S.ctypes.data_as(dp),
                                   engine._stream())
