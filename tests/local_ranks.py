@@ -98,6 +98,22 @@ class LocalRanks:
             out.append(self._timed(r, s.chi_grad, chis[r], vs[r], cscale, mu))
         return E, mu, torch.cat(out)
 
+    def energy_potential(self, den, vext):
+        """full-grid density / v_ext (device tensors) -> (E_terms, full-grid dE/dn): the sequence of
+        professad_amd.distributed.run_potential (density in, N_e from the ranks' summed densities)"""
+        sl = [s.plan.x_range() for s in self.st]
+        dens = [den[x].contiguous() for x in sl]
+        vexts = [vext[x].contiguous() if vext is not None else None for x in sl]
+        nsum = sum(self._timed(r, s.sumsq, dens[r], False) for r, s in enumerate(self.st))
+        nel = nsum / self.npts * self.vol
+        vs = [torch.empty_like(d) for d in dens]
+        for r, s in enumerate(self.st):
+            self._timed(r, s.begin, dens[r], False, 1.0, nel, vexts[r], vs[r])
+        gs = self._stages()
+        for s in self.st:
+            E, _ = s.energies(gs)
+        return E, torch.cat(vs)
+
     def close(self):
         for s in self.st:
             s.close()

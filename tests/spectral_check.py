@@ -30,6 +30,14 @@ K_TOL = {'f64': 1e-9, 'f32': 8e-3}
 # chirp-z x pass, the three-pass form and the plain DFT kernels, and 255^3).  Measured maxima there:
 #   fp64  E 7.6e-15, v 1.7e-13 (chi.grad 1.0e-13), mu 6.7e-16, per k-point 1.9e-10 (10 x 383 x 14 three-pass and fused)
 #   fp32  E 7.9e-7,  v 2.4e-5  (chi.grad 1.3e-5),  mu 3.2e-7,  per k-point 4.5e-3 (255^3 potential)
+# ... and for the slab-decomposed pipeline (tests/test_slab_matrix_gpu.py: 2, 4 and 8 emulated ranks, nine exchange geometries,
+# every term set the slab path serves, both GGA forms, both entry points).  Measured maxima there:
+#   fp64  E 9.0e-15, v 1.6e-13 (chi.grad 1.1e-13), mu 1.3e-15, per k-point 4.8e-11 (32 x 64 x 270 on 8 ranks, potential)
+#   fp32  E 3.5e-7,  v 1.5e-5  (chi.grad 5.7e-6),  mu 1.5e-7,  per k-point 1.4e-3 (32 x 64 x 270 on 8 ranks, potential)
+# and the largest difference between the slabs and one engine on the same inputs (relative; bounds 1e-12 and 5e-6 / 5e-4):
+#   fp64  v 1.6e-13 (the Lindhard-factor sets, whose N_e sums in another order; 2.6e-16 for WGC99 + PBE), chi.grad 1.6e-14,
+#         energies 4.0e-15, mu 1.4e-15
+#   fp32  v 8.4e-7, chi.grad 6.4e-7, energies 5.7e-8, mu 1.4e-7
 
 
 def spectrum(a):

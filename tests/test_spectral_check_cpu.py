@@ -9,6 +9,7 @@ import pytest
 import spectral_check as sc
 import test_chirpz_matrix_gpu as C
 import test_extent_matrix_gpu as M
+import test_slab_matrix_gpu as S
 from oracle import ions as oi
 
 SHAPE, CELL = (128, 32, 64), 'ortho'
@@ -108,6 +109,61 @@ def test_single_k_point_errors_are_rejected_on_odd_extents(shape, cell):
                 got = sc.kspace_error(bad, vo, sc.TAU[p], vok)
                 assert abs(got - REL[p]) <= 1e-3 * REL[p], (shape, name, p, got)
                 assert _rejected(bad, vo, p, vok), (shape, name, p, sc.errors(bad, vo, p, vok))
+
+
+def slab_boundary_points(shape, P):
+    """{name: (kx, ky, kz)} of the k-points where the exchange layout of P slab ranks changes record (engine_ctx.h: XchgGeom):
+    the first and the last x plane of a rank's slab, the first y line of a rank's slab -- each once in a remainder kz plane
+    (kz >= nzm = 8 (nzc / 8)) and once in the last full 8-plane block -- and both kz locations at a (kx, ky) inside a slab.
+    Without remainder planes (nzc a multiple of 8) the last plane of the last block stands in."""
+    n0, n1, n2 = shape
+    nxl, nyl, nzc = n0 // P, n1 // P, n2 // 2 + 1
+    nzm = nzc // 8 * 8
+    kz_rem = nzm + 1 if nzc - nzm > 1 else nzc - 1          # (one remainder plane: it is the Nyquist plane)
+    kz_blk = nzm - 3
+    inner = (n0 // 2 + nxl // 2) % n0, nyl // 2          # inside a slab wherever a slab has an inside (nxl >= 3, nyl >= 2)
+    pts = {'kz_remainder_plane': (inner[0], inner[1], kz_rem), 'kz_last_full_block': (inner[0], inner[1], kz_blk)}
+    for r in range(1, P):
+        kz = (kz_rem, kz_blk) if r % 2 else (kz_blk, kz_rem)
+        pts['kx_first_plane_of_rank_%d' % r] = (r * nxl, inner[1], kz[0])
+        pts['kx_last_plane_of_rank_%d' % (r - 1)] = (r * nxl - 1, inner[1], kz[1])
+        pts['ky_first_line_of_rank_%d' % r] = (inner[0], r * nyl, kz[0])
+    return pts
+
+
+@pytest.mark.parametrize('shape,P,cell', S.GEOMETRIES + [g[:3] for g in S.CHUNKED], ids=[S._gid(g) for g in S.GEOMETRIES + S.CHUNKED])
+def test_single_k_point_errors_on_slab_boundaries_are_rejected(shape, P, cell):
+    """what shows that the rows of tests/test_slab_matrix_gpu.py can fail: a single-k-point error at a slab boundary of its
+    geometries is rejected at the sizes of the sensitivity test above (1e-6 with the fp64 bounds, 1e-2 with the fp32 ones), and
+    accepted at a tenth of what the bounds admit there.  (Not at a tenth of the rejected size: with the fp64 bounds 1e-7 is
+    still a hundred times the per-k bound of 1e-9; and on the smallest grids here, 2048 and 4096 points, one k-point is so
+    large a share of the field that the real-space bound is the tighter of the two.)"""
+    n0, n1, n2 = shape
+    nzc = n2 // 2 + 1
+    pts = slab_boundary_points(shape, P)
+    assert len(pts) == 3 * (P - 1) + 2
+    for name, k in pts.items():
+        assert 0 <= k[0] < n0 and 0 <= k[1] < n1 and 0 < k[2] < nzc, (name, k)
+    assert all(k[0] % (n0 // P) == 0 for nm, k in pts.items() if nm.startswith('kx_first'))
+    assert all((k[0] + 1) % (n0 // P) == 0 for nm, k in pts.items() if nm.startswith('kx_last'))
+    assert all(k[1] % (n1 // P) == 0 and k[1] for nm, k in pts.items() if nm.startswith('ky_first'))
+    nzm = nzc // 8 * 8
+    assert pts['kz_last_full_block'][2] // 8 == nzm // 8 - 1
+    assert pts['kz_remainder_plane'][2] >= nzm or nzc == nzm
+    o = M.oracle(shape, cell, 'vwgtf1_h')
+    try:
+        for vo, vok in ((o['v'], o['vk']), (o['g'], o['gk'])):
+            for p in ('f64', 'f32'):
+                for name, k in pts.items():
+                    bad = sc.perturb(vo, k, REL[p], sc.TAU[p], vok)
+                    assert _rejected(bad, vo, p, vok), (shape, P, name, k, p, sc.errors(bad, vo, p, vok))
+                    # the errors are linear in the size of the change: a tenth of what the tighter criterion admits is accepted
+                    ev, ek = sc.errors(bad, vo, p, vok)
+                    assert abs(ek - REL[p]) <= 1e-3 * REL[p], (shape, P, name, p, ek)
+                    ok = 0.1 * REL[p] * min(sc.V_TOL[p] / ev, sc.K_TOL[p] / ek)
+                    sc.check(sc.perturb(vo, k, ok, sc.TAU[p], vok), vo, p, vok=vok)
+    finally:
+        M._ORACLE.pop((shape, cell, 'vwgtf1_h'), None)
 
 
 @pytest.mark.parametrize('shape,cell', _shapes(), ids=['%dx%dx%d-%s' % (s + (c,)) for s, c in _shapes()])
