@@ -316,12 +316,13 @@ int ensure_wgc_tables(ofdft_ctx* c, long long nel_rounded, hipStream_t st, doubl
 // takes N_e from a device sum of the density, the closure from its caller; for one density the two differ in the last bits, so
 // a caller that ALTERNATES the two entry points with XWM rebuilds the table (and re-captures its graph) on every switch.
 // Results are those of the N_e each call was given; an optimisation loop, which stays with one entry point and one N_e, builds once.
-int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st) {
-    const NlPow p = nl_pow(c);
-    const long long nel_r = std::llround(nel);
+int ensure_nlk_table(ofdft_ctx* c, const TermScalars& ts, hipStream_t st) {
+    const NlPow& p = ts.nlp;
+    const double nel = ts.nel;
+    const long long nel_r = ts.nel_r;
     if (c->nlk_valid && c->nlk_key_nel == nel_r && (p.kind != NLK_XWM || c->nlk_key_nel_exact == nel)) return 0;
     if (nel_r < 1) return fail(c, OFDFT_EINVAL, "OFDFT_NLK: the electron number %g rounds to zero (n0 = round(N_e) / vol)", nel);
-    const double n0 = (double)nel_r / c->vol, kf = std::cbrt(3.0 * kPi * kPi * n0);
+    const double n0 = ts.n0_r, kf = std::cbrt(3.0 * kPi * kPi * n0);
     const double ctf = (double)0.3L * std::pow(3.0 * kPi * kPi, (double)2 / 3);
     const double x0 = c->params[OFDFT_P_NLK_P0], x1 = c->params[OFDFT_P_NLK_P1];
     const int ncol = p.kind == NLK_XWM ? 2 : 1;
@@ -349,7 +350,7 @@ int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st) {
         t.w = c->d_nlk_w;
     } else {
         const double cx = kPi * kPi / std::cbrt(3.0 * kPi * kPi), n2k = std::pow(n0, 2.0 * x0);
-        t.inv2kf = 1.0 / (2.0 * std::cbrt(3.0 * kPi * kPi * (nel / c->vol)));
+        t.inv2kf = ts.wt_inv2kf;        // eta from the un-rounded N_e (functionals.py:631-639), everything else from n0 = round(N_e) / vol
         t.pref = 2.0 * 18.0 / ((6.0 * x0 + 5.0) * (6.0 * x0 + 5.0)) * cx / n2k / ctf;
         t.p1 = cx / (6.0 * n0) / n2k / ctf;
         t.p2 = n0 / (p.al * p.al);
@@ -367,6 +368,30 @@ int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st) {
 namespace {
 
 // ---------------------------------------------------------------------------------- combine / energies
+// the reduced sums of an evaluation (combine scalars, GGA scalars) as per-term energies and sum(v n) dV: every pipeline ends here
+void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pbe_sums, double* E_terms, double* vn_int) {
+    const unsigned mask = c->mask;
+    const double dV = c->dV;
+    if (mask & OFDFT_ION_ELECTRON) E_terms[0] = sums[0] * dV;
+    if (mask & OFDFT_HARTREE) E_terms[1] = sums[1] * dV;
+    if (mask & OFDFT_TF) E_terms[2] = sums[2] * dV;
+    if (mask & OFDFT_VW) E_terms[3] = sums[3] * dV;
+    if (mask & OFDFT_WT_NL) E_terms[4] = sums[4] * dV;
+    if (mask & OFDFT_WGC99_NL) E_terms[5] = sums[5] * dV;
+    if (mask & OFDFT_LDA_X) E_terms[6] = sums[6] * dV;
+    // one local correlation flavour is expected; if several are set their sum is split evenly
+    int nc = 0;
+    for (int b = 7; b <= 9; ++b) nc += (mask >> b) & 1;
+    for (int b = 7; b <= 9; ++b)
+        if ((mask >> b) & 1) E_terms[b] = sums[7] * dV / nc;
+    if (mask & OFDFT_PBE_X) E_terms[10] = pbe_sums[0] * dV;
+    if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
+    if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
+    if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
+    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
+    *vn_int = sums[8] * dV;
+}
+
 // launch the combine kernel and turn its partial sums into per-term energies
 // defer (the closure of the unfused / chirp-z pipelines, round 4): nothing waits here -- the sums are reduced on the device in a fixed
 // order (c->d_reduced, mirrored into the pinned host block by the reduce kernel), chi_grad forms mu from them on the device and the
@@ -374,7 +399,6 @@ namespace {
 // sums, the combine sums, the end).  Not for the two-pass stabilised WT-style functional, whose weights pass through the host.
 int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, double* E_terms, double* vn_int,
                  hipStream_t st, bool defer = false) {
-    const unsigned mask = c->mask;
     const long long npts = c->npts;
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
     CombineArgs cb = ca;     // every pointer valid: unused inputs alias the density (their terms are masked off)
@@ -407,27 +431,7 @@ int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, do
         sums[2] *= wts_f;
         sums[4] = 0.0;
     }
-    const double dV = c->dV;
-    if (mask & OFDFT_ION_ELECTRON) E_terms[0] = sums[0] * dV;
-    if (mask & OFDFT_HARTREE) E_terms[1] = sums[1] * dV;
-    if (mask & OFDFT_TF) E_terms[2] = sums[2] * dV;
-    if (mask & OFDFT_VW) E_terms[3] = sums[3] * dV;
-    if (mask & OFDFT_WT_NL) E_terms[4] = sums[4] * dV;
-    if (mask & OFDFT_WGC99_NL) E_terms[5] = sums[5] * dV;
-    if (mask & OFDFT_LDA_X) E_terms[6] = sums[6] * dV;
-    // one local correlation flavour is expected; if several are set their sum is split evenly
-    {
-        int nc = 0;
-        for (int b = 7; b <= 9; ++b) nc += (mask >> b) & 1;
-        for (int b = 7; b <= 9; ++b)
-            if ((mask >> b) & 1) E_terms[b] = sums[7] * dV / nc;
-    }
-    if (mask & OFDFT_PBE_X) E_terms[10] = pbe_sums[0] * dV;
-    if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
-    if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
-    if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
-    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
-    *vn_int = sums[8] * dV;
+    energies_from_sums(c, sums, pbe_sums, E_terms, vn_int);
     return 0;
 }
 
@@ -458,8 +462,9 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     ca.v_out = v_out;
     ca.npts = npts;
     ca.mask = combine_mask(c);
-    ca.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
-    ca.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;      // n0 = round(N_e) / vol (functionals.py:268-270)
+    TermScalars ts = term_scalars(c, nel);
+    if (int rc = ensure_term_tables(c, ts, st)) return rc;
+    ca.tc = ts.tc;
     double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
 
     cplx *s0 = nullptr, *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
@@ -471,11 +476,9 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     // batch; B: spectral multiplies; C: inverse batches; D: the GGA mid stage and its flux / divergence transforms.
     const bool has_n = mask & (OFDFT_HARTREE | kGgaAny), has_h = mask & OFDFT_HARTREE, has_g = mask & kGgaAny, has_vw = mask & OFDFT_VW,
                has_wt = mask & (OFDFT_WT_NL | OFDFT_NLK);
-    const NlPow nlp = nl_pow(c);
+    const NlPow& nlp = ts.nlp;
     const double wal = nlp.e_a, wbe = nlp.e_b;      // powers behind s_wa / s_wb (Wang-Teter: alpha, beta)
     const bool wt2 = nlp.two;
-    if (nlp.nlk)
-        if (int rc = ensure_nlk_table(c, nel, st)) return rc;
     real *t_sqrt = nullptr, *t_pb = nullptr, *t_pa = nullptr;
     cplx *s_vw = nullptr, *s_wb = nullptr, *s_wa = nullptr, *s4 = nullptr;
     real *vh = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *dfdn = nullptr, *dv = nullptr, *lapn = nullptr, *lap = nullptr,
@@ -605,9 +608,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
             ca.lap_s = lap;
         }
         if (has_wt) {
-            const double nbar = nel / c->vol;                                    // functionals.py:646-647
-            const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
-            const double pref = 5.0 / (9.0 * wal * wbe * std::pow(nbar, wal + wbe - kFiveThirds));
+            const double pref = ts.wt_pref, inv2kf = ts.wt_inv2kf;
             if (int rc = real_ws(c, "conv_b", &cb)) return rc;
             if (nlp.nlk) {                // the kernel comes from the table: one multiply kernel, or one chirp-z x pass over both spectra
                 if (wt2 && !nlp.sym) {    // KGAP: both spectra times the one column
@@ -638,11 +639,11 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
                 }
             } else if (!xm)
                 OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_LINDHARD>), dim3(sp_grid), dim3(256), 0, s_wb, s_wb, c->kg, pref,
-                                   1.0 / (2.0 * kf));
+                                   inv2kf);
             else {
                 const cplx* xi[1] = {s_wb};
                 cplx* xo[1] = {s_wb};
-                if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixScale<SPEC_LINDHARD>{c->kg, (real)pref, (real)(1.0 / (2.0 * kf))}, st)) return rc;
+                if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixScale<SPEC_LINDHARD>{c->kg, (real)pref, (real)inv2kf}, st)) return rc;
             }
             iin[ni] = s_wb; iout[ni++] = cb;
             ca.conv_b = cb;
@@ -653,20 +654,15 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
                     // (mixed above)
                 } else if (!xm)
                     OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_LINDHARD>), dim3(sp_grid), dim3(256), 0, s_wa, s_wa, c->kg, pref,
-                                       1.0 / (2.0 * kf));
+                                       inv2kf);
                 else {
                     const cplx* xi[1] = {s_wa};
                     cplx* xo[1] = {s_wa};
-                    if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixScale<SPEC_LINDHARD>{c->kg, (real)pref, (real)(1.0 / (2.0 * kf))}, st)) return rc;
+                    if (int rc = bluestein_xmix<1, 1>(c, xi, xo, MixScale<SPEC_LINDHARD>{c->kg, (real)pref, (real)inv2kf}, st)) return rc;
                 }
                 iin[ni] = s_wa; iout[ni++] = cva;
                 ca.conv_a = cva;
             }
-            ca.wt_alpha = nlp.al;
-            ca.wt_beta = nlp.be;
-            ca.wt_nbar_pa = nlp.nlk ? 0.0 : std::pow(nbar, nlp.al);     // (the tabulated kernels are 0 at k = 0 and the reference subtracts nothing)
-            ca.wt_is_56 = (nlp.al == kFiveSixths && nlp.be == kFiveSixths) ? 1 : 0;
-            ca.wt_sym = nlp.sym;
         }
         for (int b0 = 0; b0 < ni; b0 += 4)
             if (int rc = (xm ? bluestein_inv_yz_multi(c, iin + b0, iout + b0, std::min(4, ni - b0), inv_n, st)
@@ -705,9 +701,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     }
     if (mask & OFDFT_WGC99_NL) {
         const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
-        const long long nel_r = std::llround(nel);                           // functionals.py:952
-        double nref;
-        if (int rc = ensure_wgc_tables(c, nel_r, st, &nref)) return rc;
+        const real nref = ts.tc.nref;
         real *t0, *t1, *t2, *o[6];
         if (int rc = real_ws(c, "t0", &t0)) return rc;
         if (int rc = real_ws(c, "t1", &t1)) return rc;
@@ -742,10 +736,6 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
         }
         ca.u0 = o[0]; ca.u1 = o[1]; ca.u2 = o[2];
         ca.gA = o[3]; ca.gB = o[4]; ca.gC = o[5];
-        ca.wgc_alpha = al;
-        ca.wgc_beta = be;
-        ca.nref = nref;
-        ca.wgc_sum_53 = (std::fabs(al + be - kFiveThirds) < 4e-16) ? 1 : 0;
     }
     return finish_terms(c, ca, pbe_sums, E_terms, vn_int, st, defer);
 }
@@ -773,8 +763,10 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
     ca.v_out = v_out;
     ca.npts = npts;
     ca.mask = combine_mask(c);
-    ca.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
-    ca.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;      // n0 = round(N_e) / vol (functionals.py:268-270)
+    TermScalars ts = term_scalars(c, nel);
+    if (int rc = ensure_term_tables(c, ts, st)) return rc;
+    ca.tc = ts.tc;
+    const NlPow& nlp = ts.nlp;
     double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
     cplx* s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const char* sn[5] = {"s0", "s1", "s2", "s3", "s4"};
@@ -843,40 +835,30 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
         ca.lap_s = lap;
     }
     if (mask & OFDFT_WT_NL) {
-        const double al = c->params[OFDFT_P_WT_ALPHA], be = c->params[OFDFT_P_WT_BETA];
-        const double nbar = nel / c->vol;
-        const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
-        const double pref = 5.0 / (9.0 * al * be * std::pow(nbar, al + be - kFiveThirds));
         real *tmp, *cb;
         if (int rc = real_ws(c, "t0", &tmp)) return rc;
         if (int rc = real_ws(c, "conv_b", &cb)) return rc;
-        const MixScale<SPEC_LINDHARD> lind{c->kg, (real)pref, (real)(1.0 / (2.0 * kf))};
+        const MixScale<SPEC_LINDHARD> lind{c->kg, (real)ts.wt_pref, (real)ts.wt_inv2kf};
         XfIo io{};
         io.in[0] = s[0];
         io.out[0] = s[0];
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, be);
+        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.e_b);
         if (int rc = fwd_zy(c, tmp, s[0], st)) return rc;
         if (int rc = xfused<1, 1>(c, io, lind, st, "xfused_lind")) return rc;
         if (int rc = inv_yz(c, s[0], cb, inv_n, st)) return rc;
         ca.conv_b = cb;
         ca.conv_a = nullptr;
-        if (al != be) {
+        if (nlp.two) {
             real* cva;
             if (int rc = real_ws(c, "conv_a", &cva)) return rc;
-            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, al);
+            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.e_a);
             if (int rc = fwd_zy(c, tmp, s[0], st)) return rc;
             if (int rc = xfused<1, 1>(c, io, lind, st, "xfused_lind")) return rc;
             if (int rc = inv_yz(c, s[0], cva, inv_n, st)) return rc;
             ca.conv_a = cva;
         }
-        ca.wt_alpha = al;
-        ca.wt_beta = be;
-        ca.wt_nbar_pa = std::pow(nbar, al);
-        ca.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
     }
     if (mask & OFDFT_NLK) {          // the Wang-Teter stages above with the kernel from the table (one pass over both spectra for XWM)
-        const NlPow nlp = nl_pow(c);
-        if (int rc = ensure_nlk_table(c, nel, st)) return rc;
         real *tmp, *cb, *cva = nullptr;
         if (int rc = real_ws(c, "t0", &tmp)) return rc;
         if (int rc = real_ws(c, "conv_b", &cb)) return rc;
@@ -905,17 +887,10 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
             if (int rc = inv_yz(c, s[1], cva, inv_n, st)) return rc;
         ca.conv_b = cb;
         ca.conv_a = cva;
-        ca.wt_alpha = nlp.al;
-        ca.wt_beta = nlp.be;
-        ca.wt_nbar_pa = 0.0;
-        ca.wt_is_56 = (nlp.al == kFiveSixths && nlp.be == kFiveSixths) ? 1 : 0;
-        ca.wt_sym = nlp.sym;
     }
     if (mask & OFDFT_WGC99_NL) {
         const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
-        const long long nel_r = std::llround(nel);
-        double nref;
-        if (int rc = ensure_wgc_tables(c, nel_r, st, &nref)) return rc;
+        const real nref = ts.tc.nref;
         real *t[3], *o[6];
         const char* tn[3] = {"t0", "t1", "t2"};
         const char* names[6] = {"u0", "u1", "u2", "gA", "gB", "gC"};
@@ -942,10 +917,6 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
         }
         ca.u0 = o[0]; ca.u1 = o[1]; ca.u2 = o[2];
         ca.gA = o[3]; ca.gB = o[4]; ca.gC = o[5];
-        ca.wgc_alpha = al;
-        ca.wgc_beta = be;
-        ca.nref = nref;
-        ca.wgc_sum_53 = (std::fabs(al + be - kFiveThirds) < 4e-16) ? 1 : 0;
     }
     return finish_terms(c, ca, pbe_sums, E_terms, vn_int, st);
 }

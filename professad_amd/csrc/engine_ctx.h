@@ -224,6 +224,54 @@ inline NlPow nl_pow(const ofdft_ctx* c) {
 inline unsigned combine_mask(const ofdft_ctx* c) {
     return (c->mask & OFDFT_NLK) ? ((c->mask & ~OFDFT_NLK) | OFDFT_WT_NL) : c->mask;
 }
+// Where a term's host parameters live.  Every host-side number an evaluation derives from (mask, params, N_e, vol) -- for the
+// unfused / chirp-z, x-fused, z-fused and persistent-kernel paths and for the stress -- is formed here, once.
+// Which electron number each term takes follows the reference:
+//   un-rounded N_e (nbar): Wang-Teter's nbar, k_F and nbar^alpha (functionals.py:646-651), and the eta of XWM's kernel table
+//                          (functionals.py:631-639: wt_inv2kf is also what ensure_nlk_table gives XWM);
+//   round(N_e) (nel_r, n0_r): the n0 of vWGTF (:268-270, :299-300), the n_ref of WGC99 (:952-953) and the n0 of the tabulated
+//                          kernels KGAP / MGP / XWM (:1157-1158, :1422-1423, :1473-1474).
+struct TermScalars {
+    double nel = 0.0;          // N_e as the caller has it: mean(den) * vol from a device sum, or the closure's argument
+    long long nel_r = 0;       // round(N_e)
+    double nbar = 0.0;         // N_e / vol
+    double n0_r = 0.0;         // round(N_e) / vol
+    NlPow nlp;
+    double wt_kf = 0.0;        // (3 pi^2 nbar)^(1/3)
+    double wt_inv2kf = 0.0;    // eta = |k| wt_inv2kf
+    double wt_pref = 0.0;      // Lindhard kernel prefactor of the Wang-Teter family, 5 / (9 alpha beta nbar^(alpha + beta - 5/3))
+    TermConsts tc{};           // what the combine kernels read (tc.nref: ensure_term_tables)
+};
+inline TermScalars term_scalars(const ofdft_ctx* c, double nel) {
+    TermScalars t;
+    t.nel = nel;
+    t.nel_r = std::llround(nel);
+    t.nbar = nel / c->vol;
+    t.n0_r = (double)t.nel_r / c->vol;
+    t.nlp = nl_pow(c);
+    t.wt_kf = std::cbrt(3.0 * kPi * kPi * t.nbar);
+    t.wt_inv2kf = 1.0 / (2.0 * t.wt_kf);
+    t.tc.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
+    t.tc.gtf_inv_n0 = (c->mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;
+    if (t.nlp.on) {
+        const double al = t.nlp.al, be = t.nlp.be;
+        // the tabulated kernels carry their own prefactor (ensure_nlk_table), are 0 at k = 0, and the reference subtracts no
+        // nbar^alpha from their energy (functionals.py:1168, :1449, :1481 against :651)
+        if (!t.nlp.nlk) t.wt_pref = 5.0 / (9.0 * al * be * std::pow(t.nbar, al + be - kFiveThirds));
+        t.tc.wt_alpha = al;
+        t.tc.wt_beta = be;
+        t.tc.wt_nbar_pa = t.nlp.nlk ? 0.0 : std::pow(t.nbar, al);
+        t.tc.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
+        t.tc.wt_sym = t.nlp.sym;
+    }
+    if (c->mask & OFDFT_WGC99_NL) {
+        const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
+        t.tc.wgc_alpha = al;
+        t.tc.wgc_beta = be;
+        t.tc.wgc_sum_53 = (std::fabs(al + be - kFiveThirds) < 4e-16) ? 1 : 0;
+    }
+    return t;
+}
 inline bool zfused_serves(const ofdft_ctx* c) {
     return c->fast && c->pipeline == 0 && c->n2 / 2 <= 512 && (!gga_needs_laplacian(c) || c->gga_split);
 }
@@ -424,7 +472,18 @@ inline MixWgc wgc_tab(ofdft_ctx* c, long long off = 0) {
     return MixWgc{t01 + off, reinterpret_cast<const real*>(t01 + c->g.total) + off, (real)c->wgc_ck};
 }
 // OFDFT_NLK: build "t:nlk" for (cell, round(N_e) [, N_e], kind, parameters) if the key changed; the mix functors over its columns
-int ensure_nlk_table(ofdft_ctx* c, double nel, hipStream_t st);
+int ensure_nlk_table(ofdft_ctx* c, const TermScalars& ts, hipStream_t st);
+// the k-space tables of the active terms, (re)built where their key changed; fills ts.tc.nref
+inline int ensure_term_tables(ofdft_ctx* c, TermScalars& ts, hipStream_t st) {
+    if (ts.nlp.nlk)
+        if (int rc = ensure_nlk_table(c, ts, st)) return rc;
+    if (c->mask & OFDFT_WGC99_NL) {
+        double nref;
+        if (int rc = ensure_wgc_tables(c, ts.nel_r, st, &nref)) return rc;
+        ts.tc.nref = nref;
+    }
+    return 0;
+}
 inline const real* nlk_col(ofdft_ctx* c, int col) { return (const real*)c->ws["t:nlk"].p + (size_t)col * c->g.total; }
 bool resident_serves(const ofdft_ctx* c);
 constexpr int kResidentDeclined = 1;       // resident_closure: not an error -- the caller takes the graph / staged path instead

@@ -231,7 +231,10 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
     double nsum;
     if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
     if (int rc = global_sums(c, &nsum, 1)) return rc;
-    const double nbar = nsum * invN;                    // N_e / vol, un-rounded (functionals.py:634)
+    // the terms' host scalars (term_scalars, engine_ctx.h).  The un-rounded mean density stays the one formed here, straight
+    // from the sum: ts.nbar = (nsum dV) / vol may differ from it in the last bit.  (functionals.py:634)
+    const TermScalars ts = term_scalars(c, nsum * c->dV);
+    const double nbar = nsum * invN;
     cplx *s0 = nullptr, *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
     double *gx = nullptr, *gy = nullptr, *gz = nullptr, *lapn = nullptr;
     if (int rc = spec_ws(c, "s0", &s0)) return rc;
@@ -268,7 +271,7 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         double r[kStressRealScalars];
         OFDFT_LAUNCH(c, st, "stress_real", stress_real_kernel, dim3(blocks), dim3(kRedThreads), 0, den, (const double*)gx,
                      (const double*)gy, (const double*)gz, npts, mask, gga_sel(c),
-                     (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nsum * c->dV) : 0.0, (int)c->params[OFDFT_P_VWGTF_KIND],
+                     ts.tc.gtf_inv_n0, ts.tc.gtf_kind,
                      c->d_partial, lapn);
         if (int rc = fetch_partials(c, blocks, kStressRealScalars, r, st)) return rc;
         if (int rc = global_sums(c, r, kStressRealScalars)) return rc;
@@ -314,7 +317,7 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         sym_store(sig + 9 * 3, s7, 0.0);
     }
     if (mask & OFDFT_WT_NL) {
-        const double al = c->params[OFDFT_P_WT_ALPHA], be = c->params[OFDFT_P_WT_BETA];
+        const double al = ts.nlp.al, be = ts.nlp.be;
         const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
         const double ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
         const double pref = ctf * 5.0 / (9.0 * al * be * std::pow(nbar, al + be - 5.0 / 3.0));
@@ -337,8 +340,8 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         sym_store(sig + 9 * 4, c6, -2.0 / 3.0 * pref * s7[6]);                                  // -2/3 T_NL / vol
     }
     if (mask & OFDFT_NLK) {          // KGAP / XWM (stress_kernels.h: stress_nlk_kernel); n0 = round(N_e) / vol
-        const NlPow nlp = nl_pow(c);
-        const double nel = nsum * c->dV, n0 = (double)std::llround(nel) / c->vol, x0 = c->params[OFDFT_P_NLK_P0];
+        const NlPow& nlp = ts.nlp;
+        const double n0 = ts.n0_r, x0 = c->params[OFDFT_P_NLK_P0];
         const double kf = std::cbrt(3.0 * kPi * kPi * n0), ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
         NlkStress t{};
         t.kind = nlp.kind;
@@ -383,9 +386,8 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
     }
     if (mask & OFDFT_WGC99_NL) {
         const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
-        const long long nel_r = std::llround(nsum * c->dV);                                      // functionals.py:952
         WgcSeries ser{};
-        if (int rc = wgc_series_setup(c, nel_r, st, &ser)) return rc;
+        if (int rc = wgc_series_setup(c, ts.nel_r, st, &ser)) return rc;
         if (ser.v == 0.0) return fail(c, OFDFT_EINVAL, "WGC99 stress: degenerate kernel parameters (v = 0) not supported");
         const char* wn[6] = {"zw0", "zw1", "zw2", "zw3", "zw4", "zw5"};
         WgcSpectra sp{};

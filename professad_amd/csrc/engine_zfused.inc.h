@@ -1,28 +1,6 @@
 // The z-fused pipeline of the engine (five stages, two chains; single- and multi-GPU) and the launchers of the z
 // kernels.  Included once by engine.hip inside its anonymous namespace (one translation unit).
 // ---------------------------------------------------------------------------------- z-fused pipeline (zpass.h)
-void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pbe_sums, double* E_terms, double* vn_int) {
-    const unsigned mask = c->mask;
-    const double dV = c->dV;
-    if (mask & OFDFT_ION_ELECTRON) E_terms[0] = sums[0] * dV;
-    if (mask & OFDFT_HARTREE) E_terms[1] = sums[1] * dV;
-    if (mask & OFDFT_TF) E_terms[2] = sums[2] * dV;
-    if (mask & OFDFT_VW) E_terms[3] = sums[3] * dV;
-    if (mask & OFDFT_WT_NL) E_terms[4] = sums[4] * dV;
-    if (mask & OFDFT_WGC99_NL) E_terms[5] = sums[5] * dV;
-    if (mask & OFDFT_LDA_X) E_terms[6] = sums[6] * dV;
-    int nc = 0;
-    for (int b = 7; b <= 9; ++b) nc += (mask >> b) & 1;
-    for (int b = 7; b <= 9; ++b)
-        if ((mask >> b) & 1) E_terms[b] = sums[7] * dV / nc;
-    if (mask & OFDFT_PBE_X) E_terms[10] = pbe_sums[0] * dV;
-    if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
-    if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
-    if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
-    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
-    *vn_int = sums[8] * dV;
-}
-
 // Pipeline with every real-space intermediate kept on chip: z kernels compute their inputs from chi|n on the
 // fly and consume the convolution results straight out of the inverse transform.  It is written as five
 // stages separated by the four points where the spectra change between the x-slab geometry (z, y passes) and
@@ -47,7 +25,7 @@ struct ZRun {
     cplx *s_n = nullptr, *s_s = nullptr, *s_vh = nullptr, *s_g[3] = {nullptr, nullptr, nullptr};
     cplx *s_b = nullptr, *s_a = nullptr, *sw[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     real* dfdn = nullptr;
-    double wt_pref = 0.0, wt_kf = 1.0;
+    TermScalars ts{};              // host scalars of the evaluation's terms (zsetup; the nonlocal chain's stage 1 adds the tables)
     // The evaluation is two independent chains that meet only in the combine kernel:
     //   chain 0: density spectrum -> Hartree, grad n -> PBE -> divergence;  sqrt(n) -> Laplacian (vW)
     //   chain 1: the nonlocal KEDF (Wang-Teter powers or the six WGC99 spectra)
@@ -121,8 +99,8 @@ int zsetup(ofdft_ctx* c) {
     r.za.v_out = r.v_out;
     r.za.mask = combine_mask(c);
     r.za.inv_n = 1.0 / (double)c->npts_g;
-    r.za.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
-    r.za.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(r.nel) : 0.0;   // functionals.py:268-270
+    r.ts = term_scalars(c, r.nel);
+    r.za.tc = r.ts.tc;
     r.pbe_sums[0] = r.pbe_sums[1] = r.pbe_sums[2] = 0.0;
     r.wgc_yinv_done = false;
     r.s_g[0] = r.s_g[1] = r.s_g[2] = nullptr;
@@ -187,15 +165,12 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             if (r.s_s) xl.push_back(r.s_s);
         }
     } else {
+        if ((rc = ensure_term_tables(c, r.ts, sb))) return rc;
+        r.za.tc.nref = r.ts.tc.nref;
         if (r.has_wt) {
-            const NlPow nlp = nl_pow(c);
-            const double al = nlp.al, be = nlp.be;
-            const double nbar = r.nel / c->vol;                                  // functionals.py:646-647
-            r.wt_kf = std::cbrt(3.0 * kPi * kPi * nbar);
-            r.wt_pref = 5.0 / (9.0 * al * be * std::pow(nbar, al + be - kFiveThirds));
-            if (nlp.nlk && (rc = ensure_nlk_table(c, r.nel, sb))) return rc;
+            const NlPow& nlp = r.ts.nlp;
             if ((rc = spec_ws(c, "zwb", &r.s_b))) return rc;
-            if (al != be && (rc = spec_ws(c, "zwa", &r.s_a))) return rc;
+            if (nlp.two && (rc = spec_ws(c, "zwa", &r.s_a))) return rc;
             PowersArgs pa{};
             pa.out[0] = r.s_b;
             pa.out[3] = r.s_a;
@@ -207,17 +182,9 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 if (!dx && (rc = fast_axis_pass<false>(c, 1, sp, sb))) return rc;
                 xl.push_back(sp);
             }
-            r.za.wt_alpha = al;
-            r.za.wt_beta = be;
-            r.za.wt_nbar_pa = nlp.nlk ? 0.0 : std::pow(nbar, al);     // (tabulated kernels: 0 at k = 0, nothing subtracted)
-            r.za.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
-            r.za.wt_sym = nlp.sym;
         }
         if (r.has_wgc) {
             const double al = c->params[OFDFT_P_WGC_ALPHA], be = c->params[OFDFT_P_WGC_BETA];
-            const long long nel_r = std::llround(r.nel);                         // functionals.py:952
-            double nref;
-            if ((rc = ensure_wgc_tables(c, nel_r, sb, &nref))) return rc;
             const char* wn[6] = {"zw0", "zw1", "zw2", "zw3", "zw4", "zw5"};
             PowersArgs pa{};
             for (int i = 0; i < 6; ++i) {
@@ -226,8 +193,8 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             }
             pa.e0 = be;
             pa.e1 = al;
-            pa.nref = nref;
-            pa.sum53 = (std::fabs(al + be - kFiveThirds) < 4e-16) ? 1 : 0;
+            pa.nref = r.ts.tc.nref;
+            pa.sum53 = r.ts.tc.wgc_sum_53;
             // x-chunked form: each chunk's six spectra (6 x C / nchunks) are y-transformed while still in the Infinity Cache
             const int nch = chunks_for(c, 6, 2);
             if (nch > 1) {
@@ -251,10 +218,6 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 if (!dx && nch == 1 && !c->ybatch && (rc = fast_axis_pass<false>(c, 1, r.sw[i], i < 3 ? sb : sc))) return rc;
                 xl.push_back(r.sw[i]);
             }
-            r.za.wgc_alpha = al;
-            r.za.wgc_beta = be;
-            r.za.nref = nref;
-            r.za.wgc_sum_53 = pa.sum53;
         }
     }
     }   // xk <= 0
@@ -345,7 +308,7 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         if (r.has_wt && (c->mask & OFDFT_NLK)) {
             // the same stage with the kernel from "t:nlk": XWM mixes its two spectra in one 2 -> 2 pass, the others scale each
             // spectrum by the one column
-            if (nl_pow(c).sym) {
+            if (r.ts.nlp.sym) {
                 XfIo io{};
                 io.in[0] = in_of(r.s_b);
                 io.in[1] = in_of(r.s_a);
@@ -362,7 +325,7 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 }
             }
         } else if (r.has_wt) {
-            const MixScale<SPEC_LINDHARD> lind{c->kg, (real)r.wt_pref, (real)(1.0 / (2.0 * r.wt_kf))};
+            const MixScale<SPEC_LINDHARD> lind{c->kg, (real)r.ts.wt_pref, (real)r.ts.wt_inv2kf};
             for (cplx* sp : {r.s_b, r.s_a}) {
                 if (!sp) continue;
                 XfIo io{};

@@ -1037,6 +1037,17 @@ static __global__ __launch_bounds__(kRedThreads) void pbe_kernel(const real* __r
 }
 
 // ---- final combine: potential + all energy integrands -------------------------------------------
+// Per-term constants of an evaluation as every combine kernel reads them (CombineArgs::tc, ZCombineArgs::tc, the persistent
+// kernel through its CombineArgs): derived once on the host by term_scalars (engine_ctx.h), which documents each value.
+struct TermConsts {
+    real wt_alpha, wt_beta, wt_nbar_pa;     // nbar^alpha
+    real wgc_alpha, wgc_beta, nref;
+    real gtf_inv_n0;   // vWGTF: 1 / n0, n0 = round(N_e) / vol (functionals.py:268-270)
+    int gtf_kind;        // 1 = vWGTF1, 2 = vWGTF2
+    int wt_is_56;        // alpha = beta = 5/6: n^(-1/6) = 1/sqrt(cbrt n), no pow
+    int wgc_sum_53;      // alpha + beta = 5/3: n^(alpha-1) = 1/(cbrt(n) n^(beta-1)), one pow instead of two
+    int wt_sym;          // OFDFT_NLK with a 2 x 2 kernel (XWM): conv_b / conv_a are the symmetric mix' outputs, E = (n^alpha conv_b + n^beta conv_a) / 2
+};
 struct CombineArgs {
     const real* n;
     const real* vext;
@@ -1051,14 +1062,8 @@ struct CombineArgs {
     real* v_out;
     long long npts;
     unsigned mask;
-    real wt_alpha, wt_beta, wt_nbar_pa;     // nbar^alpha
-    real wgc_alpha, wgc_beta, nref;
-    real gtf_inv_n0;   // vWGTF: 1 / n0, n0 = round(N_e) / vol (functionals.py:268-270)
-    int gtf_kind;        // 1 = vWGTF1, 2 = vWGTF2
-    int wt_is_56;        // alpha = beta = 5/6: n^(-1/6) = 1/sqrt(cbrt n), no pow
-    int wgc_sum_53;      // alpha + beta = 5/3: n^(alpha-1) = 1/(cbrt(n) n^(beta-1)), one pow instead of two
+    TermConsts tc;
     real w_tf = 1.0, w_nl = 1.0;   // weights of the TF / Wang-Teter potentials (stabilised WT-style functional, OFDFT_P_WTS_KIND)
-    int wt_sym = 0;      // OFDFT_NLK with a 2 x 2 kernel (XWM): conv_b / conv_a are the symmetric mix' outputs, E = (n^alpha conv_b + n^beta conv_a) / 2
 };
 // partial scalars: 0 ion-electron, 1 hartree, 2 tf, 3 vw, 4 wt-nl, 5 wgc-nl, 6 lda-x, 7 local-c, 8 sum(v*n), 9 vWGTF
 constexpr int kCombineScalars = 10;
@@ -1114,25 +1119,25 @@ __device__ __forceinline__ real combine_point(const CombineArgs& a, const Combin
         if (n != 0.0) v += -0.5 * p.lap / s;
     }
     if (a.mask & 16u) {                                 // WT-family NL  functionals.py:650-651; tools_for_tests.py:29-39
-        const real pa1 = a.wt_is_56 ? 1.0 / sqrt(n13) : pow(n, a.wt_alpha - 1.0);
-        const real ewt = ctf * (pa1 * n - a.wt_nbar_pa) * p.cb;
+        const real pa1 = a.tc.wt_is_56 ? 1.0 / sqrt(n13) : pow(n, a.tc.wt_alpha - 1.0);
+        const real ewt = ctf * (pa1 * n - a.tc.wt_nbar_pa) * p.cb;
         if (a.conv_a) {
-            const real pb1 = pow(n, a.wt_beta - 1.0);
-            acc[4] += a.wt_sym ? (real)0.5 * (ewt + ctf * pb1 * n * p.cva) : ewt;
-            v += a.w_nl * ctf * (a.wt_alpha * pa1 * p.cb + a.wt_beta * pb1 * p.cva);
+            const real pb1 = pow(n, a.tc.wt_beta - 1.0);
+            acc[4] += a.tc.wt_sym ? (real)0.5 * (ewt + ctf * pb1 * n * p.cva) : ewt;
+            v += a.w_nl * ctf * (a.tc.wt_alpha * pa1 * p.cb + a.tc.wt_beta * pb1 * p.cva);
         } else {
             acc[4] += ewt;
-            v += a.w_nl * ctf * 2.0 * a.wt_alpha * pa1 * p.cb;
+            v += a.w_nl * ctf * 2.0 * a.tc.wt_alpha * pa1 * p.cb;
         }
     }
     if (a.mask & 32u) {                                 // WGC99 NL  SURVEY §8a-8
-        const real th = n - a.nref;
-        const real pb1 = pow(n, a.wgc_beta - 1.0);
-        const real pa1 = a.wgc_sum_53 ? 1.0 / (n13 * pb1) : pow(n, a.wgc_alpha - 1.0);
-        const real P = pa1 * n, A = pb1 * n, dA = a.wgc_beta * pb1;
+        const real th = n - a.tc.nref;
+        const real pb1 = pow(n, a.tc.wgc_beta - 1.0);
+        const real pa1 = a.tc.wgc_sum_53 ? 1.0 / (n13 * pb1) : pow(n, a.tc.wgc_alpha - 1.0);
+        const real P = pa1 * n, A = pb1 * n, dA = a.tc.wgc_beta * pb1;
         const real conv = p.u0 + th * p.u1 + 0.5 * th * th * p.u2;
         acc[5] += ctf * P * conv;
-        v += ctf * (a.wgc_alpha * pa1 * conv + P * (p.u1 + th * p.u2) + p.gA * dA + p.gB * (dA * th + A)
+        v += ctf * (a.tc.wgc_alpha * pa1 * conv + P * (p.u1 + th * p.u2) + p.gA * dA + p.gB * (dA * th + A)
                     + p.gC * (0.5 * dA * th * th + A * th));
     }
     if (a.mask & (0xFu << 6)) {                         // local XC
@@ -1144,7 +1149,7 @@ __device__ __forceinline__ real combine_point(const CombineArgs& a, const Combin
     if (a.mask & (7u << 10)) v += p.dfdn - 2.0 * p.div;   // PBE / GGA kinetic  tools_for_tests.py:168-170
     if (a.mask & (1u << 13)) {                          // vWGTF1 / 2  functionals.py:251-306
         real e, ve;
-        vwgtf_point(n, n13, ctf, a.gtf_inv_n0, a.gtf_kind, e, ve);
+        vwgtf_point(n, n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e, ve);
         acc[9] += e;
         v += ve;
     }

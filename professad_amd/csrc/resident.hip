@@ -238,7 +238,7 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
         for (int i = tid; i < N; i += T) twN[i] = twN_g[i];
     };
     stage_tables();
-    const real be = A.ca.wt_beta, al = A.ca.wt_alpha;
+    const real be = A.ca.tc.wt_beta, al = A.ca.tc.wt_alpha;
     const int x = bid;                                    // phases A, C, D: this workgroup's x plane
     const cplx* chi_pl = reinterpret_cast<const cplx*>(A.chi + (long long)x * N * N);
 
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
             cscale = A.from_den ? (acc_t)1.0 : A.nel / (tot[kCombineScalars] * A.vol_over_npts);       // system.py:833-834
             have_c = true;
         }
-        const real cs0 = (real)cscale, wal = A.ca.wgc_alpha, wbe = A.ca.wgc_beta, nref = A.ca.nref;
+        const real cs0 = (real)cscale, wal = A.ca.tc.wgc_alpha, wbe = A.ca.tc.wgc_beta, nref = A.ca.tc.nref;
         for (int g0 = 0; g0 < A.narr; g0 += AG) {
             const int ns = (A.narr - g0) < AG ? (A.narr - g0) : AG;
             rows_forward(ns, [&](int sI, int y, int e) {
@@ -726,7 +726,8 @@ int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel
         c->res_epoch = 0;
     }
     const bool gga = mask & kGgaAny, har = mask & OFDFT_HARTREE, vw = mask & OFDFT_VW, wt = mask & OFDFT_WT_NL;
-    const double al = c->params[OFDFT_P_WT_ALPHA], be = c->params[OFDFT_P_WT_BETA];
+    TermScalars ts = term_scalars(c, nel);
+    if (int rc = ensure_term_tables(c, ts, st)) return rc;
     a.done = c->res_done;
     a.reduced = c->h_partial;          // pinned, device-visible: no copy command behind the kernel
     a.sync = c->res_sync;
@@ -738,7 +739,7 @@ int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel
     a.act[0] = (har || gga) ? 1 : 0;
     a.act[1] = vw ? 1 : 0;
     a.act[2] = wt ? 1 : 0;
-    a.act[3] = (wt && al != be) ? 1 : 0;
+    a.act[3] = (wt && ts.nlp.two) ? 1 : 0;
     const bool wgc = mask & OFDFT_WGC99_NL;
     for (int k = 0; k < 4; ++k)
         if (a.act[k]) {
@@ -767,34 +768,20 @@ int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel
         for (int j = 0; j < 3; ++j) op(0, 4 + j, 3 + j);
     if (wgc) {
         for (int k = 0; k < 6; ++k) a.outs[a.nout++] = 9 + k;
-        const double wal = c->params[OFDFT_P_WGC_ALPHA], wbe = c->params[OFDFT_P_WGC_BETA];
-        double nref;
-        if (int rc = ensure_wgc_tables(c, std::llround(nel), st, &nref)) return rc;     // functionals.py:952 (rounded N_e)
         a.wtab = wgc_tab(c);
         a.wg = c->g;
-        a.ca.wgc_alpha = wal;
-        a.ca.wgc_beta = wbe;
-        a.ca.nref = nref;
-        a.ca.wgc_sum_53 = (std::fabs(wal + wbe - kFiveThirds) < 4e-16) ? 1 : 0;
     }
     a.sel = gga_sel(c);
     a.kg = c->kg;
     CombineArgs& ca = a.ca;
     ca.mask = mask;
     ca.npts = c->npts;
-    ca.gtf_kind = (int)c->params[OFDFT_P_VWGTF_KIND];
-    ca.gtf_inv_n0 = (mask & OFDFT_VWGTF) ? c->vol / (double)std::llround(nel) : 0.0;           // functionals.py:268-270
+    ca.tc = ts.tc;
     ca.conv_a = nullptr;
     if (wt) {
-        const double nbar = nel / c->vol;                                                      // functionals.py:646-647
-        const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
-        a.lind_p0 = 5.0 / (9.0 * al * be * std::pow(nbar, al + be - kFiveThirds));
-        a.lind_p1 = 1.0 / (2.0 * kf);
-        ca.wt_alpha = al;
-        ca.wt_beta = be;
-        ca.wt_nbar_pa = std::pow(nbar, al);
-        ca.wt_is_56 = (al == kFiveSixths && be == kFiveSixths) ? 1 : 0;
-        if (al != be) ca.conv_a = chi;      // any non-null pointer: combine_point only asks whether the second convolution exists
+        a.lind_p0 = ts.wt_pref;
+        a.lind_p1 = ts.wt_inv2kf;
+        if (ts.nlp.two) ca.conv_a = chi;    // any non-null pointer: combine_point only asks whether the second convolution exists
     }
     a.nel = nel;
     a.vol_over_npts = c->vol / (double)c->npts;

@@ -764,13 +764,8 @@ struct ZCombineArgs {
                             // its share of sum(v n) arrives through zi_wgc's second sum)
     unsigned mask;
     real inv_n;
-    real wt_alpha, wt_beta, wt_nbar_pa;
-    real wgc_alpha, wgc_beta, nref;
-    real gtf_inv_n0;
-    int gtf_kind;
-    int wt_is_56, wgc_sum_53;
+    TermConsts tc;          // per-term constants (pointwise_kernels.h; term_scalars, engine_ctx.h)
     const acc_t* wts_w;     // device weights (w_tf, w_nl) of the stabilised WT-style functional, or null
-    int wt_sym;             // OFDFT_NLK with a 2 x 2 kernel: E = (n^alpha conv_b + n^beta conv_a) / 2 (CombineArgs::wt_sym)
 };
 
 // WGC99 nonlocal part of one row (SURVEY §8a-8 closed form): adds the potential to vacc, returns the thread's energy sum
@@ -802,8 +797,8 @@ __device__ __forceinline__ real wgc_row_section(const cplx (&n)[E], cplx (&vacc)
 #pragma unroll
     for (int q = 0; q < E; ++q) {
         const real x0 = w[q].x * sc, x1 = w[q].y * sc;
-        t1[q].x += (n[q].x - a.nref) * x0;
-        t1[q].y += (n[q].y - a.nref) * x1;
+        t1[q].x += (n[q].x - a.tc.nref) * x0;
+        t1[q].y += (n[q].y - a.tc.nref) * x1;
         t2[q] = mkc(x0, x1);                                                            // S_1 = u1 + ...
     }
     OFDFT_ZROW(a.u[2], a.gw[0])
@@ -811,7 +806,7 @@ __device__ __forceinline__ real wgc_row_section(const cplx (&n)[E], cplx (&vacc)
     for (int q = 0; q < E; ++q) {
         __builtin_amdgcn_sched_barrier(0);      // one point pair at a time: pow_pos() is register-hungry
         const real x0 = w[q].x * sc, x1 = w[q].y * sc;
-        const real h0 = n[q].x - a.nref, h1 = n[q].y - a.nref;
+        const real h0 = n[q].x - a.tc.nref, h1 = n[q].y - a.tc.nref;
         t1[q].x += 0.5 * h0 * h0 * x0;
         t1[q].y += 0.5 * h1 * h1 * x1;
         t2[q].x += h0 * x0;
@@ -819,28 +814,28 @@ __device__ __forceinline__ real wgc_row_section(const cplx (&n)[E], cplx (&vacc)
         // fold: e_NL = ctf n^alpha S_e ; v += ctf n^(alpha-1) (alpha S_e + n S_1); keep n^(beta-1) in t2
         // n^(beta-1) and n^(alpha-1) from ONE logarithm per point
         const real l0 = fm::log(n[q].x), l1 = fm::log(n[q].y);
-        const real pb0 = fm::exp((a.wgc_beta - 1.0) * l0), pb1 = fm::exp((a.wgc_beta - 1.0) * l1);
-        const real pa0 = fm::exp((a.wgc_alpha - 1.0) * l0), pa1 = fm::exp((a.wgc_alpha - 1.0) * l1);
+        const real pb0 = fm::exp((a.tc.wgc_beta - 1.0) * l0), pb1 = fm::exp((a.tc.wgc_beta - 1.0) * l1);
+        const real pa0 = fm::exp((a.tc.wgc_alpha - 1.0) * l0), pa1 = fm::exp((a.tc.wgc_alpha - 1.0) * l1);
         e += ctf * (pa0 * n[q].x * t1[q].x + pa1 * n[q].y * t1[q].y);
-        vacc[q].x += ctf * pa0 * (a.wgc_alpha * t1[q].x + n[q].x * t2[q].x);
-        vacc[q].y += ctf * pa1 * (a.wgc_alpha * t1[q].y + n[q].y * t2[q].y);
+        vacc[q].x += ctf * pa0 * (a.tc.wgc_alpha * t1[q].x + n[q].x * t2[q].x);
+        vacc[q].y += ctf * pa1 * (a.tc.wgc_alpha * t1[q].y + n[q].y * t2[q].y);
         t2[q] = mkc(pb0, pb1);
     }
     OFDFT_ZROW(a.gw[0], a.gw[1])
 #pragma unroll
-    for (int q = 0; q < E; ++q) t1[q] = mkc(a.wgc_beta * w[q].x * sc, a.wgc_beta * w[q].y * sc);
+    for (int q = 0; q < E; ++q) t1[q] = mkc(a.tc.wgc_beta * w[q].x * sc, a.tc.wgc_beta * w[q].y * sc);
     OFDFT_ZROW(a.gw[1], a.gw[2])
 #pragma unroll
     for (int q = 0; q < E; ++q) {
-        t1[q].x += (a.wgc_beta * (n[q].x - a.nref) + n[q].x) * w[q].x * sc;
-        t1[q].y += (a.wgc_beta * (n[q].y - a.nref) + n[q].y) * w[q].y * sc;
+        t1[q].x += (a.tc.wgc_beta * (n[q].x - a.tc.nref) + n[q].x) * w[q].x * sc;
+        t1[q].y += (a.tc.wgc_beta * (n[q].y - a.tc.nref) + n[q].y) * w[q].y * sc;
     }
     OFDFT_ZROW(a.gw[2], nullptr)
 #pragma unroll
     for (int q = 0; q < E; ++q) {
-        const real h0 = n[q].x - a.nref, h1 = n[q].y - a.nref;
-        t1[q].x += (0.5 * a.wgc_beta * h0 * h0 + n[q].x * h0) * w[q].x * sc;
-        t1[q].y += (0.5 * a.wgc_beta * h1 * h1 + n[q].y * h1) * w[q].y * sc;
+        const real h0 = n[q].x - a.tc.nref, h1 = n[q].y - a.tc.nref;
+        t1[q].x += (0.5 * a.tc.wgc_beta * h0 * h0 + n[q].x * h0) * w[q].x * sc;
+        t1[q].y += (0.5 * a.tc.wgc_beta * h1 * h1 + n[q].y * h1) * w[q].y * sc;
         vacc[q].x += ctf * t2[q].x * t1[q].x;
         vacc[q].y += ctf * t2[q].y * t1[q].y;
     }
@@ -981,30 +976,30 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         for (int q = 0; q < E; ++q) {
             __builtin_amdgcn_sched_barrier(0);
             const real x0 = w[q].x * sc, x1 = w[q].y * sc;
-            pa1[q] = a.wt_is_56 ? mkc(root_y(q, 0), root_y(q, 1)) : mkc(pow_pos(n[q].x, a.wt_alpha - 1.0), pow_pos(n[q].y, a.wt_alpha - 1.0));
-            e += ctf * ((pa1[q].x * n[q].x - a.wt_nbar_pa) * x0 + (pa1[q].y * n[q].y - a.wt_nbar_pa) * x1);
-            const real f = w_nl * (a.conv_a ? a.wt_alpha : 2.0 * a.wt_alpha);
+            pa1[q] = a.tc.wt_is_56 ? mkc(root_y(q, 0), root_y(q, 1)) : mkc(pow_pos(n[q].x, a.tc.wt_alpha - 1.0), pow_pos(n[q].y, a.tc.wt_alpha - 1.0));
+            e += ctf * ((pa1[q].x * n[q].x - a.tc.wt_nbar_pa) * x0 + (pa1[q].y * n[q].y - a.tc.wt_nbar_pa) * x1);
+            const real f = w_nl * (a.conv_a ? a.tc.wt_alpha : 2.0 * a.tc.wt_alpha);
             vacc[q].x += ctf * f * pa1[q].x * x0;
             vacc[q].y += ctf * f * pa1[q].y * x1;
         }
         park[kParkWt * 256] = e;
         if (a.conv_a) {
             take_row(std::integral_constant<int, 3>{}, a.conv_a);
-            if (a.wt_sym) {                              // (its own loop: the Wang-Teter family's stays as it was)
+            if (a.tc.wt_sym) {                              // (its own loop: the Wang-Teter family's stays as it was)
                 real e2 = 0.0;
 #pragma unroll
                 for (int q = 0; q < E; ++q) {
-                    const real p0 = ctf * pow_pos(n[q].x, a.wt_beta - 1.0) * w[q].x * sc, p1 = ctf * pow_pos(n[q].y, a.wt_beta - 1.0) * w[q].y * sc;
+                    const real p0 = ctf * pow_pos(n[q].x, a.tc.wt_beta - 1.0) * w[q].x * sc, p1 = ctf * pow_pos(n[q].y, a.tc.wt_beta - 1.0) * w[q].y * sc;
                     e2 += p0 * n[q].x + p1 * n[q].y;
-                    vacc[q].x += w_nl * a.wt_beta * p0;
-                    vacc[q].y += w_nl * a.wt_beta * p1;
+                    vacc[q].x += w_nl * a.tc.wt_beta * p0;
+                    vacc[q].y += w_nl * a.tc.wt_beta * p1;
                 }
                 park[kParkWt * 256] = (real)0.5 * (park[kParkWt * 256] + e2);
             } else {
 #pragma unroll
                 for (int q = 0; q < E; ++q) {
-                    vacc[q].x += w_nl * ctf * a.wt_beta * pow_pos(n[q].x, a.wt_beta - 1.0) * w[q].x * sc;
-                    vacc[q].y += w_nl * ctf * a.wt_beta * pow_pos(n[q].y, a.wt_beta - 1.0) * w[q].y * sc;
+                    vacc[q].x += w_nl * ctf * a.tc.wt_beta * pow_pos(n[q].x, a.tc.wt_beta - 1.0) * w[q].x * sc;
+                    vacc[q].y += w_nl * ctf * a.tc.wt_beta * pow_pos(n[q].y, a.tc.wt_beta - 1.0) * w[q].y * sc;
                 }
             }
         }
@@ -1069,8 +1064,8 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
         if (a.mask & (1u << 13)) {                       // vWGTF1 / 2  functionals.py:251-306
             real e0, v0, e1, v1;
-            vwgtf_point(n[q].x, rt0.n13, ctf, a.gtf_inv_n0, a.gtf_kind, e0, v0);
-            vwgtf_point(n[q].y, rt1.n13, ctf, a.gtf_inv_n0, a.gtf_kind, e1, v1);
+            vwgtf_point(n[q].x, rt0.n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e0, v0);
+            vwgtf_point(n[q].y, rt1.n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e1, v1);
             acc[9] += e0 + e1;
             vacc[q].x += v0;
             vacc[q].y += v1;
