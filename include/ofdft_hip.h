@@ -361,7 +361,16 @@ int  ofdft_lbfgs_update(ofdft_lbfgs* h, const double* coef_s, const double* coef
                                      y-inverse of that spectrum are one y pass -- the combine kernel reads one spectrum where it read three.
                                      0: the Hartree spectrum and the two divergence parts travel separately (slabs, chirp-z path and the persistent
                                      small-grid kernel always do) */
-#define OFDFT_OPT_WGC_FOLD 28     /* 1 (default): on cells with orthogonal axes the cross-wave x pass reads the WGC99 table entry of x > n0 / 2 at
+#define OFDFT_OPT_AXIS_PASSES 17  /* one GPU, z-fused pipeline: operators of one axis run as passes of that axis.  Bits (default 3):
+                                     1 = split-derivative GGA: D_a n = i f_a n^ comes from an x pass on the z spectrum BEFORE its y-forward (the
+                                         multiply does not depend on y), so it makes no y round trip: one y pass less on every cell;
+                                     2 = cells with orthogonal axes, von Weizsaecker term: -k^2 = -(k_a^2 + k_c^2) - k_b^2, so the Laplacian of
+                                         sqrt(n) is an x pass on the z spectrum plus ONE y pass that multiplies by -k_b^2 between its transforms
+                                         and adds the x pass' result: two y passes and one launch less, one more spectrum of workspace.  fp64 library
+                                         only: the fp32 library accepts the bit and keeps the three passes, which measured faster there.
+                                     0: the sequence without either (slabs, chirp-z path, the persistent small-grid kernel and the unsplit GGA form
+                                     always run that one) */
+#define OFDFT_OPT_WGC_FOLD 28    /* 1 (default): on cells with orthogonal axes the cross-wave x pass reads the WGC99 table entry of x > n0 / 2 at
                                      n0 - x (|k| is even along a line there; functionals.py:968-972 depends on |k| only): both uses of an entry
                                      fall into one tile, the second is a cache hit, the pass' table traffic halves.  0: every k-point its own entry */
 #define OFDFT_OPT_XWAVE 8         /* fused x passes: 1 (default) = the cross-wave kernel (whole runs of memory-adjacent lines per access, the

@@ -52,6 +52,8 @@ OPT_XCHG_CHUNKS = 12
 OPT_IPC_WAIT_MS = 13
 OPT_YBATCH = 14
 OPT_BS_FUSED = 15
+OPT_POT_SPECTRUM = 16
+OPT_AXIS_PASSES = 17
 OPT_WGC_FOLD = 28
 
 EXPORTS = ['ofdft_create', 'ofdft_destroy', 'ofdft_last_error', 'ofdft_set_cell', 'ofdft_set_terms',

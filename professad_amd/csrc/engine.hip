@@ -1744,6 +1744,10 @@ int ofdft_set_option(ofdft_ctx* c, int option, double value) {
         case OFDFT_OPT_POT_SPECTRUM:
             c->pot_spectrum = value != 0.0;
             return OFDFT_OK;
+        case OFDFT_OPT_AXIS_PASSES:
+            if (value != 0.0 && value != 1.0 && value != 2.0 && value != 3.0) return fail(c, OFDFT_EINVAL, "OFDFT_OPT_AXIS_PASSES takes 0..3");
+            c->axis_passes = (int)value;
+            return OFDFT_OK;
         case OFDFT_OPT_SPLIT_COMBINE:
             c->split_combine = value != 0.0;
             c->defer_vpart = value != 1.0;

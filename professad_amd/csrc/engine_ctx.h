@@ -97,6 +97,8 @@ struct ofdft_ctx {
     bool use_bluestein = true;   // non power-of-two extents <= 512: chirp-z line transforms (else the plain O(N^2) DFT kernels)
     bool gga_split = true;       // GGA chain in split-derivative form: only the x index-derivative visits the x pass
     bool pot_spectrum = true;    // OFDFT_OPT_POT_SPECTRUM: Hartree potential folded into the divergence spectrum (one GPU, split GGA)
+    int axis_passes = 3;         // OFDFT_OPT_AXIS_PASSES (one GPU, z-fused pipeline): bit 1 = D_a n from an x pass on the z spectrum (split GGA),
+                                 // bit 2 = the von Weizsaecker Laplacian as one x pass + one y pass on cells with orthogonal axes
     bool split_combine = true;   // WGC99 part of the combine as its own kernel on the nonlocal chain's stream (forked runs)
     bool defer_vpart = true;     // ... and, in closure evaluations, merged into the potential by chi_grad (the combine kernel does not wait for it)
     int ybatch = 1;         // OFDFT_OPT_YBATCH: the y passes of the three spectra of a WGC99 half as ONE launch (grid.y = 3).  A 256^3 y pass is
@@ -402,6 +404,12 @@ inline void xchg_chunks_set(ofdft_ctx* c, int req) {
     for (int k = 0; k <= c->xc.n; ++k) c->xc.kb[k] = (int)((long long)c->xg.nb * k / c->xc.n);
 }
 
+// the reciprocal axes lie along the Cartesian ones (what the folded WGC99 table reads and the split Laplacian rest on)
+inline bool cell_axes_orthogonal(const ofdft_ctx* c) {
+    const real* bb = c->kg.b;
+    return bb[1] == 0.0 && bb[2] == 0.0 && bb[3] == 0.0 && bb[5] == 0.0 && bb[6] == 0.0 && bb[7] == 0.0;
+}
+
 // ---- workspaces and tables (engine.hip)
 int get_twiddle(ofdft_ctx* c, int n, cplx** out);
 int get_ws(ofdft_ctx* c, const std::string& name, size_t bytes, void** out);
@@ -425,6 +433,8 @@ template <bool INV> int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list,
 int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd = nullptr);
 // out = y-inverse of (i f_b scale y-forward(in) + add), add a y-forwarded spectrum of the same layout (add == out: in place)
 int yderiv_add(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st);
+// out = y-inverse of (scale f_b^2 y-forward(in)) + add, add in the layout of `out` (not y-forwarded); in == out: in place
+int ylap(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st);
 int rfftn_internal(ofdft_ctx* c, const real* in, cplx* spec, hipStream_t st);
 int rfftn_internal_multi(ofdft_ctx* c, const real* const* in, cplx* const* spec, int n, hipStream_t st);
 // chirp-z path with the fused x pass (lines.hip): z + y passes | forward-x, mix, inverse-x | y + z passes

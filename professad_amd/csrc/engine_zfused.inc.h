@@ -14,6 +14,10 @@
 // Potential-spectrum form (one GPU, split-derivative GGA with Hartree; OFDFT_OPT_POT_SPECTRUM): stage 2 forms i f_a n^ only, stage 4
 // reads n^ beside G_a^ and returns i f_a G_a^ - v_H^ / 2 (+ E_H by Parseval), stage 5 adds D_b G_b inside the y-inverse of that
 // spectrum -- the combine kernel reads one spectrum for Hartree + divergence where it read three (v_H, D_a part, D_b part).
+// One-axis operators as one-axis passes (one GPU; OFDFT_OPT_AXIS_PASSES): i f_a n^ depends on x only, so stage 1 forms D_a n by an x pass
+// on the z spectrum BEFORE its y-forward (no y round trip: stage 2 does not produce it, stage 3 does not y-invert it); on cells with
+// orthogonal axes -k^2 = -(k_a^2 + k_c^2) - k_b^2, so the von Weizsaecker Laplacian is an x pass on the z spectrum plus one y pass that
+// multiplies by -k_b^2 between its two transforms and adds the x pass' result (stage 2; two passes where there were three).
 struct ZRun {
     DenSrc ds{};
     double nel = 0.0;
@@ -36,6 +40,9 @@ struct ZRun {
     // potential-spectrum form (OFDFT_OPT_POT_SPECTRUM; one GPU, split GGA + Hartree): v_H^ rides in the divergence x pass (which reads
     // n^ again and forms E_H by Parseval), D_b G_b + the y-inverse of that spectrum are one y pass, the combine reads one spectrum
     bool pspec = false;
+    bool da_early = false;         // OFDFT_OPT_AXIS_PASSES bit 1: stage 1 formed D_a n from the z spectrum (s_g[0] is final, not an x-pass result)
+    bool lap_split = false;        // ... bit 2: the Laplacian of sqrt(n) is x pass + ylap in stage 2 (s_s is never y-forwarded)
+    cplx* s_sx = nullptr;          // ... the x pass' result, added by ylap
     cplx* s_l = nullptr;
     real* dzn = nullptr;
     bool wgc_yinv_done = false;    // kz-chunked form: the y-inverse of the WGC99 results already ran next to the x pass
@@ -106,6 +113,8 @@ int zsetup(ofdft_ctx* c) {
     r.s_g[0] = r.s_g[1] = r.s_g[2] = nullptr;
     r.s_n = r.s_s = r.s_vh = r.s_b = r.s_a = nullptr;
     r.pspec = false;
+    r.da_early = r.lap_split = false;
+    r.s_sx = nullptr;
     if ((mask & OFDFT_ION_ELECTRON) && !r.vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
     r.setup_done = true;
     return 0;
@@ -143,6 +152,13 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 if (r.lapl && (rc = spec_ws(c, "zgl", &r.s_l))) return rc;
             }
             const int nch = r.gsplit ? 1 : chunks_for(c, nb, 1);
+            r.da_early = r.gsplit && !dx && (c->axis_passes & 1);
+            // (not where the y passes of the results run inside the x-chunked combine loop: the Laplacian would leave that loop)
+            // fp64 build only: in the fp32 build the two-pass Laplacian measured 1.0 % SLOWER per evaluation than the three-pass one in
+            // every alternation (256^3, profiles/r07_ab_axis_passes.jsonl) -- bit 2 is accepted there and changes nothing
+            r.lap_split = sizeof(real) == 8 && r.s_s && !dx && nch == 1 && (c->axis_passes & 2) && cell_axes_orthogonal(c) &&
+                          chunks_for(c, 6, 8) == 1;
+            if (r.lap_split && (rc = spec_ws(c, "zsx", &r.s_sx))) return rc;
             if (nch > 1) {        // x-chunked: a chunk's spectra are y-transformed while still in the Infinity Cache
                 for (int ch = 0; ch < nch; ++ch) {
                     if ((rc = launch_zf_density(c, r.ds, r.s_n, r.s_s, st, ch, nch))) return rc;
@@ -150,6 +166,14 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 }
             } else if ((rc = launch_zf_density(c, r.ds, r.s_n, r.s_s, st, 0, 1, r.gsplit ? r.dzn : nullptr))) {
                 return rc;
+            }
+            // D_a n from the same spectrum: the multiply by i f_a commutes with the y transforms, so the x pass runs before the y-forward
+            // and its result needs no y-inverse (same stream, before yderiv overwrites s_n: no event)
+            if (r.da_early) {
+                XfIo io{};
+                io.in[0] = r.s_n;
+                io.out[0] = r.s_g[0];
+                if ((rc = xfused<1, 1>(c, io, MixDerivAS{c->n0g, (real)c->n1}, st, "xfused_n"))) return rc;
             }
             // D_b n from the (kz; y, x) spectrum before its in-place y-forward; scaled so that the consumer's 1/N fits
             // (one GPU: the y-forward of n^ rides in the same pass -- both read the same array; OFDFT_YDERIV_FWD=0: two passes)
@@ -160,7 +184,7 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 HIP_TRY(c, hipStreamWaitEvent(sc, c->ev_a, 0));
             }
             if (!dx && nch == 1 && r.s_n && !yfwd && (rc = fast_axis_pass<false>(c, 1, r.s_n, st))) return rc;
-            if (!dx && nch == 1 && r.s_s && (rc = fast_axis_pass<false>(c, 1, r.s_s, sc))) return rc;
+            if (!dx && nch == 1 && r.s_s && !r.lap_split && (rc = fast_axis_pass<false>(c, 1, r.s_s, sc))) return rc;
             if (r.s_n) xl.push_back(r.s_n);
             if (r.s_s) xl.push_back(r.s_s);
         }
@@ -280,7 +304,7 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 io.out[no++] = out_of(r.s_vh);
             }
             if (r.has_g && r.gsplit) {
-                io.out[no++] = out_of(r.s_g[0]);          // (D_a n)^ only
+                if (!r.da_early) io.out[no++] = out_of(r.s_g[0]);     // (D_a n)^ only
                 if (r.lapl) io.out[no++] = out_of(r.s_l); // -k^2 n^
             } else if (r.has_g) {
                 const char* gn[3] = {"zgx", "zgy", "zgz"};
@@ -289,7 +313,13 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                     io.out[no++] = out_of(r.s_g[k]);
                 }
             }
-            if (r.lapl && vh) rc = xfused<1, 3>(c, io, MixDensityA<true, true>{c->kg}, st, "xfused_n", lay);
+            if (r.da_early) {         // what is left beside D_a n: [v_H^] [, -k^2 n^] -- nothing in the potential-spectrum form without the latter
+                if (r.lapl && vh) rc = xfused<1, 2>(c, io, MixDensityA<true, true, false>{c->kg}, st, "xfused_n", lay);
+                else if (r.lapl) rc = xfused<1, 1>(c, io, MixScale<SPEC_LAPLACE>{c->kg, 0.0, 0.0}, st, "xfused_n", lay);
+                else if (vh) rc = xfused<1, 1>(c, io, MixDensity<true, false>{c->kg}, st, "xfused_n", lay);
+                else rc = 0;
+            }
+            else if (r.lapl && vh) rc = xfused<1, 3>(c, io, MixDensityA<true, true>{c->kg}, st, "xfused_n", lay);
             else if (r.lapl) rc = xfused<1, 2>(c, io, MixDensityA<false, true>{c->kg}, st, "xfused_n", lay);
             else if (r.gsplit && vh) rc = xfused<1, 2>(c, io, MixDensityA<true>{c->kg}, st, "xfused_n", lay);
             else if (r.gsplit) rc = xfused<1, 1>(c, io, MixDensityA<false>{c->kg}, st, "xfused_n", lay);
@@ -298,7 +328,18 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             else rc = xfused<1, 3>(c, io, MixDensity<false, true>{c->kg}, st, "xfused_n", lay);
             if (rc) return rc;
         }
-        if (r.s_s) {
+        if (r.s_s && r.lap_split) {
+            // -(k_a^2 + k_c^2) s^ by an x pass on the z spectrum, then inv_y(-k_b^2 fwd_y(s^)) + that in one y pass: s_s is final
+            // (each pass carries the other axis' transform length, as the unnormalised round trips of the three-pass route do)
+            XfIo io{};
+            io.in[0] = r.s_s;
+            io.out[0] = r.s_sx;
+            const real* bb = c->kg.b;
+            const double kb2 = (double)bb[3] * bb[3] + (double)bb[4] * bb[4] + (double)bb[5] * bb[5];
+            if ((rc = xfused<1, 1>(c, io, MixScale<SPEC_LAPLACE_AC>{c->kg, (real)c->n1, 0.0}, sc, "xfused_lap"))) return rc;
+            if ((rc = ylap(c, r.s_s, r.s_sx, r.s_s, -kb2 * (double)c->n0g, sc))) return rc;
+            c->fft_count++;
+        } else if (r.s_s) {
             XfIo io{};
             io.in[0] = in_of(r.s_s);
             io.out[0] = out_of(r.s_s);
@@ -451,7 +492,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
     if (r.has_h && !r.pspec) r.za.vh = r.s_vh;
     if (r.s_s) r.za.lap = r.s_s;
     if (r.has_g && r.gsplit) {
-        // split-derivative form: A = (D_a n) came back from the x pass and was y-inverted above, B = (D_b n) is local
+        // split-derivative form: A = (D_a n) came back from the x pass and was y-inverted above (or was formed in stage 1), B = (D_b n) is local
         if ((rc = real_ws(c, "dfdn", &r.dfdn))) return rc;
         if ((rc = launch_zpbe2(c, r.ds, r.s_g[0], r.s_g[1], r.dzn, r.dfdn, r.za.inv_n, &r.pbe_blocks, st, r.lapl ? r.s_l : nullptr)))
             return rc;

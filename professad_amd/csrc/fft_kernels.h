@@ -211,7 +211,10 @@ __device__ __forceinline__ void repattern_out_to_in(cplx (&v)[PL::E], int j, rea
 // ADD: `add` is a y-forwarded spectrum of the same layout whose line is added (in the forward transform's output order) before
 // the inverse: D_b G_b and the y-inverse of the x pass' result of the divergence in one pass, 2 spectra in and 1 out (add == out:
 // in place -- the line's loads precede the transforms' barriers, as for fwd).
-template <int LEN, bool ADD = false>
+// LAP: the factor is real, scale f_b^2 (scale carries -|b_b|^2: the y part of -k^2 on a cell whose axis b is orthogonal to the other
+// two), and `add` -- loaded at the same positions -- is NOT y-forwarded: it joins after the inverse.  With add = the x pass of the
+// (kz; y, x) spectrum with -(k_a^2 + k_c^2) this is the whole Laplacian in two passes (profiled as ylap).
+template <int LEN, bool ADD = false, bool LAP = false>
 __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* in, cplx* out,
                                                                    LineMap m_main, LineMap m_rem, int main_blocks,
                                                                    long long rem_offset, const cplx* __restrict__ tw,
@@ -237,8 +240,8 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* i
 #pragma unroll
     for (int q = 0; q < E; ++q)
         v[q] = (PL::slot_in(q) && valid && PL::lane_in(j, q)) ? buf_load_c(in + roff + b0 + PL::cin(q) * se_u, voff) : mkc(0.0, 0.0);
-    cplx x[ADD ? E : 1];
-    if constexpr (ADD) {
+    cplx x[(ADD || LAP) ? E : 1];
+    if constexpr (ADD || LAP) {
 #pragma unroll
         for (int q = 0; q < E; ++q)
             x[q] = (PL::slot_out(q) && valid && PL::lane_out(j, q)) ? buf_load_c(add + roff + b0 + PL::cout(q) * se_u, voff) : mkc(0.0, 0.0);
@@ -253,8 +256,14 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* i
 #pragma unroll
     for (int q = 0; q < E; ++q) {
         const int e = j + PL::cout(q);
-        const real f = scale * (real)(e <= LEN / 2 ? e : e - LEN);
-        v[q] = mkc(-f * v[q].y, f * v[q].x);
+        const real fe = (real)(e <= LEN / 2 ? e : e - LEN);
+        if constexpr (LAP) {
+            const real f = scale * fe * fe;
+            v[q] = mkc(f * v[q].x, f * v[q].y);
+        } else {
+            const real f = scale * fe;
+            v[q] = mkc(-f * v[q].y, f * v[q].x);
+        }
         if constexpr (ADD) v[q] = cadd(v[q], x[q]);
     }
     __syncthreads();
@@ -263,7 +272,10 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void yderiv_kernel(const cplx* i
     if (valid) {
 #pragma unroll
         for (int q = 0; q < E; ++q)
-            if (PL::slot_out(q) && PL::lane_out(j, q)) buf_store_c_aux<OFDFT_CPASS_ST_AUX>(out + roff + b0 + PL::cout(q) * se_u, voff, v[q]);
+            if (PL::slot_out(q) && PL::lane_out(j, q)) {
+                if constexpr (LAP) v[q] = cadd(v[q], x[q]);
+                buf_store_c_aux<OFDFT_CPASS_ST_AUX>(out + roff + b0 + PL::cout(q) * se_u, voff, v[q]);
+            }
     }
 }
 

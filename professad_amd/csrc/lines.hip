@@ -644,6 +644,35 @@ int yderiv_add(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double 
     }
     return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
 }
+// y part of the Laplacian plus a finished spectrum of the output's layout (yderiv_kernel<LEN, false, true>)
+template <int LEN>
+int launch_ylap_t(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
+    cplx* tw;
+    if (int rc = get_twiddle(c, LEN, &tw)) return rc;
+    using Cfg = PassCfg<LEN>;
+    LineMap main, rem;
+    pass_maps(c, 1, main, rem);
+    const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
+    OFDFT_LAUNCH(c, st, "ylap", (yderiv_kernel<LEN, false, true>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, in, out, main, rem, mb,
+                 c->g.main_count, (const cplx*)tw, (real)scale, (cplx*)nullptr, add);
+    return 0;
+}
+int ylap(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
+    switch (c->n1) {
+        case 8: return launch_ylap_t<8>(c, in, add, out, scale, st);
+        case 16: return launch_ylap_t<16>(c, in, add, out, scale, st);
+        case 32: return launch_ylap_t<32>(c, in, add, out, scale, st);
+        case 64: return launch_ylap_t<64>(c, in, add, out, scale, st);
+        case 128: return launch_ylap_t<128>(c, in, add, out, scale, st);
+        case 256: return launch_ylap_t<256>(c, in, add, out, scale, st);
+        case 512: return launch_ylap_t<512>(c, in, add, out, scale, st);
+        case 1024: return launch_ylap_t<1024>(c, in, add, out, scale, st);
+#define X(L) case L: return launch_ylap_t<L>(c, in, add, out, scale, st);
+        OFDFT_MIXED_LINES(X)
+#undef X
+    }
+    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
+}
 int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd) {
     switch (c->n1) {
         case 8: return launch_yderiv_t<8>(c, in, out, scale, st, fwd);

@@ -257,7 +257,7 @@ __device__ __forceinline__ float lindhard_shape(float eta) {
     return f;
 }
 
-enum { SPEC_HARTREE = 0, SPEC_LAPLACE = 1, SPEC_LINDHARD = 2 };
+enum { SPEC_HARTREE = 0, SPEC_LAPLACE = 1, SPEC_LINDHARD = 2, SPEC_LAPLACE_AC = 3 };
 // out = in * f(k); p0,p1 parameters (LINDHARD: p0 = prefactor, p1 = 1/(2 kF))
 template <int OP>
 __global__ void spec_scale_kernel(const cplx* __restrict__ in, cplx* __restrict__ out, KGeom kg, real p0, real p1) {
@@ -599,16 +599,17 @@ template <bool HAS_H, bool HAS_G> struct MixDensity {
 
 // split-derivative form: n^ -> [v_H^], i f_a n^  with the INTEGER frequency f_a along x (the Cartesian gradient is assembled
 // from the three index derivatives in zpbe2_kernel)
-template <bool HAS_H, bool HAS_L = false> struct MixDensityA {
+// (HAS_A = false: i f_a n^ was formed from the z spectrum before the y-forward -- OFDFT_OPT_AXIS_PASSES -- and has no output here)
+template <bool HAS_H, bool HAS_L = false, bool HAS_A = true> struct MixDensityA {
     KGeom kg;
-    // outputs: [v_H^ (real coefficient)], i f_a n^ (imaginary), [-k^2 n^ (real): the Laplacian of n for the q-dependent
+    // outputs: [v_H^ (real coefficient)], [i f_a n^ (imaginary)], [-k^2 n^ (real): the Laplacian of n for the q-dependent
     // Pauli-Gaussian members, functional_tools.py:271-287]
-    static __device__ __forceinline__ constexpr bool imag(int o) { return o == (HAS_H ? 1 : 0); }
+    static __device__ __forceinline__ constexpr bool imag(int o) { return HAS_A && o == (HAS_H ? 1 : 0); }
     template <int O, int I> static __device__ __forceinline__ constexpr bool present() { return true; }
     template <int O, int I> static __device__ __forceinline__ constexpr bool imag_oi() { return imag(O); }
     template <int O, int I>
     __device__ __forceinline__ real coef(int x, int y, int z, long long, unsigned) const {
-        if constexpr (O == (HAS_H ? 1 : 0)) {
+        if constexpr (HAS_A && O == (HAS_H ? 1 : 0)) {
             return ifreq(x, kg.g.n0);
         } else {
             real kx, ky, kz, k2;
@@ -626,6 +627,17 @@ struct MixDerivA {
     template <int O, int I> static __device__ __forceinline__ constexpr bool imag_oi() { return true; }
     template <int O, int I>
     __device__ __forceinline__ real coef(int x, int, int, long long, unsigned) const { return ifreq(x, kg.g.n0); }
+};
+// n^ -> i f_a n^ scale, for a spectrum that is not y-forwarded (the multiply does not depend on y, so the pass commutes with the
+// y transforms): scale = n1 stands in for the y round trip the unnormalised transforms of the other route make
+struct MixDerivAS {
+    int n0;
+    real scale;
+    static __device__ __forceinline__ constexpr bool imag(int) { return true; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool present() { return true; }
+    template <int O, int I> static __device__ __forceinline__ constexpr bool imag_oi() { return true; }
+    template <int O, int I>
+    __device__ __forceinline__ real coef(int x, int, int, long long, unsigned) const { return scale * ifreq(x, n0); }
 };
 // (G_a^, L^) -> i f_a G_a^ + (k^2 / 2) L^ : the x part of the divergence plus the Laplacian of df/d(lap n), folded into the
 // quantity the combine kernel subtracts twice (v += df/dn - 2 div + lap(df/dL), tools_for_tests.py:86-118)
@@ -684,7 +696,7 @@ template <bool HAS_L> struct MixDerivAH {
     }
 };
 
-// one spectrum times a real f(k): OP as spec_scale_kernel
+// one spectrum times a real f(k): OP as spec_scale_kernel; SPEC_LAPLACE_AC (x pass only): the x / z part of the Laplacian, see ylap
 template <int OP> struct MixScale {
     KGeom kg;
     real p0, p1;
@@ -694,6 +706,10 @@ template <int OP> struct MixScale {
     template <int O, int I>
     __device__ __forceinline__ real coef(int x, int y, int z, long long, unsigned) const {
         real kx, ky, kz, k2;
+        if constexpr (OP == SPEC_LAPLACE_AC) {      // -k^2(x, 0, z) p0: the spectrum is not y-forwarded, `y` is a grid index here
+            kvec_xyz(kg, x, -kg.y0, z, kx, ky, kz, k2);
+            return -p0 * k2;
+        }
         kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
         if (OP == SPEC_HARTREE) return (k2 != 0.0) ? 4.0 * kPiR / k2 : 0.0;
         if (OP == SPEC_LAPLACE) return -k2;

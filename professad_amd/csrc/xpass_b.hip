@@ -9,6 +9,9 @@ template int xfused<1, 1, MixDensityA<false, false>>(ofdft_ctx*, const XfIo&, co
 template int xfused<1, 2, MixDensityA<true, false>>(ofdft_ctx*, const XfIo&, const MixDensityA<true, false>&, hipStream_t, const char*, const XfLayout&);
 template int xfused<1, 2, MixDensityA<false, true>>(ofdft_ctx*, const XfIo&, const MixDensityA<false, true>&, hipStream_t, const char*, const XfLayout&);
 template int xfused<1, 3, MixDensityA<true, true>>(ofdft_ctx*, const XfIo&, const MixDensityA<true, true>&, hipStream_t, const char*, const XfLayout&);
+// OFDFT_OPT_AXIS_PASSES: D_a n from the z spectrum; what is left of the density pass beside a Laplacian-dependent GGA member
+template int xfused<1, 1, MixDerivAS>(ofdft_ctx*, const XfIo&, const MixDerivAS&, hipStream_t, const char*, const XfLayout&);
+template int xfused<1, 2, MixDensityA<true, true, false>>(ofdft_ctx*, const XfIo&, const MixDensityA<true, true, false>&, hipStream_t, const char*, const XfLayout&);
 
 extern template int xfused<3, 3, MixWgc>(ofdft_ctx*, const XfIo&, const MixWgc&, hipStream_t, const char*, const XfLayout&);      // xpass_a.hip
 int xfused_wgc(ofdft_ctx* c, const XfIo& io, const MixWgc& mix, hipStream_t st, const char* nm, const XfLayout& lay) {

@@ -49,9 +49,9 @@ def load_counter(d, counter):
 
 
 # kernel symbol fragment -> the engine's profiling class (the names bench.py's `kernels` table uses)
-CLASSES = [('cpass_kernel', 'cpass_y'), ('yderiv_kernel', 'yderiv'), ('ypass_xchg_kernel', 'cpass_y'),
-           ('MixWgc', 'xfused_wgc'), ('MixDiv', 'xfused_div'), ('MixDerivA', 'xfused_div'), ('MixDensity', 'xfused_n'),
-           ('MixScale<1>', 'xfused_lap'), ('MixScale<2>', 'xfused_lind'), ('xw_kernel', 'xfused_wgc'),
+CLASSES = [('cpass_kernel', 'cpass_y'), (', false, true>', 'ylap'), ('yderiv_kernel', 'yderiv'), ('ypass_xchg_kernel', 'cpass_y'),
+           ('MixWgc', 'xfused_wgc'), ('MixDiv', 'xfused_div'), ('MixDerivAS', 'xfused_n'), ('MixDerivA', 'xfused_div'), ('MixDensity', 'xfused_n'),
+           ('MixScale<1>', 'xfused_lap'), ('MixScale<3>', 'xfused_lap'), ('MixScale<2>', 'xfused_lind'), ('xw_kernel', 'xfused_wgc'),
            ('zi_combine_kernel', 'zi_combine'), ('zi_wgc_kernel', 'zi_wgc'), ('zpbe2_kernel', 'zpbe'), ('zpbe_kernel', 'zpbe'),
            ('zf_powers_kernel', 'zf_powers'), ('zf_density_kernel', 'zf_density'), ('chi_grad_kernel', 'chi_grad'),
            ('sum_kernel', 'sum'), ('wgc_table_kernel', 'wgc_table'), ('reduce_partials_kernel', 'reduce'), ('reduce_rows_kernel', 'reduce'),
