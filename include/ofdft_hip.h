@@ -104,6 +104,13 @@ typedef struct ofdft_ctx ofdft_ctx;
 #define OFDFT_P_NLK_P2      16  /* reserved (0) */
 #define OFDFT_NPARAMS       17
 
+/* The scalar block of an evaluation (ofdft_dist_finish / ofdft_dist_scalars / ofdft_dist_energies; csrc/eval_layout.h names every
+ * slot): OFDFT_NSCALARS doubles owned by the context, of which the first OFDFT_NSUMS are the local sums of an evaluation (ten of the
+ * combine kernel, then the GGA sums: exchange, correlation, kinetic) and slot OFDFT_SCALAR_SUMSQ holds sum chi^2 of the closure form. */
+#define OFDFT_NSUMS         13
+#define OFDFT_NSCALARS      16
+#define OFDFT_SCALAR_SUMSQ  15
+
 /* ofdft_query selectors */
 #define OFDFT_Q_FFT_COUNT        0  /* 3-D FFTs executed by the last energy call              */
 #define OFDFT_Q_WORKSPACE_BYTES  1  /* device bytes held by the ctx                            */
@@ -119,6 +126,8 @@ typedef struct ofdft_ctx ofdft_ctx;
                                         (the kernel is switched off for the context after the first one) */
 #define OFDFT_Q_XPASS_KINDS     11  /* bitmask of the fused x-pass kernel families the last energy call launched (OFDFT_XPASS_*); like
                                         OFDFT_Q_LAUNCH_COUNT it is reset per call and a hipGraph replay reports what its captured call launched */
+#define OFDFT_Q_RES_CLOCK       16  /* first of OFDFT_Q_RES_CLOCK_COUNT selectors: phase clock of the last persistent-kernel evaluation in    */
+#define OFDFT_Q_RES_CLOCK_COUNT 12  /* microseconds (libraries built with -DOFDFT_RES_CLOCK=1 only; tools/resident_probe.py)                  */
 #define OFDFT_XPASS_GROUP    (1u << 0)  /* group-parallel kernel (fft_kernels.h: xfused_kernel)                               */
 #define OFDFT_XPASS_WAVE     (1u << 1)  /* wave-local kernel (xwave.h)                                                        */
 #define OFDFT_XPASS_CROSS1   (1u << 2)  /* cross-wave kernel (xcross.h), one line per lane                                    */
@@ -195,11 +204,11 @@ int  ofdft_set_collectives(ofdft_ctx* ctx, ofdft_all_to_all_fn all_to_all, ofdft
  *     ofdft_dist_sumsq (closure form only) -> all-reduce -> c = N_e / (mean chi^2 vol)
  *     ofdft_dist_begin; for stage in 1..4, for chain in 0..1: [wait for the chain's previous all-to-all]
  *         ofdft_dist_stage(stage, chain) + all_to_all(bytes_per_peer)  (asynchronous if the transport allows);
- *     [wait for both] ofdft_dist_finish -> all-reduce of 13 local sums -> ofdft_dist_energies; ofdft_dist_chi_grad.
+ *     [wait for both] ofdft_dist_finish -> all-reduce of OFDFT_NSUMS local sums -> ofdft_dist_energies; ofdft_dist_chi_grad.
  * Device-resident scalars (no host round trip before the final sums): pass local_sum_host = NULL to
- * ofdft_dist_sumsq, all-reduce scalars[15] in place (ofdft_dist_scalars), call ofdft_dist_begin with from_chi = 2
+ * ofdft_dist_sumsq, all-reduce scalars[OFDFT_SCALAR_SUMSQ] in place (ofdft_dist_scalars), call ofdft_dist_begin with from_chi = 2
  * (the closure scale is then formed on the device), ofdft_dist_finish with local_sums_host = NULL, all-reduce
- * scalars[0..12] in place and copy them to the host once; ofdft_dist_chi_grad with cscale = 0 uses the device scale.
+ * scalars[0 .. OFDFT_NSUMS - 1] in place and copy them to the host once; ofdft_dist_chi_grad with cscale = 0 uses the device scale.
  * With nranks == 1 the same calls work and every bytes_per_peer is 0.  These stand behind the same reference
  * interfaces as ofdft_energy_potential / ofdft_energy_grad_chi (system.py:830-838, functional_tools.py:9-31). */
 int  ofdft_create_dist(ofdft_ctx** out, int n0_global, int n1_global, int n2, int dtype, int device_id, int nranks, int rank);
@@ -224,9 +233,9 @@ int  ofdft_dist_stage(ofdft_ctx* ctx, int stage, int chain, void* stream, unsign
  * ofdft_dist_stage serves K == 1 only. */
 int  ofdft_dist_step(ofdft_ctx* ctx, int step, int chain, int chunk, void* stream, unsigned long long* bytes_per_peer,
                      void** sendbuf_dev, void** recvbuf_dev);
-int  ofdft_dist_finish(ofdft_ctx* ctx, double* local_sums_host /*[13] or NULL*/, void* stream);
-int  ofdft_dist_scalars(ofdft_ctx* ctx, void** scalars_dev /* 16 doubles owned by the context */);
-int  ofdft_dist_energies(ofdft_ctx* ctx, const double* global_sums /*[13]*/, double* E_terms_host, double* vn_integral);
+int  ofdft_dist_finish(ofdft_ctx* ctx, double* local_sums_host /*[OFDFT_NSUMS] or NULL*/, void* stream);
+int  ofdft_dist_scalars(ofdft_ctx* ctx, void** scalars_dev /* OFDFT_NSCALARS doubles owned by the context */);
+int  ofdft_dist_energies(ofdft_ctx* ctx, const double* global_sums /*[OFDFT_NSUMS]*/, double* E_terms_host, double* vn_integral);
 int  ofdft_dist_chi_grad(ofdft_ctx* ctx, const void* chi_local_dev, const void* v_local_dev, void* grad_local_dev,
                          double cscale, double mu, void* stream);
 

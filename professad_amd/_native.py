@@ -24,6 +24,8 @@ TERM_ORDER = ['ion_electron', 'hartree', 'tf', 'vw', 'wt_nl', 'wgc99_nl', 'lda_x
               'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk']
 NTERMS = 15
 NPARAMS = 17
+# local sums of an evaluation; doubles of the context's device-resident scalar block (ofdft_dist_scalars); its slot of sum chi^2
+NSUMS, NSCALARS, SCALAR_SUMSQ = 13, 16, 15
 NLK_KGAP, NLK_MGP, NLK_XWM = 1, 2, 3      # OFDFT_P_NLK_KIND
 NTERMS_ALWAYS = 14      # per-term results always carry these terms (zero when not in the set); a later one only while it is set
 
@@ -39,8 +41,10 @@ Q_RESIDENT_FALLBACKS = 8
 Q_XCHG_CHUNKS = 9
 Q_YFWD_FUSED = 10
 Q_XPASS_KINDS = 11
+Q_RES_CLOCK, Q_RES_CLOCK_COUNT = 16, 12      # phase clock of the persistent kernel (libraries built with -DOFDFT_RES_CLOCK=1)
 # bits of ofdft_query(Q_XPASS_KINDS): the fused x-pass kernel families of the last energy call
 XPASS_GROUP, XPASS_WAVE, XPASS_CROSS1, XPASS_CROSS2, XPASS_CHIRPZ = 1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4
+OPT_PIPELINE, OPT_SIDE_STREAM, OPT_XCHUNKS, OPT_XCHUNK_MASK, OPT_SPLIT_COMBINE = 0, 1, 2, 3, 4
 OPT_BLUESTEIN = 5
 OPT_GGA_SPLIT = 6
 OPT_GRAPH = 7
@@ -96,93 +100,55 @@ def load(dtype=F64):
         raise NativeLibraryError('cannot load %s: %s (the HIP engine is required; there is no CPU fallback)'
                                  % (path, e))
     vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.c_int
+    for sym in EXPORTS:          # every entry point returns an int status, but for the four overridden below
+        getattr(lib, sym).restype = ip
     lib.ofdft_create.argtypes = [C.POINTER(vp), ip, ip, ip, ip, ip]
-    lib.ofdft_create.restype = ip
     lib.ofdft_destroy.argtypes = [vp]
     lib.ofdft_destroy.restype = None
     lib.ofdft_last_error.argtypes = [vp]
     lib.ofdft_last_error.restype = C.c_char_p
     lib.ofdft_set_cell.argtypes = [vp, dp]
-    lib.ofdft_set_cell.restype = ip
     lib.ofdft_set_terms.argtypes = [vp, C.c_uint32, dp, ip]
-    lib.ofdft_set_terms.restype = ip
     lib.ofdft_energy_potential.argtypes = [vp, vp, vp, dp, vp, vp]
-    lib.ofdft_energy_potential.restype = ip
     lib.ofdft_energy_grad_chi.argtypes = [vp, vp, vp, C.c_double, dp, dp, vp, vp]
-    lib.ofdft_energy_grad_chi.restype = ip
     lib.ofdft_rfftn.argtypes = [vp, vp, vp, vp]
-    lib.ofdft_rfftn.restype = ip
     lib.ofdft_irfftn.argtypes = [vp, vp, vp, vp]
-    lib.ofdft_irfftn.restype = ip
     lib.ofdft_debug_math.argtypes = [vp, ip, vp, vp, C.c_longlong, vp]
-    lib.ofdft_debug_math.restype = ip
     lib.ofdft_query.argtypes = [vp, ip, dp]
-    lib.ofdft_query.restype = ip
     lib.ofdft_create_dist.argtypes = [C.POINTER(vp), ip, ip, ip, ip, ip, ip, ip]
-    lib.ofdft_create_dist.restype = ip
     lib.ofdft_dist_sumsq.argtypes = [vp, vp, ip, dp, vp]
-    lib.ofdft_dist_sumsq.restype = ip
     lib.ofdft_dist_begin.argtypes = [vp, vp, ip, C.c_double, C.c_double, vp, vp, vp]
-    lib.ofdft_dist_begin.restype = ip
     lib.ofdft_dist_stage.argtypes = [vp, ip, ip, vp, C.POINTER(C.c_ulonglong), C.POINTER(vp), C.POINTER(vp)]
-    lib.ofdft_dist_stage.restype = ip
     lib.ofdft_dist_step.argtypes = [vp, ip, ip, ip, vp, C.POINTER(C.c_ulonglong), C.POINTER(vp), C.POINTER(vp)]
-    lib.ofdft_dist_step.restype = ip
     lib.ofdft_dist_scalars.argtypes = [vp, C.POINTER(vp)]
-    lib.ofdft_dist_scalars.restype = ip
     lib.ofdft_dist_finish.argtypes = [vp, dp, vp]
-    lib.ofdft_dist_finish.restype = ip
     lib.ofdft_dist_energies.argtypes = [vp, dp, dp, dp]
-    lib.ofdft_dist_energies.restype = ip
     lib.ofdft_dist_chi_grad.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, vp]
-    lib.ofdft_dist_chi_grad.restype = ip
     lib.ofdft_ipc_export.argtypes = [vp, vp, C.POINTER(C.c_ulonglong)]
-    lib.ofdft_ipc_export.restype = ip
     lib.ofdft_ipc_attach.argtypes = [vp, ip, vp, C.POINTER(C.c_ulonglong)]
-    lib.ofdft_ipc_attach.restype = ip
     lib.ofdft_ipc_detach.argtypes = [vp]
-    lib.ofdft_ipc_detach.restype = ip
     lib.ofdft_dist_closure.argtypes = [vp, vp, vp, C.c_double, dp, dp, vp, vp, vp]
-    lib.ofdft_dist_closure.restype = ip
     lib.ofdft_ionic_potential.argtypes = [vp, dp, ip, dp, dp, ip, C.c_double, ip, vp, ip, vp]
-    lib.ofdft_ionic_potential.restype = ip
     lib.ofdft_ion_electron_forces.argtypes = [vp, vp, dp, ip, dp, dp, ip, C.c_double, ip, dp, vp]
-    lib.ofdft_ion_electron_forces.restype = ip
     lib.ofdft_stress.argtypes = [vp, vp, dp, vp]
-    lib.ofdft_stress.restype = ip
     lib.ofdft_ion_electron_stress.argtypes = [vp, vp, dp, ip, dp, dp, ip, C.c_double, ip, dp, vp]
-    lib.ofdft_ion_electron_stress.restype = ip
     lib.ofdft_ion_ion.argtypes = [vp, dp, dp, ip, C.c_double, dp, dp, dp, vp]
-    lib.ofdft_ion_ion.restype = ip
     lib.ofdft_ion_ion_cells.argtypes = [vp, dp, dp, ip, C.c_double, C.c_double, ip, ip, dp, dp, dp, vp]
-    lib.ofdft_ion_ion_cells.restype = ip
     lib.ofdft_lbfgs_create.argtypes = [C.POINTER(vp), C.c_longlong, ip, ip]
-    lib.ofdft_lbfgs_create.restype = ip
     lib.ofdft_lbfgs_destroy.argtypes = [vp]
     lib.ofdft_lbfgs_destroy.restype = None
     lib.ofdft_lbfgs_last_error.argtypes = [vp]
     lib.ofdft_lbfgs_last_error.restype = C.c_char_p
     lib.ofdft_lbfgs_reset.argtypes = [vp]
-    lib.ofdft_lbfgs_reset.restype = ip
     lib.ofdft_lbfgs_dots.argtypes = [vp, vp, dp, C.POINTER(ip), vp]
-    lib.ofdft_lbfgs_dots.restype = ip
     lib.ofdft_lbfgs_commit.argtypes = [vp, ip]
-    lib.ofdft_lbfgs_commit.restype = ip
     lib.ofdft_lbfgs_update.argtypes = [vp, dp, dp, C.c_double, C.c_double, vp, vp, dp, vp]
-    lib.ofdft_lbfgs_update.restype = ip
     lib.ofdft_lbfgs_direction.argtypes = [vp, dp, ip, ip, dp, dp, dp, dp, C.POINTER(ip), C.POINTER(ip)]
-    lib.ofdft_lbfgs_direction.restype = ip
     lib.ofdft_lbfgs_abs_step.argtypes = [vp, dp]
-    lib.ofdft_lbfgs_abs_step.restype = ip
     lib.ofdft_set_collectives.argtypes = [vp, A2A_FN, ALLREDUCE_FN, vp]
-    lib.ofdft_set_collectives.restype = ip
     lib.ofdft_set_option.argtypes = [vp, ip, C.c_double]
-    lib.ofdft_set_option.restype = ip
     lib.ofdft_set_profiling.argtypes = [vp, ip]
-    lib.ofdft_set_profiling.restype = ip
     lib.ofdft_profile_count.argtypes = [vp]
-    lib.ofdft_profile_count.restype = ip
     lib.ofdft_profile_get.argtypes = [vp, ip, C.c_char_p, ip, dp, C.POINTER(C.c_longlong)]
-    lib.ofdft_profile_get.restype = ip
     _LIBS[dtype] = lib
     return lib

@@ -199,14 +199,16 @@ int fetch_partials(ofdft_ctx* c, int rows, int ns, double* sums, hipStream_t st)
     return 0;
 }
 
-int device_sum(ofdft_ctx* c, const real* a, bool square, double* out, hipStream_t st) {
+// per-workgroup sums of a (square: of a^2) over the local points -> c->d_partial; returns their count
+int enqueue_sum(ofdft_ctx* c, const real* a, bool square, hipStream_t st) {
     const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
     if (square)
         OFDFT_LAUNCH(c, st, "sum", (sum_kernel<true>), dim3(blocks), dim3(kRedThreads), 0, a, c->npts, c->d_partial);
     else
         OFDFT_LAUNCH(c, st, "sum", (sum_kernel<false>), dim3(blocks), dim3(kRedThreads), 0, a, c->npts, c->d_partial);
-    return fetch_partials(c, blocks, 1, out, st);
+    return blocks;
 }
+int device_sum(ofdft_ctx* c, const real* a, bool square, double* out, hipStream_t st) { return fetch_partials(c, enqueue_sum(c, a, square, st), 1, out, st); }
 
 // ---------------------------------------------------------------------------------- WGC tables
 void wgc_series_coeffs(int nt, std::vector<double>& A, std::vector<double>& B) {
@@ -368,28 +370,27 @@ int ensure_nlk_table(ofdft_ctx* c, const TermScalars& ts, hipStream_t st) {
 namespace {
 
 // ---------------------------------------------------------------------------------- combine / energies
-// the reduced sums of an evaluation (combine scalars, GGA scalars) as per-term energies and sum(v n) dV: every pipeline ends here
-void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pbe_sums, double* E_terms, double* vn_int) {
+// the reduced sums of an evaluation as per-term energies and sum(v n) dV: every pipeline ends here.
+// Term index (bit position, E_terms[]) -> slot of its energy sum (eval_layout.h): a new term is one line
+constexpr int kTermSumSlot[OFDFT_NTERMS] = {
+    kSumIonElectron, kSumHartree, kSumTf, kSumVw, kSumNl /* WT_NL */, kSumWgc, kSumLdaX, kSumLocalC /* PZ_C */, kSumLocalC /* PW_C */,
+    kSumLocalC /* CHACHIYO_C */, kSumGgaX, kSumGgaC, kSumGgaK, kSumVwgtf, kSumNl /* NLK: rides the Wang-Teter section (combine_mask) */};
+double energies_from_sums(const ofdft_ctx* c, const double sums[kNSums], double* E_terms) {
     const unsigned mask = c->mask;
     const double dV = c->dV;
-    if (mask & OFDFT_ION_ELECTRON) E_terms[0] = sums[0] * dV;
-    if (mask & OFDFT_HARTREE) E_terms[1] = sums[1] * dV;
-    if (mask & OFDFT_TF) E_terms[2] = sums[2] * dV;
-    if (mask & OFDFT_VW) E_terms[3] = sums[3] * dV;
-    if (mask & OFDFT_WT_NL) E_terms[4] = sums[4] * dV;
-    if (mask & OFDFT_WGC99_NL) E_terms[5] = sums[5] * dV;
-    if (mask & OFDFT_LDA_X) E_terms[6] = sums[6] * dV;
     // one local correlation flavour is expected; if several are set their sum is split evenly
     int nc = 0;
-    for (int b = 7; b <= 9; ++b) nc += (mask >> b) & 1;
-    for (int b = 7; b <= 9; ++b)
-        if ((mask >> b) & 1) E_terms[b] = sums[7] * dV / nc;
-    if (mask & OFDFT_PBE_X) E_terms[10] = pbe_sums[0] * dV;
-    if (mask & OFDFT_PBE_C) E_terms[11] = pbe_sums[1] * dV;
-    if (mask & OFDFT_GGA_K) E_terms[12] = pbe_sums[2] * dV;
-    if (mask & OFDFT_VWGTF) E_terms[13] = sums[9] * dV;
-    if (mask & OFDFT_NLK) E_terms[14] = sums[4] * dV;
-    *vn_int = sums[8] * dV;
+    for (int t = 0; t < OFDFT_NTERMS; ++t) nc += kTermSumSlot[t] == kSumLocalC && ((mask >> t) & 1);
+    for (int t = 0; t < OFDFT_NTERMS; ++t)
+        if ((mask >> t) & 1) E_terms[t] = kTermSumSlot[t] == kSumLocalC ? sums[kSumLocalC] * dV / nc : sums[kTermSumSlot[t]] * dV;
+    return sums[kSumVn] * dV;
+}
+// the epilogue of an entry point: E_terms (entries of unset terms 0) and mu = sum(v n) dV / N_e from the sums; returns sum(v n) dV
+double report_energies(const ofdft_ctx* c, const double sums[kNSums], double* E_terms, double* mu_host = nullptr, double n_electrons = 1.0) {
+    for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
+    const double vn = energies_from_sums(c, sums, E_terms);
+    if (mu_host) *mu_host = vn / n_electrons;
+    return vn;
 }
 
 // launch the combine kernel and turn its partial sums into per-term energies
@@ -397,7 +398,8 @@ void energies_from_sums(const ofdft_ctx* c, const double* sums, const double* pb
 // order (c->d_reduced, mirrored into the pinned host block by the reduce kernel), chi_grad forms mu from them on the device and the
 // caller turns the mirror into energies after ITS one synchronisation (an evaluation used to wait four times: sum chi^2, the GGA
 // sums, the combine sums, the end).  Not for the two-pass stabilised WT-style functional, whose weights pass through the host.
-int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, double* E_terms, double* vn_int,
+// sums: the caller's kNSums sums with the GGA slots already filled (or zero); the combine's slots are filled here
+int finish_terms(ofdft_ctx* c, const CombineArgs& ca, double sums[kNSums], double* E_terms, double* vn_int,
                  hipStream_t st, bool defer = false) {
     const long long npts = c->npts;
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
@@ -409,14 +411,13 @@ int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, do
     if (!cb.conv_b) cb.conv_b = d;
     if (!cb.u0) cb.u0 = cb.u1 = cb.u2 = cb.gA = cb.gB = cb.gC = d;
     if (!cb.dfdn) cb.dfdn = cb.div = d;
-    double sums[kCombineScalars];
     double wts_f = 1.0;
     if (wts_active(c)) {      // first pass: energies only -> X = T_NL / T_TF -> weights of the two potentials
         CombineArgs c1 = cb;
         c1.v_out = nullptr;
         OFDFT_LAUNCH(c, st, "combine", combine_kernel, dim3(blocks), dim3(kRedThreads), 0, c1, c->d_partial);
         if (int rc = fetch_partials(c, blocks, kCombineScalars, sums, st)) return rc;
-        const double X = sums[4] / sums[2];
+        const double X = sums[kSumNl] / sums[kSumTf];
         wts_f = std::exp(X);
         cb.w_tf = (real)(wts_f * (1.0 - X));
         cb.w_nl = (real)wts_f;
@@ -428,10 +429,10 @@ int finish_terms(ofdft_ctx* c, const CombineArgs& ca, const double* pbe_sums, do
     }
     if (int rc = fetch_partials(c, blocks, kCombineScalars, sums, st)) return rc;
     if (wts_active(c)) {
-        sums[2] *= wts_f;
-        sums[4] = 0.0;
+        sums[kSumTf] *= wts_f;
+        sums[kSumNl] = 0.0;
     }
-    energies_from_sums(c, sums, pbe_sums, E_terms, vn_int);
+    *vn_int = energies_from_sums(c, sums, E_terms);
     return 0;
 }
 
@@ -465,7 +466,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
     TermScalars ts = term_scalars(c, nel);
     if (int rc = ensure_term_tables(c, ts, st)) return rc;
     ca.tc = ts.tc;
-    double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
+    double sums[kNSums] = {};
 
     cplx *s0 = nullptr, *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
     if (int rc = spec_ws(c, "s0", &s0)) return rc;
@@ -675,8 +676,8 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
         OFDFT_LAUNCH(c, st, "pbe", pbe_kernel, dim3(blocks), dim3(kRedThreads), 0, den, gx, gy, gz, dfdn, npts,
                            gga_sel(c), c->d_partial, lapn);
         if (defer) {
-            OFDFT_REDUCE(c, st, c->d_partial, blocks, kPbeScalars, c->d_reduced + kCombineScalars, c->h_partial + kCombineScalars);
-        } else if (int rc = fetch_partials(c, blocks, kPbeScalars, pbe_sums, st)) {
+            OFDFT_REDUCE(c, st, c->d_partial, blocks, kPbeScalars, c->d_reduced + kSumGga, c->h_partial + kSumGga);
+        } else if (int rc = fetch_partials(c, blocks, kPbeScalars, sums + kSumGga, st)) {
             return rc;
         }
         {
@@ -737,7 +738,7 @@ int run_terms_unfused(ofdft_ctx* c, const real* den, const real* vext, double* E
         ca.u0 = o[0]; ca.u1 = o[1]; ca.u2 = o[2];
         ca.gA = o[3]; ca.gB = o[4]; ca.gC = o[5];
     }
-    return finish_terms(c, ca, pbe_sums, E_terms, vn_int, st, defer);
+    return finish_terms(c, ca, sums, E_terms, vn_int, st, defer);
 }
 
 
@@ -767,7 +768,7 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
     if (int rc = ensure_term_tables(c, ts, st)) return rc;
     ca.tc = ts.tc;
     const NlPow& nlp = ts.nlp;
-    double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
+    double sums[kNSums] = {};
     cplx* s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const char* sn[5] = {"s0", "s1", "s2", "s3", "s4"};
     if (int rc = spec_ws(c, sn[0], &s[0])) return rc;
@@ -809,7 +810,7 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
             const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
             OFDFT_LAUNCH(c, st, "pbe", pbe_kernel, dim3(blocks), dim3(kRedThreads), 0, den, gr[0], gr[1], gr[2], dfdn, npts,
                          gga_sel(c), c->d_partial);
-            if ((rc = fetch_partials(c, blocks, kPbeScalars, pbe_sums, st))) return rc;
+            if ((rc = fetch_partials(c, blocks, kPbeScalars, sums + kSumGga, st))) return rc;
             for (int k = 0; k < 3; ++k)
                 if ((rc = fwd_zy(c, gr[k], s[2 + k], st))) return rc;
             XfIo dio{};
@@ -918,14 +919,14 @@ int run_terms_fast(ofdft_ctx* c, const real* den, const real* vext, double* E_te
         ca.u0 = o[0]; ca.u1 = o[1]; ca.u2 = o[2];
         ca.gA = o[3]; ca.gB = o[4]; ca.gC = o[5];
     }
-    return finish_terms(c, ca, pbe_sums, E_terms, vn_int, st);
+    return finish_terms(c, ca, sums, E_terms, vn_int, st);
 }
 
 // *deferred (out): the unfused pipeline ran in the host-free form (finish_terms: defer) -- E_terms / vn_int are NOT filled yet
 int run_terms(ofdft_ctx* c, const real* den, const real* vext, double* E_terms, real* v_out, double* vn_int,
               hipStream_t st, double nel_known = 0.0, bool* deferred = nullptr) {
     if (deferred) *deferred = false;
-    if (c->fast && !c->force_unfused && !gga_needs_laplacian(c)) return run_terms_fast(c, den, vext, E_terms, v_out, vn_int, st);
+    if (xfused_serves(c)) return run_terms_fast(c, den, vext, E_terms, v_out, vn_int, st);
     const bool defer = deferred && !wts_active(c);
     if (deferred) *deferred = defer;
     return run_terms_unfused(c, den, vext, E_terms, v_out, vn_int, st, nel_known, defer);
@@ -1000,7 +1001,7 @@ int ofdft_create_dist(ofdft_ctx** out, int n0g, int n1g, int n2, int dtype, int 
     }
     if (e == hipSuccess) e = hipMalloc((void**)&c->d_partial, sizeof(double) * (c->partial_rows + kRedMidRows) * kMaxScalars);   // + the first-level sums of OFDFT_REDUCE
     if (e == hipSuccess) e = hipMalloc((void**)&c->d_reduced, sizeof(double) * kMaxScalars);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_scal, sizeof(double) * 8);    // [0] closure scale, [2] split WGC99 energy, [4..6] WT-style weights
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_scal, sizeof(double) * kScalLen);
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_partial, sizeof(double) * kRedBlocks * kMaxScalars);
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
@@ -1142,11 +1143,8 @@ int ofdft_energy_potential(ofdft_ctx* c, const void* den, const void* vext, doub
             if (rrc < 0) return rrc;
             if (rrc == 0) {
                 if (int rc = end_call(c, st)) return rc;
-                if (c->h_partial[13] == 0.0) {
-                    double sums[kNSums];
-                    for (int i = 0; i < kNSums; ++i) sums[i] = c->h_partial[i];
-                    for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-                    energies_from_sums(c, sums, sums + kCombineScalars, E_terms, &vn);
+                if (c->h_partial[kMirrorResTimeout] == 0.0) {
+                    report_energies(c, c->h_partial, E_terms);
                     c->resident_evals++;
                     return OFDFT_OK;
                 }
@@ -1165,9 +1163,8 @@ int ofdft_energy_potential(ofdft_ctx* c, const void* den, const void* vext, doub
     if (int rc = end_call(c, st)) return rc;
     if (deferred) {
         double sums[kNSums];
-        zfused_collect(c, (c->mask & kGgaAny) ? 0 : kCollectNoGga, sums);
-        for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-        energies_from_sums(c, sums, sums + kCombineScalars, E_terms, &vn);
+        zfused_collect(c, collect_flags_unfused(c), sums);
+        report_energies(c, sums, E_terms);
     }
     return OFDFT_OK;
 }
@@ -1188,20 +1185,34 @@ void resident_give_up(ofdft_ctx* c) {
     c->version++;
 }
 
-int closure_enqueue(ofdft_ctx* c, const real* chi, const real* vext, double nel, real* v, real* grad, hipStream_t st) {
-    const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
-    OFDFT_LAUNCH(c, st, "sum", (sum_kernel<true>), dim3(blocks), dim3(kRedThreads), 0, chi, c->npts, c->d_partial);
+// the closure prologue on one GPU, host-free: sum chi^2 -> d_reduced[kSumsqSlot], c = N_e / (mean(chi^2) vol) -> d_scal[kScalClosure] (system.py:833-834)
+void enqueue_closure_scale(ofdft_ctx* c, const real* chi, double n_electrons, hipStream_t st) {
+    const int blocks = enqueue_sum(c, chi, true, st);
     OFDFT_LAUNCH(c, st, "reduce", closure_scale_reduce_kernel, dim3(1), dim3(kRedThreads), 0, (const acc_t*)c->d_partial, blocks,
-                 c->d_reduced + kSumsqSlot, c->d_scal, nel, c->vol / (double)c->npts);
-    const DenSrc ds{chi, 0.0, 1, c->d_scal};
-    if (int rc = zfused_enqueue(c, ds, nel, vext, v, c->h_partial /* any non-null: host copy wanted */, st, true)) return rc;
-    if (grad) {
-        const ZRun& zr = zrun(c);
-        OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, chi, (const real*)v, grad,
-                     c->npts, 0.0, (const acc_t*)c->d_scal, 2.0 * c->dV, 0.0, (const acc_t*)(c->d_reduced + 8), c->dV, nel,
-                     zr.vpart_deferred ? zr.za.v_part : (const real*)nullptr,
-                     zr.late_join ? (const acc_t*)(c->d_scal + 3) : (const acc_t*)nullptr);
-    }
+                 c->d_reduced + kSumsqSlot, c->d_scal + kScalClosure, n_electrons, c->vol / (double)c->npts);
+}
+// One launch of chi_grad_kernel: grad = c 2 chi (v [+ v_part] - mu) dV (system.py:836-837, 850-853)
+struct ChiGrad {
+    const real *chi, *v;
+    real* grad;
+    double cscale, mu;               // the closure scale c and mu from the host; cscale = 0: the kernel reads d_scal[kScalClosure]
+    double nel = 0.0;                // nel > 0: mu is formed by the kernel instead, as d_reduced[kSumVn] dV / nel
+    const real* v_part = nullptr;    // a part of the potential kept in its own array (the split WGC99 kernel's) ...
+    bool vn_share = false;           // ... whose share of sum(v n), d_scal[kScalWgcSplitVn], the kernel adds to d_reduced[kSumVn]
+};
+void enqueue_chi_grad(ofdft_ctx* c, const ChiGrad& g, hipStream_t st) {
+    const bool mu_dev = g.nel > 0.0;
+    OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, g.chi, g.v, g.grad, c->npts,
+                 g.cscale * 2.0 * c->dV, g.cscale > 0.0 ? (const acc_t*)nullptr : (const acc_t*)(c->d_scal + kScalClosure), 2.0 * c->dV,
+                 g.mu, mu_dev ? (const acc_t*)(c->d_reduced + kSumVn) : (const acc_t*)nullptr, c->dV, mu_dev ? g.nel : 1.0, g.v_part,
+                 g.vn_share ? (const acc_t*)(c->d_scal + kScalWgcSplitVn) : (const acc_t*)nullptr);
+}
+
+int closure_enqueue(ofdft_ctx* c, const real* chi, const real* vext, double nel, real* v, real* grad, hipStream_t st) {
+    enqueue_closure_scale(c, chi, nel, st);
+    if (int rc = zfused_enqueue(c, DenSrc{chi, 0.0, 1, c->d_scal + kScalClosure}, nel, vext, v, c->h_partial /* any non-null: host copy wanted */, st, true)) return rc;
+    const ZRun& zr = zrun(c);
+    if (grad) enqueue_chi_grad(c, ChiGrad{chi, v, grad, 0.0, 0.0, nel, zr.vpart_deferred ? zr.za.v_part : nullptr, zr.late_join}, st);
     return 0;
 }
 
@@ -1213,9 +1224,7 @@ void graph_drop(ofdft_ctx* c) {
 
 // the unfused / chirp-z closure can run without touching the host (finish_terms: defer): not the two-pass WT-style functional,
 // and not the configurations run_terms hands to the x-fused pipeline
-bool unfused_deferrable(const ofdft_ctx* c) {
-    return !wts_active(c) && !(c->fast && !c->force_unfused && !gga_needs_laplacian(c));
-}
+bool unfused_deferrable(const ofdft_ctx* c) { return !wts_active(c) && !xfused_serves(c); }
 
 // chi -> (sums in the pinned mirror, grad) for extents without a plan, enqueued on ONE stream without a host synchronisation when
 // *deferred comes back true: sum chi^2 -> c = N_e / (mean(chi^2) vol) stays on the device (system.py:833-834), n = c chi^2 is formed
@@ -1224,32 +1233,23 @@ bool unfused_deferrable(const ofdft_ctx* c) {
 int closure_enqueue_unfused(ofdft_ctx* c, const real* chi, const real* vext, double nel, real* v, real* grad, hipStream_t st,
                             double* E_terms, double* mu_host, bool* deferred) {
     real* den;
-    {
-        const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
-        OFDFT_LAUNCH(c, st, "sum", (sum_kernel<true>), dim3(blocks), dim3(kRedThreads), 0, chi, c->npts, c->d_partial);
-        OFDFT_LAUNCH(c, st, "reduce", closure_scale_reduce_kernel, dim3(1), dim3(kRedThreads), 0, (const acc_t*)c->d_partial, blocks,
-                     c->d_reduced + kSumsqSlot, c->d_scal, nel, c->vol / (double)c->npts);
-    }
+    enqueue_closure_scale(c, chi, nel, st);
     if (int rc = real_ws(c, "den", &den)) return rc;
     OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_SCALE_SQ>), dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, chi, den, c->npts, 0.0,
-                 (const acc_t*)c->d_scal);
+                 (const acc_t*)(c->d_scal + kScalClosure));
     double vn = 0.0;
     double E_tmp[OFDFT_NTERMS];
     if (int rc = run_terms(c, den, vext, E_terms ? E_terms : E_tmp, v, &vn, st, nel, deferred)) return rc;
     if (!*deferred) {          // (the x-fused pipeline with the z-fused stage off, or the two-pass WT-style functional: sums via the host)
         double cfac;
-        HIP_TRY(c, hipMemcpyAsync(&cfac, c->d_scal, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(&cfac, c->d_scal + kScalClosure, sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         const double mu = vn / nel;                                                   // system.py:851
         if (mu_host) *mu_host = mu;
-        if (grad)
-            OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, chi, (const real*)v, grad, c->npts,
-                         cfac * 2.0 * c->dV, (const acc_t*)nullptr, 0.0, mu);
+        if (grad) enqueue_chi_grad(c, ChiGrad{chi, v, grad, cfac, mu}, st);
         return 0;
     }
-    if (grad)
-        OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, chi, (const real*)v, grad, c->npts, 0.0,
-                     (const acc_t*)c->d_scal, 2.0 * c->dV, 0.0, (const acc_t*)(c->d_reduced + 8), c->dV, nel);
+    if (grad) enqueue_chi_grad(c, ChiGrad{chi, v, grad, 0.0, 0.0, nel}, st);
     return 0;
 }
 
@@ -1295,7 +1295,7 @@ int closure_graph(ofdft_ctx* c, const real* chi, const real* vext, double nel, r
             graph_drop(c);
             return 0;
         }
-        ge->collect = unfused ? ((c->mask & kGgaAny) ? 0 : kCollectNoGga) : collect_flags(zrun(c), zrun(c).late_join);
+        ge->collect = unfused ? collect_flags_unfused(c) : collect_flags(zrun(c), zrun(c).late_join);
         ge->fft_count = c->fft_count;
         ge->launch_count = c->launch_count;
         ge->xpass_kinds = c->xpass_kinds;
@@ -1331,12 +1331,12 @@ int ofdft_energy_grad_chi(ofdft_ctx* c, const void* chi, const void* vext, doubl
     if (!(n_electrons > 0.0)) return fail(c, OFDFT_EINVAL, "n_electrons must be positive");
     real* v;
     if (int rc = real_ws(c, "v", &v)) return rc;
+    double sums[kNSums];
+    bool done = false;
     if (zfused_serves(c)) {
         // sum chi^2 -> c = N_e / (mean(chi^2) vol) stays on the device; n = c chi^2 is formed on the fly inside the
         // z kernels; mean(n) vol = N_e by construction; mu is formed on the device too.  One host sync per evaluation
         // (the final sums), nothing in between: the sequence is graph-capturable (closure_graph).
-        double sums[kNSums];
-        bool done = false;
         if (resident_serves(c)) {
             // grids that fit on chip: the whole evaluation is one persistent kernel (resident.hip)
             const int rrc = resident_closure(c, (const real*)chi, (const real*)vext, n_electrons, v, (real*)grad, st);
@@ -1364,7 +1364,7 @@ int ofdft_energy_grad_chi(ofdft_ctx* c, const void* chi, const void* vext, doubl
                 } else {
                     if (int rc = end_call(c, st, timed)) return rc;
                 }
-                if (c->h_partial[13] == 0.0) {
+                if (c->h_partial[kMirrorResTimeout] == 0.0) {
                     for (int i = 0; i < kNSums; ++i) sums[i] = c->h_partial[i];
                     c->resident_evals++;
                     done = true;
@@ -1382,17 +1382,9 @@ int ofdft_energy_grad_chi(ofdft_ctx* c, const void* chi, const void* vext, doubl
             if (int rc = end_call(c, st)) return rc;
             zfused_collect(c, collect_flags(zrun(c), zrun(c).late_join), sums);
         }
-        double vn;
-        for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-        energies_from_sums(c, sums, sums + kCombineScalars, E_terms, &vn);
-        if (mu_host) *mu_host = vn / n_electrons;
-        return OFDFT_OK;
-    }
-    // Unfused / chirp-z pipelines (extents without a plan -- the reference's own odd grids): host-free like the fused form,
-    // and replayed from a captured graph on small grids (closure_enqueue_unfused, closure_graph)
-    {
-        double sums[kNSums];
-        bool done = false;
+    } else {
+        // Unfused / chirp-z pipelines (extents without a plan -- the reference's own odd grids): host-free like the fused form,
+        // and replayed from a captured graph on small grids (closure_enqueue_unfused, closure_graph)
         if (unfused_deferrable(c))
             if (int rc = closure_graph(c, (const real*)chi, (const real*)vext, n_electrons, v, (real*)grad, st, sums, &done, true)) return rc;
         if (!done) {
@@ -1402,13 +1394,10 @@ int ofdft_energy_grad_chi(ofdft_ctx* c, const void* chi, const void* vext, doubl
                 return rc;
             if (int rc = end_call(c, st)) return rc;
             if (!deferred) return OFDFT_OK;        // (E_terms / mu were filled on the way)
-            zfused_collect(c, (c->mask & kGgaAny) ? 0 : kCollectNoGga, sums);
+            zfused_collect(c, collect_flags_unfused(c), sums);
         }
-        double vn;
-        for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-        energies_from_sums(c, sums, sums + kCombineScalars, E_terms, &vn);
-        if (mu_host) *mu_host = vn / n_electrons;
     }
+    report_energies(c, sums, E_terms, mu_host, n_electrons);
     return OFDFT_OK;
 }
 
@@ -1480,14 +1469,8 @@ int ofdft_dist_sumsq(ofdft_ctx* c, const void* x_local, int square, double* loca
     if (!c || !x_local) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
     if (local_sum) return device_sum(c, (const real*)x_local, square != 0, local_sum, st);
-    // device-resident form: the local sum goes to scalars[15] (ofdft_dist_scalars), no host synchronisation
-    const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
-    if (square)
-        OFDFT_LAUNCH(c, st, "sum", (sum_kernel<true>), dim3(blocks), dim3(kRedThreads), 0, (const real*)x_local, c->npts,
-                     c->d_partial);
-    else
-        OFDFT_LAUNCH(c, st, "sum", (sum_kernel<false>), dim3(blocks), dim3(kRedThreads), 0, (const real*)x_local, c->npts,
-                     c->d_partial);
+    // device-resident form: the local sum goes to scalars[OFDFT_SCALAR_SUMSQ] (ofdft_dist_scalars), no host synchronisation
+    const int blocks = enqueue_sum(c, (const real*)x_local, square != 0, st);
     OFDFT_REDUCE(c, st, c->d_partial, blocks, 1, c->d_reduced + kSumsqSlot);
     HIP_TRY(c, hipGetLastError());
     return OFDFT_OK;
@@ -1514,10 +1497,10 @@ int ofdft_dist_begin(ofdft_ctx* c, const void* src_local, int from_chi, double c
     if (wts_active(c) && c->nranks > 1)
         return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND) is served by single-GPU contexts");
     ZRun& r = zrun(c);
-    if (from_chi == 2) {      // closure scale from the (all-reduced) sum of chi^2 in scalars[15]; it never visits the host
-        OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal, nel_global,
-                     c->vol / (double)c->npts_g);
-        r.ds = DenSrc{(const real*)src_local, 0.0, 1, c->d_scal};
+    if (from_chi == 2) {      // closure scale from the (all-reduced) sum of chi^2 in scalars[OFDFT_SCALAR_SUMSQ]; it never visits the host
+        OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal + kScalClosure,
+                     nel_global, c->vol / (double)c->npts_g);
+        r.ds = DenSrc{(const real*)src_local, 0.0, 1, c->d_scal + kScalClosure};
     } else {
         r.ds = DenSrc{(const real*)src_local, (real)cscale, from_chi, nullptr};
     }
@@ -1632,8 +1615,8 @@ int ofdft_dist_step(ofdft_ctx* c, int step, int chain, int chunk, void* stream, 
     return OFDFT_OK;
 }
 
-// Stage 5: y-inverse of the last exchange, combine; local_sums[12] = 9 combine scalars + GGA sums (PBE x, c, kinetic) (to be summed
-// over ranks by the caller, then turned into energies by ofdft_dist_energies).
+// Stage 5: y-inverse of the last exchange, combine; local_sums[OFDFT_NSUMS] = the combine sums + the GGA sums (to be summed over ranks
+// by the caller, then turned into energies by ofdft_dist_energies).
 int ofdft_dist_finish(ofdft_ctx* c, double* local_sums, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c) return OFDFT_EINVAL;
@@ -1645,7 +1628,7 @@ int ofdft_dist_finish(ofdft_ctx* c, double* local_sums, void* stream) {
         return fail(c, OFDFT_ESTATE, "ofdft_dist_finish called before step 6 of both chains");
     int rc;
     if ((rc = zstage5(c, local_sums, st, false, stepped ? 2 : 0))) return rc;
-    if (!local_sums) {        // device-resident form: scalars[0..10] hold the local sums, nothing waits here
+    if (!local_sums) {        // device-resident form: scalars[0 .. OFDFT_NSUMS - 1] hold the local sums, nothing waits here
         HIP_TRY(c, hipEventRecord(c->ev1, st));
         c->ms_pending = true;
         HIP_TRY(c, hipGetLastError());
@@ -1660,8 +1643,7 @@ int ofdft_dist_finish(ofdft_ctx* c, double* local_sums, void* stream) {
 
 int ofdft_dist_energies(ofdft_ctx* c, const double* global_sums, double* E_terms, double* vn_int) {
     if (!c || !global_sums || !E_terms || !vn_int) return OFDFT_EINVAL;
-    for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-    energies_from_sums(c, global_sums, global_sums + kCombineScalars, E_terms, vn_int);
+    *vn_int = report_energies(c, global_sums, E_terms);
     return OFDFT_OK;
 }
 
@@ -1670,9 +1652,8 @@ int ofdft_dist_chi_grad(ofdft_ctx* c, const void* chi_local, const void* v_local
     hipStream_t st = (hipStream_t)stream;
     if (!c || !chi_local || !v_local || !grad_local) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
-    OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, (const real*)chi_local,
-                 (const real*)v_local, (real*)grad_local, c->npts, cscale * 2.0 * c->dV,
-                 cscale > 0.0 ? (const acc_t*)nullptr : (const acc_t*)c->d_scal, 2.0 * c->dV, mu);
+    // (cscale = 0: the device-resident scale ofdft_dist_begin left)
+    enqueue_chi_grad(c, ChiGrad{(const real*)chi_local, (const real*)v_local, (real*)grad_local, cscale, mu}, st);
     HIP_TRY(c, hipGetLastError());
     return OFDFT_OK;
 }
@@ -1835,11 +1816,10 @@ int ofdft_query(ofdft_ctx* c, int what, double* out) {
         case OFDFT_Q_XCHG_CHUNKS: *out = (double)c->xc.n; return OFDFT_OK;
         case OFDFT_Q_YFWD_FUSED: *out = (double)c->yfwd_fused; return OFDFT_OK;
         case OFDFT_Q_XPASS_KINDS: *out = (double)c->xpass_kinds; return OFDFT_OK;
-        case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27:      // phase clock of the last persistent-kernel evaluation (microseconds)
-            *out = c->h_partial[what] * 0.01;
-            return OFDFT_OK;
     }
-    return fail(c, OFDFT_EINVAL, "unknown query %d", what);
+    if (what < OFDFT_Q_RES_CLOCK || what >= OFDFT_Q_RES_CLOCK + OFDFT_Q_RES_CLOCK_COUNT) return fail(c, OFDFT_EINVAL, "unknown query %d", what);
+    *out = c->h_partial[kMirrorResClock + (what - OFDFT_Q_RES_CLOCK)] * 0.01;      // phase clock of the last persistent-kernel evaluation (microseconds)
+    return OFDFT_OK;
 }
 
 }  // extern "C"

@@ -66,9 +66,9 @@ struct ofdft_ctx {
     size_t ws_bytes = 0;
     // reduction partials (device) + pinned host mirror
     double* d_partial = nullptr;
-    double* d_reduced = nullptr;     // second-level sums [kMaxScalars]
-    double* d_scal = nullptr;        // device-resident scalars: [0] = closure scale c
-    double* h_partial = nullptr;
+    double* d_reduced = nullptr;     // second-level sums [kMaxScalars]; an evaluation's: eval_layout.h (kSum*, kSumsqSlot)
+    double* d_scal = nullptr;        // device-resident scalars [kScalLen] (eval_layout.h: kScal*)
+    double* h_partial = nullptr;     // pinned host mirror [kRedBlocks x kMaxScalars]; an evaluation's sums and extras: eval_layout.h (kMirror*)
     long long partial_rows = 0;
     // WGC tables
     double* d_wgc_coef = nullptr;   // ca[nt], cb[nt]
@@ -159,10 +159,6 @@ struct ofdft_ctx {
 
 
 namespace eng {
-
-constexpr unsigned kGgaAny = OFDFT_PBE_X | OFDFT_PBE_C | OFDFT_GGA_K;   // terms served by the gradient / divergence machinery
-constexpr int kNSums = kCombineScalars + kPbeScalars;                  // local sums of an evaluation (12)
-constexpr int kSumsqSlot = 15;                                         // d_reduced slot of sum chi^2 (closure form)
 
 inline GgaSel gga_sel(const ofdft_ctx* c) {
     return GgaSel{(c->mask & OFDFT_PBE_X) ? 1 : 0, (c->mask & OFDFT_PBE_C) ? 1 : 0, (c->mask & OFDFT_GGA_K) ? 1 : 0,
@@ -277,6 +273,8 @@ inline TermScalars term_scalars(const ofdft_ctx* c, double nel) {
 inline bool zfused_serves(const ofdft_ctx* c) {
     return c->fast && c->pipeline == 0 && c->n2 / 2 <= 512 && (!gga_needs_laplacian(c) || c->gga_split);
 }
+// where the z-fused pipeline does not serve: the x-fused pipeline (run_terms_fast) takes the evaluation, else the unfused one
+inline bool xfused_serves(const ofdft_ctx* c) { return c->fast && !c->force_unfused && !gga_needs_laplacian(c); }
 
 int fail(ofdft_ctx* c, int code, const char* fmt, ...);
 

@@ -24,7 +24,6 @@ struct ZRun {
     const real* vext = nullptr;
     real* v_out = nullptr;
     ZCombineArgs za{};
-    double pbe_sums[kPbeScalars] = {0.0, 0.0, 0.0};
     bool has_h = false, has_g = false, has_vw = false, has_wt = false, has_wgc = false;
     cplx *s_n = nullptr, *s_s = nullptr, *s_vh = nullptr, *s_g[3] = {nullptr, nullptr, nullptr};
     cplx *s_b = nullptr, *s_a = nullptr, *sw[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -108,7 +107,6 @@ int zsetup(ofdft_ctx* c) {
     r.za.inv_n = 1.0 / (double)c->npts_g;
     r.ts = term_scalars(c, r.nel);
     r.za.tc = r.ts.tc;
-    r.pbe_sums[0] = r.pbe_sums[1] = r.pbe_sums[2] = 0.0;
     r.wgc_yinv_done = false;
     r.s_g[0] = r.s_g[1] = r.s_g[2] = nullptr;
     r.s_n = r.s_s = r.s_vh = r.s_b = r.s_a = nullptr;
@@ -479,7 +477,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
                 HIP_TRY(c, hipStreamWaitEvent(sb, c->ev_c, 0));
             }
             if ((rc = launch_zi_wgc(c, r.za, vp, part2, &blocks, sb))) return rc;
-            OFDFT_REDUCE(c, sb, (const acc_t*)part2, blocks, 2, c->d_scal + 2, c->h_partial + kNSums);        // [2] energy sum, [3] this part's sum(v n); host mirror
+            OFDFT_REDUCE(c, sb, (const acc_t*)part2, blocks, 2, c->d_scal + kScalWgcSplit, c->h_partial + kMirrorWgcSplit);      // energy sum, this part's sum(v n); host mirror
             r.za.v_part = vp;
             r.wgc_split = true;
             // closure evaluations leave v in two parts: the combine kernel then has nothing to wait for on this stream
@@ -496,7 +494,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
         if ((rc = real_ws(c, "dfdn", &r.dfdn))) return rc;
         if ((rc = launch_zpbe2(c, r.ds, r.s_g[0], r.s_g[1], r.dzn, r.dfdn, r.za.inv_n, &r.pbe_blocks, st, r.lapl ? r.s_l : nullptr)))
             return rc;
-        OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kCombineScalars, c->h_partial + kCombineScalars);
+        OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kSumGga, c->h_partial + kSumGga);
         // D_b G_b in one y pass, in place (scaled like B); only G_a goes on to the x pass
         // (potential-spectrum form: G_b waits for stage 5, where its D_b joins the y-inverse of the divergence spectrum)
         if (!r.pspec && (rc = yderiv(c, r.s_g[1], r.s_g[1], (double)c->n0g, st))) return rc;
@@ -521,7 +519,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
             if (pbe_chunked && (rc = fast_axis_pass_multi<false>(c, 1, r.s_g, 3, st, x0, cx))) return rc;
         }
         // no host round trip in the middle of the evaluation: reduce on the device, read with the final sums
-        OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kCombineScalars, c->h_partial + kCombineScalars);
+        OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kSumGga, c->h_partial + kSumGga);
         for (int k = 0; k < 3; ++k) {
             if (!dx && !pbe_chunked && (rc = fast_axis_pass<false>(c, 1, r.s_g[k], st))) return rc;
             xl.push_back(r.s_g[k]);
@@ -609,21 +607,23 @@ int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
 
 // the local sums of an evaluation from the pinned host mirror (after the stream that copied them has been drained)
 // what the host has to fold when it reads the pinned mirror of an evaluation's sums (the reducing kernels write it directly)
-constexpr int kCollectWgcSplit = 1;     // the split WGC99 kernel's energy sum sits in slot kNSums
-constexpr int kCollectVnShare = 2;      // ... and its share of sum(v n) in slot kNSums + 1 (closure form: chi_grad added it on the device)
+constexpr int kCollectWgcSplit = 1;     // the split WGC99 kernel's energy sum sits in slot kMirrorWgcSplit
+constexpr int kCollectVnShare = 2;      // ... and its share of sum(v n) in slot kMirrorWgcSplitVn (closure form: chi_grad added it on the device)
 constexpr int kCollectNoGga = 4;        // no GGA term: the three GGA slots are not written
 int collect_flags(const ZRun& r, bool late_join) {
     return (r.wgc_split ? kCollectWgcSplit : 0) | (late_join ? kCollectVnShare : 0) | (r.has_g ? 0 : kCollectNoGga);
 }
+// ... of the unfused / chirp-z pipelines in their host-free form (finish_terms: defer)
+int collect_flags_unfused(const ofdft_ctx* c) { return (c->mask & kGgaAny) ? 0 : kCollectNoGga; }
 void zfused_collect(const ofdft_ctx* c, int flags, double* sums) {
     for (int i = 0; i < kNSums; ++i) sums[i] = c->h_partial[i];
     if (flags & kCollectNoGga)
-        for (int i = kCombineScalars; i < kNSums; ++i) sums[i] = 0.0;
-    if (flags & kCollectWgcSplit) sums[5] += c->h_partial[kNSums];
-    if (flags & kCollectVnShare) sums[8] += c->h_partial[kNSums + 1];
+        for (int i = kSumGga; i < kNSums; ++i) sums[i] = 0.0;
+    if (flags & kCollectWgcSplit) sums[kSumWgc] += c->h_partial[kMirrorWgcSplit];
+    if (flags & kCollectVnShare) sums[kSumVn] += c->h_partial[kMirrorWgcSplitVn];
 }
 
-// local sums: sums[0..8] combine scalars, sums[9..10] PBE x / c
+// local sums: sums[kNSums] in the layout of eval_layout.h (the combine sums, then the GGA sums)
 // `sums` == nullptr: the caller reduces the device-resident sums itself (slab-decomposed path).  `defer`: the sums are
 // copied to the pinned host mirror but nothing waits here (zfused_collect reads them after the caller's stream sync --
 // the graph-capturable form)
@@ -676,8 +676,8 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
         z1.v_out = nullptr;
         if ((rc = launch_zi_combine(c, z1, &r.combine_blocks, st))) return rc;
         OFDFT_REDUCE(c, st, c->d_partial, r.combine_blocks, kCombineScalars, c->d_reduced);
-        OFDFT_LAUNCH(c, st, "reduce", wts_weights_kernel, dim3(1), dim3(64), 0, (const acc_t*)c->d_reduced, c->d_scal + 4);
-        r.za.wts_w = c->d_scal + 4;
+        OFDFT_LAUNCH(c, st, "reduce", wts_weights_kernel, dim3(1), dim3(64), 0, (const acc_t*)c->d_reduced, c->d_scal + kScalWts);
+        r.za.wts_w = c->d_scal + kScalWts;
     }
     if (chunked) {        // y-inverse of a chunk of every result spectrum, then the combine kernel on the same x planes
         const int narr = (int)r.deferred.size();
@@ -694,21 +694,21 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
     // (host-bound sums: the reduce kernel writes the pinned mirror itself -- no copy command behind it; the stabilised
     // WT-style functional rewrites two of the sums afterwards and keeps the copy)
     OFDFT_REDUCE(c, st, c->d_partial, r.combine_blocks, kCombineScalars, c->d_reduced, (sums && !wts) ? c->h_partial : (acc_t*)nullptr);
-    if (wts) OFDFT_LAUNCH(c, st, "reduce", wts_finalize_kernel, dim3(1), dim3(64), 0, c->d_reduced, (const acc_t*)(c->d_scal + 4));
+    if (wts) OFDFT_LAUNCH(c, st, "reduce", wts_finalize_kernel, dim3(1), dim3(64), 0, c->d_reduced, (const acc_t*)(c->d_scal + kScalWts));
     if (late_join) {      // now the nonlocal chain: its share of sum(v n) joins the combine's (mu is formed from the total)
         HIP_TRY(c, hipEventRecord(c->ev_join, r.sb));
         HIP_TRY(c, hipStreamWaitEvent(st, c->ev_join, 0));
-        // host-bound sums: chi_grad and the host each add the share (slot 3 of the device scalars / its pinned mirror) themselves
+        // host-bound sums: chi_grad and the host each add the share (kScalWgcSplitVn of the device scalars / its pinned mirror) themselves
         if (!sums)
-            OFDFT_LAUNCH(c, st, "reduce", (axpy_kernel<acc_t>), dim3(1), dim3(64), 0, (const acc_t*)(c->d_scal + 3), c->d_reduced + 8,
+            OFDFT_LAUNCH(c, st, "reduce", (axpy_kernel<acc_t>), dim3(1), dim3(64), 0, (const acc_t*)(c->d_scal + kScalWgcSplitVn), c->d_reduced + kSumVn,
                          (long long)1, 1);
     }
     r.late_join = late_join && sums != nullptr;
-    if (!r.has_g) HIP_TRY(c, hipMemsetAsync(c->d_reduced + kCombineScalars, 0, kPbeScalars * sizeof(double), st));
+    if (!r.has_g) HIP_TRY(c, hipMemsetAsync(c->d_reduced + kSumGga, 0, kPbeScalars * sizeof(double), st));
     r.stage[0] = r.stage[1] = 5;
     if (!sums) {                  // the caller reduces the device-resident sums (c->d_reduced) itself
         if (r.wgc_split)          // fold in the energy sum of the split WGC99 kernel
-            OFDFT_LAUNCH(c, st, "reduce", (axpy_kernel<acc_t>), dim3(1), dim3(64), 0, (const acc_t*)(c->d_scal + 2), c->d_reduced + 5,
+            OFDFT_LAUNCH(c, st, "reduce", (axpy_kernel<acc_t>), dim3(1), dim3(64), 0, (const acc_t*)(c->d_scal + kScalWgcSplit), c->d_reduced + kSumWgc,
                          (long long)1, 1);
         return 0;
     }
@@ -764,10 +764,9 @@ int zfused_enqueue(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext,
 
 int run_terms_zfused(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext, double* E_terms, real* v_out,
                      double* vn_int, hipStream_t st) {
-    for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
     double sums[kNSums];
     if (int rc = zfused_enqueue(c, ds, nel, vext, v_out, sums, st, false)) return rc;
-    energies_from_sums(c, sums, sums + kCombineScalars, E_terms, vn_int);
+    *vn_int = report_energies(c, sums, E_terms);
     return 0;
 }
 

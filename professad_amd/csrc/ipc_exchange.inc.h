@@ -414,14 +414,13 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
     c->recv_parity[0] = c->recv_parity[1] = 0;
     HIP_TRY(c, hipMemsetAsync(s->d_err, 0, sizeof(int), st));
     // ---- sum chi^2 over all ranks -> closure scale on the device
-    const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
-    OFDFT_LAUNCH(c, st, "sum", (sum_kernel<true>), dim3(blocks), dim3(kRedThreads), 0, chi, c->npts, c->d_partial);
+    const int blocks = enqueue_sum(c, chi, true, st);
     OFDFT_REDUCE(c, st, c->d_partial, blocks, 1, c->d_reduced + kSumsqSlot);
     if (int rc = ipc_allreduce(c, 0, c->d_reduced + kSumsqSlot, 1, c->d_reduced + kSumsqSlot, st)) return rc;
-    OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal, n_electrons,
-                 c->vol / (double)c->npts_g);
+    OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal + kScalClosure,
+                 n_electrons, c->vol / (double)c->npts_g);
     ZRun& r = zrun(c);
-    r.ds = DenSrc{chi, 0.0, 1, c->d_scal};
+    r.ds = DenSrc{chi, 0.0, 1, c->d_scal + kScalClosure};
     r.nel = n_electrons;
     r.vext = (const real*)vext_local;
     r.v_out = (real*)v_work_local;
@@ -480,12 +479,13 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
         HIP_TRY(c, hipEventRecord(s->ev_cjoin[ch], s->comm[ch]));
         HIP_TRY(c, hipStreamWaitEvent(st, s->ev_cjoin[ch], 0));
     }
-    if (int rc = zstage5(c, nullptr, st, false, 2)) return rc;     // combine; local sums -> d_reduced[0..12]
-    if (int rc = ipc_allreduce(c, 1, c->d_reduced, kNSums + 1, c->d_reduced, st)) return rc;
-    OFDFT_LAUNCH(c, st, "chi_grad", chi_grad_kernel, dim3(grid_for(c->npts / 2 + 1)), dim3(256), 0, chi, (const real*)v_work_local,
-                 (real*)grad_local, c->npts, 0.0, (const acc_t*)c->d_scal, 2.0 * c->dV, 0.0, (const acc_t*)(c->d_reduced + 8), c->dV,
-                 n_electrons);
-    HIP_TRY(c, hipMemcpyAsync(c->h_partial, c->d_reduced, sizeof(double) * (kNSums + 1), hipMemcpyDeviceToHost, st));
+    if (int rc = zstage5(c, nullptr, st, false, 2)) return rc;     // combine; local sums -> d_reduced[0 .. kNSums - 1]
+    // one double more than the sums, as since the commit that added this routine (kNSums was 13 then too; only its comment said
+    // "(12)"); it carries nothing: zstage5 folds the split WGC99 sum into d_reduced[kSumWgc], nothing writes d_reduced[kNSums]
+    constexpr int kIpcReducedCount = kNSums + 1;
+    if (int rc = ipc_allreduce(c, 1, c->d_reduced, kIpcReducedCount, c->d_reduced, st)) return rc;
+    enqueue_chi_grad(c, ChiGrad{chi, (const real*)v_work_local, (real*)grad_local, 0.0, 0.0, n_electrons}, st);
+    HIP_TRY(c, hipMemcpyAsync(c->h_partial, c->d_reduced, sizeof(double) * kIpcReducedCount, hipMemcpyDeviceToHost, st));
     OFDFT_LAUNCH(c, st, "ipc_sync", ipc_abort_check_kernel, dim3(1), dim3(64), 0, ipc_abort_word(s), s->eval_id, s->d_err);
     HIP_TRY(c, hipMemcpyAsync(s->h_err, s->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     if (int rc = end_call(c, st)) return rc;
@@ -496,9 +496,6 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
         return fail(c, OFDFT_EHIP, "ipc transport: no delivery from rank %d within %.0f ms (OFDFT_OPT_IPC_WAIT_MS); evaluation %u aborted on all ranks",
                     code - 1, c->ipc_wait_ms, s->eval_id);
     }
-    double vn;
-    for (int i = 0; i < OFDFT_NTERMS; ++i) E_terms[i] = 0.0;
-    energies_from_sums(c, c->h_partial, c->h_partial + kCombineScalars, E_terms, &vn);
-    if (mu_host) *mu_host = vn / n_electrons;
+    report_energies(c, c->h_partial, E_terms, mu_host, n_electrons);
     return OFDFT_OK;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "eval_layout.h"
 #include "fastmath.h"
 #include "fft_kernels.h"
 
@@ -34,6 +35,7 @@ constexpr real kCx = (real)(-0.75L * 0.984745021842696541178973376907781690L); /
 constexpr int kRedBlocks = 1024;   // grid cap for reducing kernels (partials buffer rows)
 constexpr int kRedThreads = 256;
 constexpr int kMaxScalars = 28;    // scalars reduced by one kernel (27: the real-space stress sums)
+static_assert(kMaxScalars >= kReducedLen, "c->d_reduced holds kMaxScalars doubles");
 
 // ---- block reduction of NS scalars; thread 0 writes partial[blockIdx.x * NS + s]
 template <int NS>
@@ -851,13 +853,13 @@ struct XcLocal { real ex, vx, ec, vc; };   // energy densities (per volume) and 
 __device__ __forceinline__ XcLocal lda_point(real n, unsigned mask, const fm::Roots<real>& q) {
     XcLocal r = {0.0, 0.0, 0.0, 0.0};
     const real n13 = q.n13;
-    if (mask & (1u << 6)) {
+    if (mask & OFDFT_LDA_X) {
         r.ex = kCx * n13 * n;
         r.vx = (4.0 / 3.0) * kCx * n13;
     }
-    if (mask & ((1u << 7) | (1u << 8) | (1u << 9))) {
+    if (mask & (OFDFT_PZ_C | OFDFT_PW_C | OFDFT_CHACHIYO_C)) {
         const real rs = kCrs * q.inv13;                         // (3 / (4 pi n))^(1/3)
-        if (mask & (1u << 7)) {
+        if (mask & OFDFT_PZ_C) {
             const real gm = -0.1423, b1 = 1.0529, b2 = 0.3334, A = 0.0311, B = -0.048, C = 0.002, D = -0.0116;
             real eps, v;
             if (rs < 1.0) {
@@ -872,13 +874,13 @@ __device__ __forceinline__ XcLocal lda_point(real n, unsigned mask, const fm::Ro
             r.ec += eps * n;
             r.vc += v;
         }
-        if (mask & (1u << 8)) {
+        if (mask & OFDFT_PW_C) {
             real eps, d;
             pw92_roots(kSqrtCrs * q.y, kInvSqrtCrs * (n * q.inv13 * q.inv13 * q.y), eps, d);
             r.ec += eps * n;
             r.vc += eps - rs * kThird * d;
         }
-        if (mask & (1u << 9)) {
+        if (mask & OFDFT_CHACHIYO_C) {
             const real a = (kLn2 - 1.0) / (2.0 * kPiR * kPiR), b = 20.4562557;
             const real irs = fm::rcp(rs);
             const real arg = 1.0 + b * irs + b * irs * irs;
@@ -897,7 +899,6 @@ struct PbePoint { real fx, fc, fk, dfdn, dfdg; };
 // which GGA pieces a pass evaluates: PBE exchange / correlation, and the Pauli part of a GGA kinetic functional
 // (kkind 0: LuoKarasievTrickey F = 1/cosh(1.3 s), functionals.py:309-333; 1: Pauli-Gaussian F = exp(-mu s^2), :336-403)
 struct GgaSel { int x, c, k, kkind; real kmu, kbeta, klambda, ksigma; };
-constexpr int kPbeScalars = 3;     // energy sums of a GGA pass: exchange, correlation, kinetic
 
 // PBE x and c: energy density f, df/dn, df/d|grad n|^2 (functionals.py:1597-1618; tools_for_tests.py:155-207)
 // This is the hot pointwise function of the evaluation (the GGA mid-stage kernel is bound by fp64 vector issue): every
@@ -1010,9 +1011,9 @@ static __global__ __launch_bounds__(kRedThreads) void pbe_kernel(const real* __r
             PbePoint p = pbe_point(n[i], a * a + b * b + c * c, nk);
             real dfdl;
             pg_laplacian_point(n[i], a * a + b * b + c * c, lapn[i], sel, p, dfdl);
-            acc[0] += p.fx;
-            acc[1] += p.fc;
-            acc[2] += p.fk;
+            acc[kGgaX] += p.fx;
+            acc[kGgaC] += p.fc;
+            acc[kGgaK] += p.fk;
             dfdn[i] = p.dfdn;
             gx[i] = p.dfdg * a;
             gy[i] = p.dfdg * b;
@@ -1029,9 +1030,9 @@ static __global__ __launch_bounds__(kRedThreads) void pbe_kernel(const real* __r
                       c = reinterpret_cast<cplx*>(gz)[i];
         const PbePoint p0 = pbe_point(d.x, a.x * a.x + b.x * b.x + c.x * c.x, sel);
         const PbePoint p1 = pbe_point(d.y, a.y * a.y + b.y * b.y + c.y * c.y, sel);
-        acc[0] += p0.fx + p1.fx;
-        acc[1] += p0.fc + p1.fc;
-        acc[2] += p0.fk + p1.fk;
+        acc[kGgaX] += p0.fx + p1.fx;
+        acc[kGgaC] += p0.fc + p1.fc;
+        acc[kGgaK] += p0.fk + p1.fk;
         reinterpret_cast<cplx*>(dfdn)[i] = mkc(p0.dfdn, p1.dfdn);
         reinterpret_cast<cplx*>(gx)[i] = mkc(p0.dfdg * a.x, p1.dfdg * a.y);
         reinterpret_cast<cplx*>(gy)[i] = mkc(p0.dfdg * b.x, p1.dfdg * b.y);
@@ -1041,9 +1042,9 @@ static __global__ __launch_bounds__(kRedThreads) void pbe_kernel(const real* __r
         const long long i = npts - 1;
         const real a = gx[i], b = gy[i], c = gz[i];
         const PbePoint p = pbe_point(n[i], a * a + b * b + c * c, sel);
-        acc[0] += p.fx;
-        acc[1] += p.fc;
-        acc[2] += p.fk;
+        acc[kGgaX] += p.fx;
+        acc[kGgaC] += p.fc;
+        acc[kGgaK] += p.fk;
         dfdn[i] = p.dfdn;
         gx[i] = p.dfdg * a;
         gy[i] = p.dfdg * b;
@@ -1081,8 +1082,7 @@ struct CombineArgs {
     TermConsts tc;
     real w_tf = 1.0, w_nl = 1.0;   // weights of the TF / Wang-Teter potentials (stabilised WT-style functional, OFDFT_P_WTS_KIND)
 };
-// partial scalars: 0 ion-electron, 1 hartree, 2 tf, 3 vw, 4 wt-nl, 5 wgc-nl, 6 lda-x, 7 local-c, 8 sum(v*n), 9 vWGTF
-constexpr int kCombineScalars = 10;
+// (the combine kernels' partial sums: slots kSumIonElectron .. kSumVwgtf of eval_layout.h; a.mask is combine_mask(c))
 
 // Pauli enhancement factor of vWGTF1 / vWGTF2 and its derivative with respect to d = n / n0 (functionals.py:251-306)
 __device__ __forceinline__ void vwgtf_factor(real d, int kind, real& G, real& dG) {
@@ -1115,61 +1115,61 @@ __device__ __forceinline__ real combine_point(const CombineArgs& a, const Combin
                                                 acc_t (&acc)[kCombineScalars]) {
     const real n = p.n;
     real v = 0.0;
-    if (a.mask & 1u) {                                  // ion-electron  functionals.py:46
-        acc[0] += n * p.vext;
+    if (a.mask & OFDFT_ION_ELECTRON) {                  // ion-electron  functionals.py:46
+        acc[kSumIonElectron] += n * p.vext;
         v += p.vext;
     }
-    if (a.mask & 2u) {                                  // Hartree  functionals.py:72
-        acc[1] += 0.5 * n * p.vh;
+    if (a.mask & OFDFT_HARTREE) {                       // Hartree  functionals.py:72
+        acc[kSumHartree] += 0.5 * n * p.vh;
         v += p.vh;
     }
     const real n13 = cbrt(n);
-    if (a.mask & 4u) {                                  // TF  functionals.py:223; tools_for_tests.py:19-20
+    if (a.mask & OFDFT_TF) {                            // TF  functionals.py:223; tools_for_tests.py:19-20
         const real n23 = n13 * n13;
-        acc[2] += ctf * n23 * n;
+        acc[kSumTf] += ctf * n23 * n;
         v += a.w_tf * (5.0 / 3.0) * ctf * n23;
     }
-    if (a.mask & 8u) {                                  // vW  functionals.py:245; tools_for_tests.py:23-26
+    if (a.mask & OFDFT_VW) {                            // vW  functionals.py:245; tools_for_tests.py:23-26
         const real s = (n != 0.0) ? sqrt(n) : 0.0;
-        acc[3] += -0.5 * s * p.lap;
+        acc[kSumVw] += -0.5 * s * p.lap;
         if (n != 0.0) v += -0.5 * p.lap / s;
     }
-    if (a.mask & 16u) {                                 // WT-family NL  functionals.py:650-651; tools_for_tests.py:29-39
+    if (a.mask & OFDFT_WT_NL) {                         // WT-family NL  functionals.py:650-651; tools_for_tests.py:29-39
         const real pa1 = a.tc.wt_is_56 ? 1.0 / sqrt(n13) : pow(n, a.tc.wt_alpha - 1.0);
         const real ewt = ctf * (pa1 * n - a.tc.wt_nbar_pa) * p.cb;
         if (a.conv_a) {
             const real pb1 = pow(n, a.tc.wt_beta - 1.0);
-            acc[4] += a.tc.wt_sym ? (real)0.5 * (ewt + ctf * pb1 * n * p.cva) : ewt;
+            acc[kSumNl] += a.tc.wt_sym ? (real)0.5 * (ewt + ctf * pb1 * n * p.cva) : ewt;
             v += a.w_nl * ctf * (a.tc.wt_alpha * pa1 * p.cb + a.tc.wt_beta * pb1 * p.cva);
         } else {
-            acc[4] += ewt;
+            acc[kSumNl] += ewt;
             v += a.w_nl * ctf * 2.0 * a.tc.wt_alpha * pa1 * p.cb;
         }
     }
-    if (a.mask & 32u) {                                 // WGC99 NL  SURVEY §8a-8
+    if (a.mask & OFDFT_WGC99_NL) {                      // WGC99 NL  SURVEY §8a-8
         const real th = n - a.tc.nref;
         const real pb1 = pow(n, a.tc.wgc_beta - 1.0);
         const real pa1 = a.tc.wgc_sum_53 ? 1.0 / (n13 * pb1) : pow(n, a.tc.wgc_alpha - 1.0);
         const real P = pa1 * n, A = pb1 * n, dA = a.tc.wgc_beta * pb1;
         const real conv = p.u0 + th * p.u1 + 0.5 * th * th * p.u2;
-        acc[5] += ctf * P * conv;
+        acc[kSumWgc] += ctf * P * conv;
         v += ctf * (a.tc.wgc_alpha * pa1 * conv + P * (p.u1 + th * p.u2) + p.gA * dA + p.gB * (dA * th + A)
                     + p.gC * (0.5 * dA * th * th + A * th));
     }
-    if (a.mask & (0xFu << 6)) {                         // local XC
+    if (a.mask & kLocalXcAny) {                         // local XC
         const XcLocal x = lda_point(n, a.mask);
-        acc[6] += x.ex;
-        acc[7] += x.ec;
+        acc[kSumLdaX] += x.ex;
+        acc[kSumLocalC] += x.ec;
         v += x.vx + x.vc;
     }
-    if (a.mask & (7u << 10)) v += p.dfdn - 2.0 * p.div;   // PBE / GGA kinetic  tools_for_tests.py:168-170
-    if (a.mask & (1u << 13)) {                          // vWGTF1 / 2  functionals.py:251-306
+    if (a.mask & kGgaAny) v += p.dfdn - 2.0 * p.div;    // PBE / GGA kinetic  tools_for_tests.py:168-170
+    if (a.mask & OFDFT_VWGTF) {                         // vWGTF1 / 2  functionals.py:251-306
         real e, ve;
         vwgtf_point(n, n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e, ve);
-        acc[9] += e;
+        acc[kSumVwgtf] += e;
         v += ve;
     }
-    acc[8] += v * n;
+    acc[kSumVn] += v * n;
     return v;
 }
 
@@ -1240,17 +1240,17 @@ static __global__ __launch_bounds__(kRedThreads) void closure_scale_reduce_kerne
 // potentials from the reduced sums of a first (energy-only) combine pass ...
 static __global__ void wts_weights_kernel(const acc_t* __restrict__ sums, acc_t* __restrict__ w) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const acc_t X = sums[4] / sums[2], fx = ::exp(X);
+        const acc_t X = sums[kSumNl] / sums[kSumTf], fx = ::exp(X);
         w[0] = fx * (1.0 - X);      // f - f' X
         w[1] = fx;                  // f' / f'(0)
         w[2] = fx;
     }
 }
-// ... and the reported sums after the second pass: [2] <- T_TF f(X), [4] <- 0
+// ... and the reported sums after the second pass: kSumTf <- T_TF f(X), kSumNl <- 0
 static __global__ void wts_finalize_kernel(acc_t* __restrict__ sums, const acc_t* __restrict__ w) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        sums[2] *= w[2];
-        sums[4] = 0.0;
+        sums[kSumTf] *= w[2];
+        sums[kSumNl] = 0.0;
     }
 }
 

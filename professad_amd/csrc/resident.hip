@@ -24,7 +24,9 @@
 
 namespace ofdft {
 
-constexpr int kResSlots = 16;        // doubles per workgroup in the partials: [0..9] combine sums, [10] sum chi^2, [11..13] GGA sums
+// doubles per workgroup in the partials (ResArgs::part): the combine sums in their slots of eval_layout.h, then sum chi^2, then the GGA sums
+constexpr int kResPartSumsq = kCombineScalars, kResPartGga = kResPartSumsq + 1, kResPartUsed = kResPartGga + kPbeScalars, kResSlots = 16;
+static_assert(kResPartUsed <= kResSlots, "a workgroup's partials fit their row");
 
 constexpr int kResT = 15;            // spectrum slots: 0 chi^2 (Hartree in / out), 1 |chi| (vW), 2 chi^(2 beta), 3 chi^(2 alpha),
                                      // 4-6 grad n -> flux -> (4) divergence, 7 v_H when the chi^2 spectrum also feeds the gradient,
@@ -40,8 +42,8 @@ struct ResArgs {
     real* grad;
     cplx* T;                 // kResT spectra [slot][ky][x][kz]
     real* R;                 // kResR real-space arrays [slot][x][y][z] (unscaled transforms; flux and df/dn as computed)
-    acc_t* part;             // [N][kResSlots]: [0..9] combine sums, [10] sum chi^2, [11..13] GGA energy sums
-    acc_t* reduced;          // the context's pinned host mirror of the sums, written by the kernel: [0..12] sums, [13] barrier time-out flag
+    acc_t* part;             // [N][kResSlots]: combine sums, kResPartSumsq, kResPartGga ..
+    acc_t* reduced;          // the context's pinned host mirror of the sums, written by the kernel: the kNSums sums, kMirrorResTimeout
     unsigned* sync;          // [0] barrier counter, [1] count-out word
     unsigned epoch0;         // counter value before this launch
     unsigned* done;          // pinned host word: the last workgroup to finish stores done_target there (the host may spin on it
@@ -68,7 +70,7 @@ struct ResArgs {
     real inv_n, lind_p0, lind_p1;
 };
 
-// -DOFDFT_RES_CLOCK=1: workgroup 0 writes a phase clock into the host mirror (ofdft_query 16..27, tools/resident_probe.py);
+// -DOFDFT_RES_CLOCK=1: workgroup 0 writes a phase clock into the host mirror (ofdft_query OFDFT_Q_RES_CLOCK .., tools/resident_probe.py);
 // off by default -- the stores cross the bus and every barrier waits for them
 #ifndef OFDFT_RES_CLOCK
 #define OFDFT_RES_CLOCK 0
@@ -213,7 +215,7 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
     const int bid = (int)blockIdx.x;
     extern __shared__ __attribute__((aligned(16))) real lds[];
     __shared__ acc_t red[C::WAVES][kCombineScalars];
-    __shared__ acc_t tot[16];
+    __shared__ acc_t tot[kResSlots];
     __shared__ acc_t stage[16 * 64];
     real* rowbuf = lds;
     cplx* twM = reinterpret_cast<cplx*>(lds + C::RB);
@@ -225,11 +227,11 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
     real* zmine = rowbuf + (zslot < C::ROWS ? zslot : 0) * C::RSZ;
     const int ll = lane % C::LPWV, lj = lane / C::LPWV;
     int timed_out = 0;
-    // phase clock of workgroup 0 (100 MHz ticks since kernel entry) -> reduced[16..22]
+    // phase clock of workgroup 0 (100 MHz ticks since kernel entry) -> reduced[kMirrorResClock ..]
     const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
     auto stamp = [&](int i) {
 #if OFDFT_RES_CLOCK
-        if (bid == 0 && tid == 0) A.reduced[16 + i] = (acc_t)(__builtin_amdgcn_s_memrealtime() - clk0);
+        if (bid == 0 && tid == 0) A.reduced[kMirrorResClock + i] = (acc_t)(__builtin_amdgcn_s_memrealtime() - clk0);
 #endif
     };
     (void)clk0;
@@ -278,7 +280,7 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
                 ld[k] = A.T[(((long long)slots[sI] * N + ky) * N + x) * NZH + kz];
             }
         }
-        if (first_group && tid < N) stage[tid] = __builtin_nontemporal_load(A.part + tid * kResSlots + 10);
+        if (first_group && tid < N) stage[tid] = __builtin_nontemporal_load(A.part + tid * kResSlots + kResPartSumsq);
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int i = tid + k * T;
@@ -334,12 +336,12 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
         if (tid == 0) {
             acc_t t = 0.0;
             for (int w = 0; w < C::WAVES; ++w) t += red[w][0];
-            A.part[bid * kResSlots + 10] = t;
+            A.part[bid * kResSlots + kResPartSumsq] = t;
         }
         if (A.need_c) {       // the WGC99 inputs are not homogeneous in the closure scale (theta = n - n_ref): reduce sum chi^2 first
             barrier();
-            res_totals<N>(A.part, 10, 1, tot + kCombineScalars, stage);
-            cscale = A.from_den ? (acc_t)1.0 : A.nel / (tot[kCombineScalars] * A.vol_over_npts);       // system.py:833-834
+            res_totals<N>(A.part, kResPartSumsq, 1, tot + kResPartSumsq, stage);
+            cscale = A.from_den ? (acc_t)1.0 : A.nel / (tot[kResPartSumsq] * A.vol_over_npts);       // system.py:833-834
             have_c = true;
         }
         const real cs0 = (real)cscale, wal = A.ca.tc.wgc_alpha, wbe = A.ca.tc.wgc_beta, nref = A.ca.tc.nref;
@@ -471,8 +473,8 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
     // ------------------------------------------------------------------ phase C
     // the loads that cross XCDs -- this plane of the first group's spectra and the partial sums of chi^2 -- go out together
     if (A.nout == 0 && !have_c) {                         // purely local term set: nothing to transform back
-        res_totals<N>(A.part, 10, 1, tot + kCombineScalars, stage);
-        cscale = A.nel / (tot[kCombineScalars] * A.vol_over_npts);
+        res_totals<N>(A.part, kResPartSumsq, 1, tot + kResPartSumsq, stage);
+        cscale = A.nel / (tot[kResPartSumsq] * A.vol_over_npts);
     }
     for (int g0 = 0; g0 < A.nout; g0 += AG) {
         const int ns = (A.nout - g0) < AG ? (A.nout - g0) : AG;
@@ -503,15 +505,15 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
             const real a0 = fg * gx.x, b0 = fg * gy.x, c0 = fg * gz.x, a1 = fg * gx.y, b1 = fg * gy.y, c1 = fg * gz.y;
             const PbePoint p0 = pbe_point(A.from_den ? c.x : cs * c.x * c.x, a0 * a0 + b0 * b0 + c0 * c0, A.sel);
             const PbePoint p1 = pbe_point(A.from_den ? c.y : cs * c.y * c.y, a1 * a1 + b1 * b1 + c1 * c1, A.sel);
-            pacc[0] += p0.fx + p1.fx;
-            pacc[1] += p0.fc + p1.fc;
-            pacc[2] += p0.fk + p1.fk;
+            pacc[kGgaX] += p0.fx + p1.fx;
+            pacc[kGgaC] += p0.fc + p1.fc;
+            pacc[kGgaK] += p0.fk + p1.fk;
             rp[8 * AS + i] = mkc(p0.dfdn, p1.dfdn);
             rp[4 * AS + i] = mkc(p0.dfdg * a0, p1.dfdg * a1);
             rp[5 * AS + i] = mkc(p0.dfdg * b0, p1.dfdg * b1);
             rp[6 * AS + i] = mkc(p0.dfdg * c0, p1.dfdg * c1);
         }
-        res_block_sums<kPbeScalars>(pacc, lds, stage, A.part + bid * kResSlots + 11);
+        res_block_sums<kPbeScalars>(pacc, lds, stage, A.part + bid * kResSlots + kResPartGga);
         stage_tables();                                   // the ordered sums borrowed the dynamic LDS, twiddle tables included
         __syncthreads();
         // flux components of this plane -> z- and y-forward -> T[4..6]
@@ -569,7 +571,7 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
         const real f0 = A.inv_n * cs, f1 = A.inv_n * sqrt(cs);
         const real f2 = A.act[2] ? A.inv_n * (real)::pow((double)cs, (double)be) : (real)0.0;
         const real f3 = A.act[3] ? A.inv_n * (real)::pow((double)cs, (double)al) : (real)0.0;
-        const bool has_h = A.ca.mask & 2u;
+        const bool has_h = A.ca.mask & OFDFT_HARTREE;
         acc_t acc[kCombineScalars];
 #pragma unroll
         for (int s = 0; s < kCombineScalars; ++s) acc[s] = 0.0;
@@ -616,18 +618,18 @@ __global__ __launch_bounds__(kResThreads, 1) void resident_closure_kernel(ResArg
     stamp(5);
 
     // ------------------------------------------------------------------ phase D: mu and chi.grad
-    res_totals<N>(A.part, 0, 14, tot, stage);
+    res_totals<N>(A.part, 0, kResPartUsed, tot, stage);
     if (bid == 0) {          // (a workgroup that never arrives stalls every barrier, this one's included: one flag suffices)
         if (tid < kCombineScalars) A.reduced[tid] = tot[tid];
-        else if (tid < 13) A.reduced[tid] = A.gga ? tot[tid + 1] : 0.0;        // GGA energy sums (partials [11..13])
+        else if (tid < kNSums) A.reduced[tid] = A.gga ? tot[tid - kSumGga + kResPartGga] : 0.0;      // GGA energy sums
         if (tid == 0) {       // (sync[2]: set by any workgroup whose barrier ran out of patience; read after the last barrier)
             const unsigned any = __hip_atomic_load(A.sync + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            A.reduced[13] = (timed_out || any) ? 1.0 : 0.0;
+            A.reduced[kMirrorResTimeout] = (timed_out || any) ? 1.0 : 0.0;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");     // system scope: the sums are in host memory before this workgroup counts out
     }
     if (A.grad) {
-        const real mu = (real)((tot[8] * A.dV) / A.nel);                                        // system.py:851
+        const real mu = (real)((tot[kSumVn] * A.dV) / A.nel);                                        // system.py:851
         const real c2dV = (real)(cscale * (2.0 * A.dV));                                        // system.py:836-837,853
         const cplx* vp = reinterpret_cast<const cplx*>(A.v) + po;
         cplx* gp = reinterpret_cast<cplx*>(A.grad) + po;

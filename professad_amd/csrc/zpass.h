@@ -594,9 +594,9 @@ __global__ __launch_bounds__(256, (z_waves<M, E>(OFDFT_ZPBE_WAVES))) void zpbe_k
             p0 = pbe_point(ds(n[q].x), ax * ax + bx * bx + cx * cx, sel);
             p1 = pbe_point(ds(n[q].y), ay * ay + by * by + cy * cy, sel);
         }
-        acc[0] += p0.fx + p1.fx;
-        acc[1] += p0.fc + p1.fc;
-        acc[2] += p0.fk + p1.fk;
+        acc[kGgaX] += p0.fx + p1.fx;
+        acc[kGgaC] += p0.fc + p1.fc;
+        acc[kGgaK] += p0.fk + p1.fk;
         d[q] = mkc(p0.dfdn, p1.dfdn);
         a[q] = mkc(p0.dfdg * ax, p1.dfdg * ay);
         b[q] = mkc(p0.dfdg * bx, p1.dfdg * by);
@@ -705,9 +705,9 @@ __global__ __launch_bounds__(256, (z_waves<M, E, OFDFT_Z_EMAX_PBE>(2))) void zpb
             p0 = pbe_point(ds(n[q].x), gx0 * gx0 + gy0 * gy0 + gz0 * gz0, sel);
             p1 = pbe_point(ds(n[q].y), gx1 * gx1 + gy1 * gy1 + gz1 * gz1, sel);
         }
-        acc[0] += p0.fx + p1.fx;
-        acc[1] += p0.fc + p1.fc;
-        acc[2] += p0.fk + p1.fk;
+        acc[kGgaX] += p0.fx + p1.fx;
+        acc[kGgaC] += p0.fc + p1.fc;
+        acc[kGgaK] += p0.fk + p1.fk;
         d[q] = mkc(p0.dfdn, p1.dfdn);
         // contravariant components of the flux F = df/dg grad n:  G_axis = sum_j b[axis][j] F_j
         if (diag) {
@@ -914,9 +914,9 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
     // cap -- it lifted the kernel from 0.33 to 0.39 of the peak, but a fourth wave per SIMD without it does better still, 0.43 -> 0.47:
     // OFDFT_Z_PIPE_BIG_F32 / OFDFT_ZI_WAVES_BIG_F32)
     constexpr bool PIPE = OFDFT_Z_PREFETCH && !WGC_INLINE && (M < 512 || (sizeof(real) == 4 && OFDFT_Z_PIPE_BIG_F32));
-    const bool gga = (a.mask & (7u << 10)) != 0;
-    const cplx* chain[6] = {(a.mask & 2u) ? a.vh : nullptr,  (a.mask & 8u) ? a.lap : nullptr, (a.mask & 16u) ? a.conv_b : nullptr,
-                            (a.mask & 16u) ? a.conv_a : nullptr, gga ? a.div : nullptr, gga ? a.div2 : nullptr};
+    const bool gga = (a.mask & kGgaAny) != 0;
+    const cplx* chain[6] = {(a.mask & OFDFT_HARTREE) ? a.vh : nullptr,  (a.mask & OFDFT_VW) ? a.lap : nullptr, (a.mask & OFDFT_WT_NL) ? a.conv_b : nullptr,
+                            (a.mask & OFDFT_WT_NL) ? a.conv_a : nullptr, gga ? a.div : nullptr, gga ? a.div2 : nullptr};
     cplx nx[PIPE ? E : 1];
     real nyq_nx = 0.0;
     auto request_after = [&](auto ic) {       // rows of the first present spectrum after section I -> nx
@@ -940,7 +940,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
     };
     request_after(std::integral_constant<int, -1>{});
-    if ((a.mask & 2u) && a.vh) {                         // Hartree  functionals.py:72  (vh == null: in div, see eh_part)
+    if ((a.mask & OFDFT_HARTREE) && a.vh) {              // Hartree  functionals.py:72  (vh == null: in div, see eh_part)
         take_row(std::integral_constant<int, 0>{}, a.vh);
         real e = 0.0;
 #pragma unroll
@@ -952,7 +952,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
         park[kParkH * 256] = e;
     }
-    if (a.mask & 8u) {                                   // vW  functionals.py:245; tools_for_tests.py:23-26
+    if (a.mask & OFDFT_VW) {                             // vW  functionals.py:245; tools_for_tests.py:23-26
         take_row(std::integral_constant<int, 1>{}, a.lap);
         real e = 0.0;
 #pragma unroll
@@ -968,7 +968,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
         park[kParkVw * 256] = e;
     }
-    if (a.mask & 16u) {                                  // WT family  functionals.py:650-651; tools_for_tests.py:29-39
+    if (a.mask & OFDFT_WT_NL) {                          // WT family  functionals.py:650-651; tools_for_tests.py:29-39
         take_row(std::integral_constant<int, 2>{}, a.conv_b);
         cplx pa1[E];
         real e = 0.0;
@@ -1004,7 +1004,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
             }
         }
     }
-    if (a.mask & 32u) {                                  // WGC99
+    if (a.mask & OFDFT_WGC99_NL) {                       // WGC99
         if (WGC_INLINE) {
             park[kParkWgc * 256] = wgc_row_section<M, E>(n, vacc, w, z, a, g, twM, twN, sc, ctf);
         } else if (!a.v_part_deferred) {                 // computed by zi_wgc_kernel on the nonlocal chain's stream
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
             }
         }
     }
-    if (a.mask & (7u << 10)) {                           // PBE / GGA kinetic: v += df/dn - 2 div  (tools_for_tests.py:168-170)
+    if (a.mask & kGgaAny) {                              // PBE / GGA kinetic: v += df/dn - 2 div  (tools_for_tests.py:168-170)
         take_row(std::integral_constant<int, 4>{}, a.div);
         cplx d[E];
         z_load_real<M, E, true>(d, z, a.dfdn);
@@ -1035,7 +1035,7 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         }
     }
     // ---- local terms and the sum of v n
-    if (a.mask & 1u) {
+    if (a.mask & OFDFT_ION_ELECTRON) {
         cplx ve[E];
         z_load_real<M, E, true>(ve, z, a.vext);
         real e = 0.0;
@@ -1056,41 +1056,41 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
         if (!(PL::slot_out(q) && PL::lane_out(z.j, q))) continue;      // (rows with factors 3 / 5: slots without a grid point)
         // (the local sections of a point share one root in either form)
         const fm::Roots<real> rt0 = fm::roots_from_y(n[q].x, root_y(q, 0)), rt1 = fm::roots_from_y(n[q].y, root_y(q, 1));
-        if (a.mask & 4u) {                               // TF  functionals.py:223
+        if (a.mask & OFDFT_TF) {                         // TF  functionals.py:223
             const real c0 = rt0.n13, c1 = rt1.n13;
-            acc[2] += ctf * (c0 * c0 * n[q].x + c1 * c1 * n[q].y);
+            acc[kSumTf] += ctf * (c0 * c0 * n[q].x + c1 * c1 * n[q].y);
             vacc[q].x += w_tf * (5.0 / 3.0) * ctf * c0 * c0;
             vacc[q].y += w_tf * (5.0 / 3.0) * ctf * c1 * c1;
         }
-        if (a.mask & (1u << 13)) {                       // vWGTF1 / 2  functionals.py:251-306
+        if (a.mask & OFDFT_VWGTF) {                      // vWGTF1 / 2  functionals.py:251-306
             real e0, v0, e1, v1;
             vwgtf_point(n[q].x, rt0.n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e0, v0);
             vwgtf_point(n[q].y, rt1.n13, ctf, a.tc.gtf_inv_n0, a.tc.gtf_kind, e1, v1);
-            acc[9] += e0 + e1;
+            acc[kSumVwgtf] += e0 + e1;
             vacc[q].x += v0;
             vacc[q].y += v1;
         }
-        if (a.mask & (0xFu << 6)) {                      // local XC
+        if (a.mask & kLocalXcAny) {                      // local XC
             const XcLocal x0 = lda_point(n[q].x, a.mask, rt0), x1 = lda_point(n[q].y, a.mask, rt1);
-            acc[6] += x0.ex + x1.ex;
-            acc[7] += x0.ec + x1.ec;
+            acc[kSumLdaX] += x0.ex + x1.ex;
+            acc[kSumLocalC] += x0.ec + x1.ec;
             vacc[q].x += x0.vx + x0.vc;
             vacc[q].y += x1.vx + x1.vc;
         }
-        acc[8] += vacc[q].x * n[q].x + vacc[q].y * n[q].y;
+        acc[kSumVn] += vacc[q].x * n[q].x + vacc[q].y * n[q].y;
     }
-    acc[0] = park[kParkIe * 256];
-    acc[1] = park[kParkH * 256];
-    acc[3] = park[kParkVw * 256];
-    acc[4] = park[kParkWt * 256];
-    acc[5] = park[kParkWgc * 256];
+    acc[kSumIonElectron] = park[kParkIe * 256];
+    acc[kSumHartree] = park[kParkH * 256];
+    acc[kSumVw] = park[kParkVw * 256];
+    acc[kSumNl] = park[kParkWt * 256];
+    acc[kSumWgc] = park[kParkWgc * 256];
     if (!z.valid) {
 #pragma unroll
         for (int s = 0; s < kCombineScalars; ++s) acc[s] = 0.0;
     }
     if (a.eh_part && g.blk0 + blockIdx.x == 0) {
         // E_H from the divergence x pass: its partials join the Hartree slot of the first workgroup (the same order in an x-chunked loop)
-        for (long long i = threadIdx.x; i < a.eh_rows; i += blockDim.x) acc[1] += a.eh_part[i];
+        for (long long i = threadIdx.x; i < a.eh_rows; i += blockDim.x) acc[kSumHartree] += a.eh_part[i];
     }
     if (a.v_out) z_store_real<M, E>(vacc, z, a.v_out);
     block_reduce_store<kCombineScalars>(acc, partial + (long long)g.blk0 * kCombineScalars);
@@ -1117,13 +1117,15 @@ __global__ __launch_bounds__(256, (z_waves<M, E>(OFDFT_ZIWGC_WAVES))) void zi_wg
         n[q] = (z.valid && PL::slot_out(q) && PL::lane_out(z.j, q)) ? mkc(a.ds(n[q].x), a.ds(n[q].y)) : mkc(1.0, 1.0);
         vacc[q] = mkc(0.0, 0.0);
     }
-    acc_t acc[2];         // the WGC99 energy integrand, and this part's share of sum(v n) (for mu when the parts are merged later)
-    acc[0] = wgc_row_section<M, E>(n, vacc, w, z, a, g, twM, twN, a.inv_n, ctf);
-    acc[1] = 0.0;
+    // the WGC99 energy integrand, and this part's share of sum(v n) (for mu when the parts are merged later): -> kScalWgcSplit[Vn], kMirrorWgcSplit[Vn]
+    constexpr int kE = 0, kVn = 1;
+    acc_t acc[2];
+    acc[kE] = wgc_row_section<M, E>(n, vacc, w, z, a, g, twM, twN, a.inv_n, ctf);
+    acc[kVn] = 0.0;
 #pragma unroll
     for (int q = 0; q < E; ++q)
-        if (PL::slot_out(q) && PL::lane_out(z.j, q)) acc[1] += vacc[q].x * n[q].x + vacc[q].y * n[q].y;
-    if (!z.valid) acc[0] = acc[1] = 0.0;
+        if (PL::slot_out(q) && PL::lane_out(z.j, q)) acc[kVn] += vacc[q].x * n[q].x + vacc[q].y * n[q].y;
+    if (!z.valid) acc[kE] = acc[kVn] = 0.0;
     z_store_real<M, E>(vacc, z, v_part);
     block_reduce_store<2>(acc, partial + (long long)g.blk0 * 2);
 }

@@ -24,8 +24,8 @@ import torch.distributed as dist
 from . import _native as N
 from .engine import Engine
 
-NSUMS = 13   # 10 combine scalars + GGA sums (PBE exchange, correlation, kinetic GGA)
-SUMSQ_SLOT = 15   # slot of sum chi^2 in the context's device-resident scalar block (16 doubles)
+NSUMS = N.NSUMS                 # local sums of an evaluation (include/ofdft_hip.h: OFDFT_NSUMS)
+SUMSQ_SLOT = N.SCALAR_SUMSQ     # slot of sum chi^2 in the context's device-resident scalar block (N.NSCALARS doubles)
 
 
 class SlabPlan:
@@ -208,8 +208,8 @@ class HipStages(Engine):
         super().__init__(shape, device, nranks=nranks, rank=rank, dtype=dtype)
         p = C.c_void_p(0)
         self._check(self.lib.ofdft_dist_scalars(self._ctx, C.byref(p)), 'ofdft_dist_scalars')
-        # 16 device-resident doubles owned by the context: [0..12] local sums of an evaluation, [15] sum chi^2
-        self.device_scalars = torch.as_tensor(_RawDeviceBuffer(p.value, 16, '<f8'), device=self.device)
+        # the device-resident doubles owned by the context: [0:NSUMS] local sums of an evaluation, [SUMSQ_SLOT] sum chi^2
+        self.device_scalars = torch.as_tensor(_RawDeviceBuffer(p.value, N.NSCALARS, '<f8'), device=self.device)
         self._xbuf = {}
 
     def enable_collectives(self, comm):
@@ -304,7 +304,7 @@ class HipStages(Engine):
         return N.per_term(E, 0), mu.value, out        # (slab contexts serve the first NTERMS_ALWAYS terms only)
 
     def sumsq(self, x, square=True, on_device=False):
-        """local sum of x^2 (or x): returned as a float, or left in device_scalars[15] without a host sync"""
+        """local sum of x^2 (or x): returned as a float, or left in device_scalars[SUMSQ_SLOT] without a host sync"""
         x = self._grid_tensor(x, 'x')
         out = C.c_double(0.0)
         self._check(self.lib.ofdft_dist_sumsq(self._ctx, C.c_void_p(x.data_ptr()), 1 if square else 0,
@@ -313,7 +313,7 @@ class HipStages(Engine):
 
     def begin(self, src, from_chi, cscale, nel, vext, v_out):
         """from_chi: False = src is the density, True = chi with the host scale `cscale`, 2 = chi with the scale formed
-        on the device from the all-reduced device_scalars[15]"""
+        on the device from the all-reduced device_scalars[SUMSQ_SLOT]"""
         self._keep = (src, vext, v_out)          # keep the tensors alive for the duration of the evaluation
         self._check(self.lib.ofdft_dist_begin(self._ctx, C.c_void_p(src.data_ptr()), int(from_chi), float(cscale),
                                               float(nel), C.c_void_p(vext.data_ptr() if vext is not None else 0),
@@ -364,7 +364,7 @@ class HipStages(Engine):
         return ex
 
     def finish(self, on_device=False):
-        """the 11 local sums: as a numpy vector, or left in device_scalars[0:13] without a host sync"""
+        """the NSUMS local sums: as a numpy vector, or left in device_scalars[0:NSUMS] without a host sync"""
         if on_device:
             self._check(self.lib.ofdft_dist_finish(self._ctx, None, self._stream()), 'ofdft_dist_finish')
             return None
@@ -437,7 +437,7 @@ def run_closure(stages, comm, chi, n_elec, vext, vol, npts_global, new_like):
     sc = getattr(stages, 'device_scalars', None)
     if sc is not None:
         # device-resident scalars: sum chi^2 and the closure scale never visit the host; the only host
-        # synchronisation of the evaluation is the copy of the 11 all-reduced sums
+        # synchronisation of the evaluation is the copy of the NSUMS all-reduced sums
         stages.sumsq(chi, True, on_device=True)
         comm.all_reduce_dev(sc[SUMSQ_SLOT:SUMSQ_SLOT + 1])
         v = new_like(chi)

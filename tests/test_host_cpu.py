@@ -33,13 +33,24 @@ def test_header_constants_match_python_mirror():
     queries = {nm: int(v) for nm, v in re.findall(r'#define OFDFT_Q_([A-Z0-9_]+)\s+(\d+)', header)}
     for nm, v in queries.items():
         assert getattr(N, 'Q_' + nm) == v, nm
-    assert len(set(queries.values())) == len(queries)
+    selectors = {nm: v for nm, v in queries.items() if nm != 'RES_CLOCK_COUNT'}      # (a count, not a selector)
+    assert len(set(selectors.values())) == len(selectors)
+    assert not set(range(N.Q_RES_CLOCK + 1, N.Q_RES_CLOCK + N.Q_RES_CLOCK_COUNT)) & set(selectors.values())
     for nm in ('GROUP', 'WAVE', 'CROSS1', 'CROSS2', 'CHIRPZ'):
         assert getattr(N, 'XPASS_' + nm) == 1 << int(bits['XPASS_' + nm]), nm
     options = {nm: int(v) for nm, v in re.findall(r'#define OFDFT_OPT_([A-Z0-9_]+)\s+(\d+)', header)}
     for nm in dir(N):
         if nm.startswith('OPT_'):
             assert options[nm[4:]] == getattr(N, nm), nm
+    for nm, v in options.items():      # ... and no option of the header without its Python name
+        assert getattr(N, 'OPT_' + nm) == v, nm
+    # the published part of an evaluation's scalar layout (csrc/eval_layout.h holds the whole of it and asserts the same numbers)
+    for nm in ('NSUMS', 'NSCALARS', 'SCALAR_SUMSQ', 'NPARAMS'):
+        assert int(re.search(r'#define OFDFT_%s\s+(\d+)' % nm, header).group(1)) == getattr(N, nm), nm
+    assert N.SCALAR_SUMSQ < N.NSCALARS and N.NSUMS <= N.SCALAR_SUMSQ
+    assert queries['RES_CLOCK'] == N.Q_RES_CLOCK and queries['RES_CLOCK_COUNT'] == N.Q_RES_CLOCK_COUNT
+    from professad_amd import distributed
+    assert distributed.NSUMS == N.NSUMS and distributed.SUMSQ_SLOT == N.SCALAR_SUMSQ
 
 
 def test_error_paths_without_gpu():

@@ -34,4 +34,4 @@ for _ in range(reps):
 torch.cuda.synchronize()
 print(json.dumps({'grid': n, 'cfg': cfg, 'mode': mode, 'ms_per_eval': round((time.perf_counter() - t0) / reps * 1e3, 4),
                   'resident_evals': int(eng.query(N.Q_RESIDENT_EVALS)),
-                  'phase_clock_us': [round(eng.query(16 + i), 2) for i in range(12)]}))
+                  'phase_clock_us': [round(eng.query(N.Q_RES_CLOCK + i), 2) for i in range(N.Q_RES_CLOCK_COUNT)]}))
