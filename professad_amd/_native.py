@@ -44,7 +44,7 @@ Q_XPASS_KINDS = 11
 Q_RES_CLOCK, Q_RES_CLOCK_COUNT = 16, 12      # phase clock of the persistent kernel (libraries built with -DOFDFT_RES_CLOCK=1)
 # bits of ofdft_query(Q_XPASS_KINDS): the fused x-pass kernel families of the last energy call
 XPASS_GROUP, XPASS_WAVE, XPASS_CROSS1, XPASS_CROSS2, XPASS_CHIRPZ = 1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4
-OPT_PIPELINE, OPT_SIDE_STREAM, OPT_XCHUNKS, OPT_XCHUNK_MASK, OPT_SPLIT_COMBINE = 0, 1, 2, 3, 4
+OPT_PIPELINE, OPT_SIDE_STREAM, OPT_SPLIT_COMBINE = 0, 1, 4
 OPT_BLUESTEIN = 5
 OPT_GGA_SPLIT = 6
 OPT_GRAPH = 7

@@ -1512,7 +1512,6 @@ int ofdft_dist_begin(ofdft_ctx* c, const void* src_local, int from_chi, double c
     c->recv_parity[0] = c->recv_parity[1] = 0;
     r.step[0] = r.step[1] = 0;
     r.step_chunk[0] = r.step_chunk[1] = 0;
-    r.deferred.clear();
     r.forked = false;
     r.closure = false;
     r.vpart_deferred = false;
@@ -1709,10 +1708,6 @@ int ofdft_set_option(ofdft_ctx* c, int option, double value) {
         case OFDFT_OPT_SIDE_STREAM:
             c->use_side_stream = value != 0.0;
             return OFDFT_OK;
-        case OFDFT_OPT_XCHUNKS:
-            if (value < 0.0 || value > 64.0) return fail(c, OFDFT_EINVAL, "x chunks must be 0 (automatic) or 1..64");
-            c->xchunks = (int)value;
-            return OFDFT_OK;
         case OFDFT_OPT_BLUESTEIN:
             c->use_bluestein = value != 0.0;
             return OFDFT_OK;
@@ -1732,9 +1727,6 @@ int ofdft_set_option(ofdft_ctx* c, int option, double value) {
         case OFDFT_OPT_SPLIT_COMBINE:
             c->split_combine = value != 0.0;
             c->defer_vpart = value != 1.0;
-            return OFDFT_OK;
-        case OFDFT_OPT_XCHUNK_MASK:
-            c->xchunk_mask = (int)value & 31;
             return OFDFT_OK;
         case OFDFT_OPT_MIXED_RADIX:
             if (c->nranks > 1 && value == 0.0 && !all_pow2(c))

@@ -87,7 +87,7 @@ struct ofdft_ctx {
     int fft_count = 0, launch_count = 0;
     int xpass_blocks = 0;       // workgroups of the last fused x pass launched (rows of its energy partials, if its mix has any)
     unsigned xpass_kinds = 0;   // OFDFT_XPASS_* bits of the fused x-pass kernels the last energy call launched (OFDFT_Q_XPASS_KINDS)
-    double ypass_count = 0.0;   // whole-spectrum y passes executed (fractions for x- / kz-range launches)
+    double ypass_count = 0.0;   // whole-spectrum y passes executed (fractions for the kz chunks of the exchange)
     float last_ms = 0.f;
     bool ms_pending = false;    // ev1 recorded without a host wait (device-resident dist finish): elapsed time read on demand
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
@@ -105,10 +105,7 @@ struct ofdft_ctx {
                             // 8 256 waves -- exactly what the chip holds at once -- so alone every workgroup loads, transforms and stores in lock
                             // step; three spectra per launch stagger: the batched passes 50 -> 46.5 us (fp64), 34 -> 27 us (fp32) per spectrum,
                             // evaluation neutral in fp64 (three alternations within 0.3 %), +0.9 % in fp32
-    int xchunk_mask = 2;    // which stage pairs are chunked: 1 density forward, 2 nonlocal forward, 4 PBE loop, 8 combine loop
     int use_xwave = 1;   // fused x pass: 1 = wave-local kernel (xwave.h) where it measured faster (passes over >= 3 spectra, x extents <= 512), 2 = wherever it exists, 0 = group-parallel kernel only
-    int xchunks = 1;    // 1 (default since the round-2 kernels: -0.7 % at 256^3, neutral at 128^3 / 512^3): off; 0: automatic (about 100 MB of
-                        // spectra per chunk); > 1: z kernels and the y passes next to them walk the grid in x chunks (Infinity-Cache reuse)
     // optional per-kernel-class profiling (HIP events around every launch)
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;
@@ -422,8 +419,7 @@ int global_sums(ofdft_ctx* c, double* v, int n);
 // ---- line-transform drivers (lines.hip)
 void pass_maps(const ofdft_ctx* c, int axis, LineMap& main, LineMap& rem);
 template <bool INV>
-int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, hipStream_t st, int x0 = 0, int cx = 0,
-                         int kb0 = 0, int kb1 = 0);
+int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, hipStream_t st);
 template <bool INV> int fast_axis_pass(ofdft_ctx* c, int axis, cplx* spec, hipStream_t st);
 // xk: chunk of the exchange layout (-1: every chunk, one launch each; kWholeXchg: the unchunked layout)
 template <bool INV> int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStream_t st, int xk = -1);
@@ -453,7 +449,6 @@ int inv_yz(ofdft_ctx* c, cplx* spec, real* out, double scale, hipStream_t st);
 // element strides along x of the inputs, the outputs and the k-point tables
 struct XfLayout {
     long long se_in = 0, se_out = 0, tse = 0;
-    int kb0 = 0, kb1 = 0;          // one GPU: kb1 > kb0 = kz blocks [kb0, kb1) of the full arrays only
     int xnb = -1, xnrem = 0;       // exchange buffers: kz blocks / remainder planes of the chunk the pointers address (xnb < 0: all of c->xg)
     int kz0 = 0;                   // ... and the kz of its first block
 };
@@ -468,10 +463,8 @@ template <int NIN, class Mix>
 int xfused_energy(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const char* nm);
 bool xfused_energy_serves(const ofdft_ctx* c, int nin);
 
-// ---- launchers of the fused z kernels (zfused.hip).  (chunk, nchunks): the launch covers that share of the rows, i.e. the
-// x planes [chunk, chunk + 1) * n0 / nchunks (x-chunked pipeline); partial sums land where a full launch would put them.
-int launch_zf_density(ofdft_ctx* c, const DenSrc& ds, cplx* out_n, cplx* out_s, hipStream_t st, int chunk = 0, int nchunks = 1,
-                      real* dzn = nullptr);
+// ---- launchers of the fused z kernels (zfused.hip)
+int launch_zf_density(ofdft_ctx* c, const DenSrc& ds, cplx* out_n, cplx* out_s, hipStream_t st, real* dzn = nullptr);
 // WGC99 kernel tables (w0, K1, K2, K3 interleaved per k-point, spectrum order) for round(N_e) = nel_rounded; *nref_out = kappa n0
 int ensure_wgc_tables(ofdft_ctx* c, long long nel_rounded, hipStream_t st, double* nref_out);
 // the tables as the mix functor of the fused x passes sees them, from element `off` (a kz chunk of a chunk-major table)
@@ -497,12 +490,12 @@ bool resident_serves(const ofdft_ctx* c);
 constexpr int kResidentDeclined = 1;       // resident_closure: not an error -- the caller takes the graph / staged path instead
 // chi -> (sums, v, chi.grad) -- or, with from_den, density -> (sums, v) -- by the persistent small-grid kernel (resident.hip)
 int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel, real* v, real* grad, hipStream_t st, bool from_den = false);
-int launch_zf_powers(ofdft_ctx* c, const DenSrc& ds, const PowersArgs& pa, hipStream_t st, int chunk = 0, int nchunks = 1);
+int launch_zf_powers(ofdft_ctx* c, const DenSrc& ds, const PowersArgs& pa, hipStream_t st);
 int launch_zpbe(ofdft_ctx* c, const DenSrc& ds, cplx* gx, cplx* gy, cplx* gz, real* dfdn, double inv_n, int* blocks_out,
-                hipStream_t st, int chunk = 0, int nchunks = 1);
+                hipStream_t st);
 int launch_zpbe2(ofdft_ctx* c, const DenSrc& ds, cplx* A, cplx* B, const real* dzn, real* dfdn, double inv_n, int* blocks_out,
                  hipStream_t st, cplx* L = nullptr);
-int launch_zi_combine(ofdft_ctx* c, const ZCombineArgs& a, int* blocks_out, hipStream_t st, int chunk = 0, int nchunks = 1);
+int launch_zi_combine(ofdft_ctx* c, const ZCombineArgs& a, int* blocks_out, hipStream_t st);
 int launch_zi_wgc(ofdft_ctx* c, const ZCombineArgs& a, real* v_part, double* partial, int* blocks_out, hipStream_t st);
 
 }  // namespace eng

@@ -44,13 +44,11 @@ struct ZRun {
     cplx* s_sx = nullptr;          // ... the x pass' result, added by ylap
     cplx* s_l = nullptr;
     real* dzn = nullptr;
-    bool wgc_yinv_done = false;    // kz-chunked form: the y-inverse of the WGC99 results already ran next to the x pass
     bool wgc_split = false;        // the WGC99 potential was formed by zi_wgc_kernel (za.v_part)
     bool closure = false;          // single-GPU closure evaluation: only chi.grad leaves the call, so v may stay in two parts
     bool setup_done = false;       // zsetup ran for the evaluation being enqueued (zstage1 of chain 0 consumes it)
     bool late_join = false;        // host-bound sums of a closure evaluation: the share of sum(v n) of the deferred part is added by chi_grad / the host
     bool vpart_deferred = false;   // ... and does: zi_combine does not wait for zi_wgc, chi_grad adds v_part (zstage5)
-    std::vector<cplx*> deferred;   // x-chunked pipeline: spectra whose y-inverse runs inside the combine loop
     int stage[2] = {0, 0};
     // kz-chunked exchange (ofdft_dist_step): last (step, chunk) of each chain; what stage 1 sent (read again by every chunk of stage 2)
     int step[2] = {0, 0}, step_chunk[2] = {0, 0};
@@ -69,19 +67,6 @@ ZRun& zrun(ofdft_ctx* c);
 
 // ---- all-to-all buffers of the slab-decomposed path, one pair per chain (both directions reuse the pair):
 // chain 0 carries at most 5 spectra (Hartree, grad n, vW leaving stage 2), chain 1 at most 8 (2 Wang-Teter + 6 WGC99)
-// x chunks for a loop whose working set is `narr` spectra: the option value is the count for six spectra; more
-// spectra -> proportionally more chunks, so that a chunk's working set stays the same share of the Infinity Cache.
-// Every chunk must be whole workgroups of every z kernel (at most 256 rows each) -> powers of two that divide n0.
-int chunks_for(const ofdft_ctx* c, int narr, int which = 15) {
-    if (c->nranks > 1 || c->xchunks == 1 || !(c->xchunk_mask & which) || !all_pow2(c)) return 1;
-    if (which == 8 && wts_active(c)) return 1;        // the two-pass combine of the stabilised WT-style functional is not chunked
-    // automatic: about 100 MB of spectra per chunk (measured best at 256^3: 8 chunks for the six WGC99 spectra)
-    int want = c->xchunks > 1 ? (c->xchunks * narr + 5) / 6
-                              : (int)std::min<double>(64.0, (double)narr * sizeof(cplx) * (double)c->g.total / 100e6);
-    int n = 1;
-    while (n * 2 <= want && c->n0 % (n * 2) == 0 && ((long long)(c->n0 / (n * 2)) * c->n1) % 256 == 0) n *= 2;
-    return n;
-}
 
 // Stage 1: z-forward (with the pointwise pre-ops) and y-forward of the chain's input spectra.
 // (xk: chunk of the kz-chunked exchange -- the z kernels run with chunk 0, every call y-transforms its chunk into the send
@@ -107,7 +92,6 @@ int zsetup(ofdft_ctx* c) {
     r.za.inv_n = 1.0 / (double)c->npts_g;
     r.ts = term_scalars(c, r.nel);
     r.za.tc = r.ts.tc;
-    r.wgc_yinv_done = false;
     r.s_g[0] = r.s_g[1] = r.s_g[2] = nullptr;
     r.s_n = r.s_s = r.s_vh = r.s_b = r.s_a = nullptr;
     r.pspec = false;
@@ -134,10 +118,6 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         if (r.has_vw)
             if ((rc = spec_ws(c, "zs", &r.s_s))) return rc;
         if (r.s_n || r.s_s) {
-            cplx* both[2];
-            int nb = 0;
-            if (r.s_n) both[nb++] = r.s_n;
-            if (r.s_s) both[nb++] = r.s_s;
             r.gsplit = r.has_g && c->gga_split;
             r.lapl = r.gsplit && gga_needs_laplacian(c);
             r.s_l = nullptr;
@@ -149,22 +129,12 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
                 if ((rc = spec_ws(c, "zgy", &r.s_g[1]))) return rc;
                 if (r.lapl && (rc = spec_ws(c, "zgl", &r.s_l))) return rc;
             }
-            const int nch = r.gsplit ? 1 : chunks_for(c, nb, 1);
             r.da_early = r.gsplit && !dx && (c->axis_passes & 1);
-            // (not where the y passes of the results run inside the x-chunked combine loop: the Laplacian would leave that loop)
             // fp64 build only: in the fp32 build the two-pass Laplacian measured 1.0 % SLOWER per evaluation than the three-pass one in
             // every alternation (256^3, profiles/r07_ab_axis_passes.jsonl) -- bit 2 is accepted there and changes nothing
-            r.lap_split = sizeof(real) == 8 && r.s_s && !dx && nch == 1 && (c->axis_passes & 2) && cell_axes_orthogonal(c) &&
-                          chunks_for(c, 6, 8) == 1;
+            r.lap_split = sizeof(real) == 8 && r.s_s && !dx && (c->axis_passes & 2) && cell_axes_orthogonal(c);
             if (r.lap_split && (rc = spec_ws(c, "zsx", &r.s_sx))) return rc;
-            if (nch > 1) {        // x-chunked: a chunk's spectra are y-transformed while still in the Infinity Cache
-                for (int ch = 0; ch < nch; ++ch) {
-                    if ((rc = launch_zf_density(c, r.ds, r.s_n, r.s_s, st, ch, nch))) return rc;
-                    if ((rc = fast_axis_pass_multi<false>(c, 1, both, nb, st, ch * (c->n0 / nch), c->n0 / nch))) return rc;
-                }
-            } else if ((rc = launch_zf_density(c, r.ds, r.s_n, r.s_s, st, 0, 1, r.gsplit ? r.dzn : nullptr))) {
-                return rc;
-            }
+            if ((rc = launch_zf_density(c, r.ds, r.s_n, r.s_s, st, r.gsplit ? r.dzn : nullptr))) return rc;
             // D_a n from the same spectrum: the multiply by i f_a commutes with the y transforms, so the x pass runs before the y-forward
             // and its result needs no y-inverse (same stream, before yderiv overwrites s_n: no event)
             if (r.da_early) {
@@ -175,14 +145,14 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             }
             // D_b n from the (kz; y, x) spectrum before its in-place y-forward; scaled so that the consumer's 1/N fits
             // (one GPU: the y-forward of n^ rides in the same pass -- both read the same array; OFDFT_YDERIV_FWD=0: two passes)
-            const bool yfwd = OFDFT_YDERIV_FWD && r.gsplit && !dx && nch == 1;
+            const bool yfwd = OFDFT_YDERIV_FWD && r.gsplit && !dx;
             if (r.gsplit && (rc = yderiv(c, r.s_n, r.s_g[1], (double)c->n0g, st, yfwd ? r.s_n : nullptr))) return rc;
             if (r.forked && r.s_s) {          // the vW chain continues on the second side stream
                 HIP_TRY(c, hipEventRecord(c->ev_a, st));
                 HIP_TRY(c, hipStreamWaitEvent(sc, c->ev_a, 0));
             }
-            if (!dx && nch == 1 && r.s_n && !yfwd && (rc = fast_axis_pass<false>(c, 1, r.s_n, st))) return rc;
-            if (!dx && nch == 1 && r.s_s && !r.lap_split && (rc = fast_axis_pass<false>(c, 1, r.s_s, sc))) return rc;
+            if (!dx && r.s_n && !yfwd && (rc = fast_axis_pass<false>(c, 1, r.s_n, st))) return rc;
+            if (!dx && r.s_s && !r.lap_split && (rc = fast_axis_pass<false>(c, 1, r.s_s, sc))) return rc;
             if (r.s_n) xl.push_back(r.s_n);
             if (r.s_s) xl.push_back(r.s_s);
         }
@@ -217,27 +187,18 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             pa.e1 = al;
             pa.nref = r.ts.tc.nref;
             pa.sum53 = r.ts.tc.wgc_sum_53;
-            // x-chunked form: each chunk's six spectra (6 x C / nchunks) are y-transformed while still in the Infinity Cache
-            const int nch = chunks_for(c, 6, 2);
-            if (nch > 1) {
-                for (int ch = 0; ch < nch; ++ch) {
-                    if ((rc = launch_zf_powers(c, r.ds, pa, sb, ch, nch))) return rc;
-                    if ((rc = fast_axis_pass_multi<false>(c, 1, r.sw, 6, sb, ch * (c->n0 / nch), c->n0 / nch))) return rc;
-                }
-            } else if ((rc = launch_zf_powers(c, r.ds, pa, sb))) {
-                return rc;
-            }
+            if ((rc = launch_zf_powers(c, r.ds, pa, sb))) return rc;
             if (r.forked) {                    // second half (P, Q, S) continues on the second side stream
                 HIP_TRY(c, hipEventRecord(c->ev_b, sb));
                 HIP_TRY(c, hipStreamWaitEvent(sc, c->ev_b, 0));
             }
-            if (!dx && nch == 1 && c->ybatch) {       // a half's three y passes as ONE launch (grid.y = 3): more workgroups than the
-                                                      // chip holds at once, so loads, transforms and stores of different tiles overlap
+            if (!dx && c->ybatch) {       // a half's three y passes as ONE launch (grid.y = 3): more workgroups than the
+                                          // chip holds at once, so loads, transforms and stores of different tiles overlap
                 if ((rc = fast_axis_pass_multi<false>(c, 1, r.sw, 3, sb))) return rc;
                 if ((rc = fast_axis_pass_multi<false>(c, 1, r.sw + 3, 3, sc))) return rc;
             }
             for (int i = 0; i < 6; ++i) {
-                if (!dx && nch == 1 && !c->ybatch && (rc = fast_axis_pass<false>(c, 1, r.sw[i], i < 3 ? sb : sc))) return rc;
+                if (!dx && !c->ybatch && (rc = fast_axis_pass<false>(c, 1, r.sw[i], i < 3 ? sb : sc))) return rc;
                 xl.push_back(r.sw[i]);
             }
         }
@@ -277,7 +238,7 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
         nout = chain == 0 ? (r.has_h ? 1 : 0) + (r.has_g ? (r.gsplit ? (r.lapl ? 2 : 1) : 3) : 0) + (r.s_s ? 1 : 0)
                           : (r.s_b ? 1 : 0) + (r.s_a ? 1 : 0) + (r.has_wgc ? 6 : 0);
-        lay = XfLayout{(long long)in_list.size() * xv.arr_sz, nout * xv.arr_sz, xv.arr_sz, 0, 0, xv.nb, xv.nrem, xv.kb0 * 8};
+        lay = XfLayout{(long long)in_list.size() * xv.arr_sz, nout * xv.arr_sz, xv.arr_sz, xv.nb, xv.nrem, xv.kb0 * 8};
         recv += (long long)in_list.size() * xv.base1;         // this chunk's region of either buffer
         send += (long long)nout * xv.base1;
     }
@@ -375,30 +336,13 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         }
         if (r.has_wgc) {
             const MixWgc mix = wgc_tab(c, dx ? xv.base1 : 0);    // (the table is chunk-major like the buffers)
-            // kz-chunked form (one GPU): the fused x pass of a range of kz blocks is followed at once by the y-inverse
-            // of the same range, which then reads the x pass' output from the Infinity Cache
-            const int nb = c->g.nzm / 8;
-            int nkz = (!dx && (c->xchunk_mask & 16) && c->xchunks != 1) ? chunks_for(c, 6, 16) : 1;
-            while (nkz > 1 && nb % nkz) nkz >>= 1;
-            r.wgc_yinv_done = nkz > 1;
             for (int half = 0; half < 2; ++half) {
                 XfIo io{};
                 for (int i = 0; i < 3; ++i) {
                     io.in[i] = in_of(r.sw[3 * half + i]);
                     io.out[i] = out_of(r.sw[3 * half + i]);
                 }
-                hipStream_t hs = half == 0 ? sb : sc;
-                if (nkz == 1) {
-                    if ((rc = xfused_wgc(c, io, mix, hs, "xfused_wgc", lay))) return rc;
-                    continue;
-                }
-                for (int ch = 0; ch < nkz; ++ch) {
-                    XfLayout lk = lay;
-                    lk.kb0 = ch * (nb / nkz);
-                    lk.kb1 = (ch + 1) * (nb / nkz);
-                    if ((rc = xfused_wgc(c, io, mix, hs, "xfused_wgc", lk))) return rc;
-                    if ((rc = fast_axis_pass_multi<true>(c, 1, r.sw + 3 * half, 3, hs, 0, 0, lk.kb0, lk.kb1))) return rc;
-                }
+                if ((rc = xfused_wgc(c, io, mix, half == 0 ? sb : sc, "xfused_wgc", lay))) return rc;
             }
         }
     }
@@ -430,10 +374,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
         return 0;
     }
     const int yk = part == 2 ? 0 : -1;           // chunks the y-forwards below cover
-    // x-chunked pipeline: the y-inverse of every spectrum the combine kernel consumes moves into the combine loop
-    // (stage 5) and that of grad n into the PBE loop below, so the consumer reads the lines from the Infinity Cache
-    const bool chunked = chunks_for(c, 6, 8) > 1, pbe_chunked = !r.gsplit && chunks_for(c, 6, 4) > 1;
-    const bool wbatch = !dx && c->ybatch && chain == 1 && r.has_wgc && !r.wgc_yinv_done && !chunked && xl.size() >= 6;
+    const bool wbatch = !dx && c->ybatch && chain == 1 && r.has_wgc && xl.size() >= 6;
     if (wbatch) {           // the six WGC99 results: one batched y-inverse per half (see stage 1)
         if ((rc = fast_axis_pass_multi<true>(c, 1, r.sw, 3, sb))) return rc;
         if ((rc = fast_axis_pass_multi<true>(c, 1, r.sw + 3, 3, sc))) return rc;
@@ -443,13 +384,8 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
         const bool on_c = sp == r.s_s || sp == r.sw[3] || sp == r.sw[4] || sp == r.sw[5];
         const bool is_g = sp == r.s_g[0] || sp == r.s_g[1] || sp == r.s_g[2] || (r.s_l && sp == r.s_l);
         const bool is_w = sp == r.sw[0] || sp == r.sw[1] || sp == r.sw[2] || sp == r.sw[3] || sp == r.sw[4] || sp == r.sw[5];
-        if (is_w && (r.wgc_yinv_done || wbatch)) {
-            // already y-inverted next to the x pass / by the batched launches above
-        } else if (is_g ? pbe_chunked : chunked) {
-            if (!is_g) r.deferred.push_back(sp);
-        } else if (!dx && (rc = fast_axis_pass<true>(c, 1, sp, on_b ? sb : (on_c ? sc : st)))) {
-            return rc;
-        }
+        // (the six WGC99 results were y-inverted by the batched launches above)
+        if (!(is_w && wbatch) && !dx && (rc = fast_axis_pass<true>(c, 1, sp, on_b ? sb : (on_c ? sc : st)))) return rc;
         if (!is_g) c->fft_count++;
     }
     xl.clear();
@@ -464,7 +400,7 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
                 r.za.gw[i] = r.sw[3 + i];
             }
         r.wgc_split = false;
-        if (r.has_wgc && !chunked && c->split_combine && !graph_eligible(c)) {
+        if (r.has_wgc && c->split_combine && !graph_eligible(c)) {
             // both halves of the chain are done -> its part of the combine runs here, beside the other chain's PBE tail
             real* vp;
             acc_t* part2;
@@ -510,18 +446,11 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
         }
     } else if (r.has_g) {
         if ((rc = real_ws(c, "dfdn", &r.dfdn))) return rc;
-        const int nch = chunks_for(c, 6, 4);       // 3 spectra in, 3 out, the density and df/dn rows
-        for (int ch = 0; ch < nch; ++ch) {
-            const int x0 = ch * (c->n0 / nch), cx = c->n0 / nch;
-            if (pbe_chunked && (rc = fast_axis_pass_multi<true>(c, 1, r.s_g, 3, st, x0, cx))) return rc;
-            if ((rc = launch_zpbe(c, r.ds, r.s_g[0], r.s_g[1], r.s_g[2], r.dfdn, r.za.inv_n, &r.pbe_blocks, st, ch, nch)))
-                return rc;
-            if (pbe_chunked && (rc = fast_axis_pass_multi<false>(c, 1, r.s_g, 3, st, x0, cx))) return rc;
-        }
+        if ((rc = launch_zpbe(c, r.ds, r.s_g[0], r.s_g[1], r.s_g[2], r.dfdn, r.za.inv_n, &r.pbe_blocks, st))) return rc;
         // no host round trip in the middle of the evaluation: reduce on the device, read with the final sums
         OFDFT_REDUCE(c, st, c->d_partial, r.pbe_blocks, kPbeScalars, c->d_reduced + kSumGga, c->h_partial + kSumGga);
         for (int k = 0; k < 3; ++k) {
-            if (!dx && !pbe_chunked && (rc = fast_axis_pass<false>(c, 1, r.s_g[k], st))) return rc;
+            if (!dx && (rc = fast_axis_pass<false>(c, 1, r.s_g[k], st))) return rc;
             xl.push_back(r.s_g[k]);
         }
         if (dx) {
@@ -573,7 +502,7 @@ int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             if (int rc = dist_buffers(c, 0, &send, &recv)) return rc;
             dio.in[0] = recv + (long long)nin * xv.base1;
             dio.out[0] = send + xv.base1;
-            lay = XfLayout{xv.arr_sz, xv.arr_sz, xv.arr_sz, 0, 0, xv.nb, xv.nrem, xv.kb0 * 8};
+            lay = XfLayout{xv.arr_sz, xv.arr_sz, xv.arr_sz, xv.nb, xv.nrem, xv.kb0 * 8};
         }
         if (r.lapl) {            // i f_a G_a^ + (k^2 / 2) (df/dL)^ -> the spectrum the combine subtracts twice
             dio.in[1] = r.s_l;
@@ -596,7 +525,7 @@ int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             if (int rc = dist_buffers(c, 0, &send, &recv)) return rc;
             for (int k = 0; k < 3; ++k) dio.in[k] = recv + 3 * xv.base1 + k * xv.arr_sz;
             dio.out[0] = send + xv.base1;
-            lay = XfLayout{3 * xv.arr_sz, xv.arr_sz, xv.arr_sz, 0, 0, xv.nb, xv.nrem, xv.kb0 * 8};
+            lay = XfLayout{3 * xv.arr_sz, xv.arr_sz, xv.arr_sz, xv.nb, xv.nrem, xv.kb0 * 8};
         }
         if (int rc = xfused<3, 1>(c, dio, MixDiv{c->kg}, st, "xfused_div", lay)) return rc;
         r.xlist[0].push_back(r.s_n);
@@ -631,7 +560,6 @@ void zfused_collect(const ofdft_ctx* c, int flags, double* sums) {
 int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int part = 0, int xk = -1) {
     ZRun& r = zrun(c);
     int rc;
-    const bool chunked = chunks_for(c, 6, 8) > 1;
     if (part == 1) {
         if (r.has_g && c->nranks > 1) {
             cplx *send, *recv;
@@ -647,9 +575,7 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
             if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
             if (part != 2 && (rc = ypass_xchg<true>(c, {dsp}, recv, st))) return rc;
         } else if (r.pspec) {     // D_b G_b + the y-inverse of the divergence spectrum (+ v_H) in one pass, into that spectrum
-            if ((rc = yderiv_add(c, r.s_g[1], dsp, dsp, (double)c->n0g, st))) return rc;      // (x-chunked combine: before its loop)
-        } else if (chunked) {
-            r.deferred.push_back(dsp);
+            if ((rc = yderiv_add(c, r.s_g[1], dsp, dsp, (double)c->n0g, st))) return rc;
         } else if ((rc = fast_axis_pass<true>(c, 1, dsp, st))) {
             return rc;
         }
@@ -679,18 +605,7 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
         OFDFT_LAUNCH(c, st, "reduce", wts_weights_kernel, dim3(1), dim3(64), 0, (const acc_t*)c->d_reduced, c->d_scal + kScalWts);
         r.za.wts_w = c->d_scal + kScalWts;
     }
-    if (chunked) {        // y-inverse of a chunk of every result spectrum, then the combine kernel on the same x planes
-        const int narr = (int)r.deferred.size();
-        const int nch = chunks_for(c, narr + 2, 8);       // + the real rows (chi, v_ext, df/dn, v) the kernel touches
-        for (int ch = 0; ch < nch; ++ch) {
-            if (narr && (rc = fast_axis_pass_multi<true>(c, 1, r.deferred.data(), narr, st, ch * (c->n0 / nch), c->n0 / nch)))
-                return rc;
-            if ((rc = launch_zi_combine(c, r.za, &r.combine_blocks, st, ch, nch))) return rc;
-        }
-        r.deferred.clear();
-    } else if ((rc = launch_zi_combine(c, r.za, &r.combine_blocks, st))) {
-        return rc;
-    }
+    if ((rc = launch_zi_combine(c, r.za, &r.combine_blocks, st))) return rc;
     // (host-bound sums: the reduce kernel writes the pinned mirror itself -- no copy command behind it; the stabilised
     // WT-style functional rewrites two of the sums afterwards and keeps the copy)
     OFDFT_REDUCE(c, st, c->d_partial, r.combine_blocks, kCombineScalars, c->d_reduced, (sums && !wts) ? c->h_partial : (acc_t*)nullptr);
@@ -730,7 +645,6 @@ int zfused_enqueue(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext,
     r.nel = nel;
     r.vext = vext;
     r.v_out = v_out;
-    r.deferred.clear();
     r.closure = defer;            // (only the closure enqueues in deferred form; its consumer is chi_grad)
     r.vpart_deferred = false;
     r.za.v_part_deferred = 0;

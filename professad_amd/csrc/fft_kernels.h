@@ -18,7 +18,6 @@ namespace ofdft {
 
 struct SpecGeom {
     int n0, n1, n2, nzc, nzm;
-    int blk0 = 0;          // first workgroup of a z-kernel launch that covers only a range of rows (x-chunked pipeline)
     long long nrows;       // n0*n1
     long long main_count;  // nzm*n0*n1
     long long total;       // nzc*n0*n1
@@ -56,10 +55,7 @@ struct LineMap {
     int sl;
     int nlines;
     int lf;  // lines that vary fastest over the lanes (memory-contiguous direction)
-    // optional restriction to a range of an outer index (x-chunked y passes): group G = L / d enumerates (b, xl) with
-    // xl < gc; it stands for group (G / gc) * gn + g0 + G % gc of the full array.  gc == 0: no remapping.
-    int gc = 0, gn = 0, g0 = 0;
-    int blk0 = 0;   // first workgroup (in units of the kernel's lines-per-workgroup) of a launch that covers a line range
+    int blk0 = 0;   // first workgroup (in units of the kernel's lines-per-workgroup) of a launch that covers a line range (kz chunk of the exchange)
     int kz0 = 0;    // fused x pass on a kz chunk of an exchange buffer: kz of line 0 (the lines are numbered inside the chunk)
 };
 
@@ -77,9 +73,7 @@ template <int LEN> struct PassCfg {
 
 // uniform base of a tile (first line of the workgroup) and the per-lane byte offset of line L, element j
 __device__ __forceinline__ long long line_base(const LineMap& m, long long L) {
-    long long grp = L / m.d;
-    if (m.gc) grp = (grp / m.gc) * m.gn + m.g0 + grp % m.gc;
-    return grp * m.sb + (L % m.d) * (long long)m.sl;
+    return (L / m.d) * m.sb + (L % m.d) * (long long)m.sl;
 }
 
 struct ArrList { cplx* p[16]; };
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(PassCfg<LEN>::TPB) void cpass_kernel(ArrList arrs, 
         const bool in_rem = blk >= main_blocks;
         const LineMap m = in_rem ? m_rem : m_main;
         cplx* data = in_rem ? data0 + rem_offset : data0;
-        const int bid = in_rem ? blk - main_blocks : blk + m.blk0;
+        const int bid = in_rem ? blk - main_blocks : blk;
         const int l_lo = tid % m.lf;
         const int j = (tid / m.lf) % P;
         const int l = (tid / (m.lf * P)) * m.lf + l_lo;
@@ -809,7 +803,6 @@ __global__ __launch_bounds__((XfCfg<LEN, (NIN > NOUT ? NIN : NOUT), NOUT>::TPB),
         // the 8 XCDs, so blocks b and b+8 share an L2) -- speed only, never correctness
         bid = (bid & ~15) + ((bid & 7) << 1) + ((bid >> 3) & 1);
     }
-    if (!is_rem) bid += m.blk0;          // launch over a range of kz blocks (multiple of 16 workgroups)
     const long long L = (long long)bid * LPW + l;
     const bool valid = L < m.nlines;
     const long long base = valid ? (L / m.d) * m.sb + (L % m.d) * (long long)m.sl : 0;

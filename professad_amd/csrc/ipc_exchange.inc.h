@@ -425,7 +425,6 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
     r.vext = (const real*)vext_local;
     r.v_out = (real*)v_work_local;
     r.stage[0] = r.stage[1] = 0;
-    r.deferred.clear();
     r.forked = false;
     r.closure = false;
     r.vpart_deferred = false;

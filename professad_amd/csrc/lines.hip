@@ -10,12 +10,10 @@ int launch_cpass_t(ofdft_ctx* c, const ArrList& arrs, int narr, const LineMap& m
     cplx* tw;
     if (int rc = get_twiddle(c, LEN, &tw)) return rc;
     using Cfg = PassCfg<LEN>;
-    LineMap mm = main;
-    mm.blk0 = main.blk0 / Cfg::LPW;                     // line offset -> workgroup offset
     // (tiles of the main part rounded up to whole groups of OFDFT_CPASS_TILES: a workgroup's tiles never straddle the two parts)
     constexpr int T = OFDFT_CPASS_TILES;
-    const int mb = ((main.nlines - main.blk0 + Cfg::LPW - 1) / Cfg::LPW + T - 1) / T * T, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
-    OFDFT_LAUNCH(c, st, nm, (cpass_kernel<LEN, INV>), dim3((mb + rb + T - 1) / T, narr), dim3(Cfg::TPB), Cfg::LDS, arrs, mm, rem, mb,
+    const int mb = ((main.nlines + Cfg::LPW - 1) / Cfg::LPW + T - 1) / T * T, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
+    OFDFT_LAUNCH(c, st, nm, (cpass_kernel<LEN, INV>), dim3((mb + rb + T - 1) / T, narr), dim3(Cfg::TPB), Cfg::LDS, arrs, main, rem, mb,
                  c->g.main_count, tw);
     return 0;
 }
@@ -36,34 +34,14 @@ void pass_maps(const ofdft_ctx* c, int axis, LineMap& main, LineMap& rem) {
     if (rem.nlines == 0) { rem.d = 1; rem.lf = 1; }
 }
 
-// line pass over `narr` spectra in ONE launch; cx > 0 restricts a y pass to the x planes [x0, x0 + cx)
-// kb1 > kb0 restricts a y pass to the kz blocks [kb0, kb1) (the remainder planes ride with the last range)
+// line pass over `narr` spectra in ONE launch
 template <bool INV>
-int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, hipStream_t st, int x0, int cx,
-                         int kb0, int kb1) {
+int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, hipStream_t st) {
     LineMap main, rem;
     pass_maps(c, axis, main, rem);
-    if (kb1 > kb0 && axis == 1) {
-        const int per_block = c->g.n0 * 8;              // lines per kz block
-        main.blk0 = kb0 * per_block;                    // converted to workgroups below
-        main.nlines = kb1 * per_block;
-        if (kb1 != c->g.nzm / 8) rem.nlines = 0;
-    }
-    if (cx > 0 && axis == 1) {
-        main.gc = rem.gc = cx;
-        main.gn = rem.gn = c->g.n0;
-        main.g0 = rem.g0 = x0;
-        main.nlines = (c->g.nzm / 8) * cx * 8;
-        rem.nlines = (c->g.nzc - c->g.nzm) * cx;
-    }
     ArrList arrs{};
     for (int a = 0; a < narr; ++a) arrs.p[a] = specs[a];
-    if (axis == 1) {
-        double frac = 1.0;
-        if (cx > 0) frac *= (double)cx / c->g.n0;
-        if (kb1 > kb0) frac *= (double)(kb1 - kb0) * 8.0 / c->g.nzc;
-        c->ypass_count += narr * frac;
-    }
+    if (axis == 1) c->ypass_count += narr;
     const int len = axis == 0 ? c->n0g : c->n1;
     const char* nm = axis == 0 ? "cpass_x" : "cpass_y";
 #define OFDFT_CASE(L)                                                   \
@@ -691,8 +669,8 @@ int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st
 }
 
 
-template int fast_axis_pass_multi<false>(ofdft_ctx*, int, cplx* const*, int, hipStream_t, int, int, int, int);
-template int fast_axis_pass_multi<true>(ofdft_ctx*, int, cplx* const*, int, hipStream_t, int, int, int, int);
+template int fast_axis_pass_multi<false>(ofdft_ctx*, int, cplx* const*, int, hipStream_t);
+template int fast_axis_pass_multi<true>(ofdft_ctx*, int, cplx* const*, int, hipStream_t);
 template int fast_axis_pass<false>(ofdft_ctx*, int, cplx*, hipStream_t);
 template int fast_axis_pass<true>(ofdft_ctx*, int, cplx*, hipStream_t);
 template int ypass_xchg<false>(ofdft_ctx*, const std::vector<cplx*>&, cplx*, hipStream_t, int);

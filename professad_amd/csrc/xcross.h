@@ -185,7 +185,6 @@ __global__ __launch_bounds__(XcCfg<LEN>::TPB, (xc_waves<LEN, NIN, NOUT>())) void
         // round-robin over the 8 XCDs) -- speed only, never correctness
         bid = (bid & ~15) + ((bid & 7) << 1) + ((bid >> 3) & 1);
     }
-    if (!is_rem) bid += m.blk0;           // launch over a range of kz blocks
     const long long L0 = (long long)bid * LPB;
     const long long L = L0 + NL * l;      // first line of this lane's group (the launcher guarantees whole groups: nlines % NL == 0)
     const bool valid = L < m.nlines;

@@ -6,6 +6,20 @@
 
 namespace eng {
 
+// line maps of a fused x pass and the geometry its kernel sees: the block-8 arrays (one GPU), or the records of the chunk of an
+// exchange buffer that `lay` addresses
+inline void xpass_maps(const ofdft_ctx* c, const XfLayout& lay, LineMap& main, LineMap& rem, SpecGeom& gk) {
+    if (!lay.se_in) return pass_maps(c, 0, main, rem);
+    const int nyl = c->xg.nyl;
+    const int xnb = lay.xnb >= 0 ? lay.xnb : c->xg.nb, xnrem = lay.xnb >= 0 ? lay.xnrem : c->xg.nrem;   // this chunk's share
+    main.d = nyl * 8; main.sb = nyl * 8; main.sl = 1; main.se = lay.se_in; main.nlines = xnb * nyl * 8;
+    main.kz0 = lay.kz0;
+    rem.d = nyl; rem.sb = nyl; rem.sl = 1; rem.se = lay.se_in; rem.nlines = xnrem * nyl;
+    if (main.nlines == 0) main.d = 1;
+    if (rem.nlines == 0) rem.d = 1;
+    gk.main_count = (long long)xnb * nyl * 8;          // offset of the plane part inside a record
+}
+
 template <int LEN, int NIN, int NOUT, class Mix>
 int launch_xfused_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& lay, hipStream_t st, const char* nm) {
     if constexpr (mix_has_energy<Mix>::value)      // (the group-parallel kernel has no energy partials: xfused_energy never routes here)
@@ -16,28 +30,9 @@ int launch_xfused_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout
     if (int rc = get_twiddle(c, LEN, &tw)) return rc;
     LineMap main, rem;
     SpecGeom gk = c->gx;
-    if (lay.se_in) {
-        const int nyl = c->xg.nyl;
-        const int xnb = lay.xnb >= 0 ? lay.xnb : c->xg.nb, xnrem = lay.xnb >= 0 ? lay.xnrem : c->xg.nrem;   // this chunk's share
-        main.d = nyl * 8; main.sb = nyl * 8; main.sl = 1; main.se = lay.se_in; main.nlines = xnb * nyl * 8;
-        main.kz0 = lay.kz0;
-        rem.d = nyl; rem.sb = nyl; rem.sl = 1; rem.se = lay.se_in; rem.nlines = xnrem * nyl;
-        if (main.nlines == 0) main.d = 1;
-        if (rem.nlines == 0) rem.d = 1;
-        gk.main_count = (long long)xnb * nyl * 8;          // offset of the plane part inside a record
-    } else {
-        pass_maps(c, 0, main, rem);
-    }
+    xpass_maps(c, lay, main, rem, gk);
     main.lf = rem.lf = Cfg::LPW;
-    int line0 = 0;
-    if (lay.kb1 > lay.kb0 && !lay.se_in) {              // a range of kz blocks; the remainder planes ride with the last one
-        const int per_block = c->gx.n1 * 8;
-        line0 = lay.kb0 * per_block;
-        main.nlines = lay.kb1 * per_block;
-        if (lay.kb1 != c->gx.nzm / 8) rem.nlines = 0;
-    }
-    main.blk0 = line0 / Cfg::LPW;
-    const int mb = (main.nlines - line0 + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
+    const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
     c->xpass_kinds |= OFDFT_XPASS_GROUP;
     c->xpass_blocks = mb + rb;
     OFDFT_LAUNCH(c, st, nm, (xfused_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb,
@@ -53,29 +48,9 @@ int launch_xw_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
     if (int rc = get_twiddle(c, LEN, &tw)) return rc;
     LineMap main, rem;
     SpecGeom gk = c->gx;
-    if (lay.se_in) {
-        const int nyl = c->xg.nyl;
-        const int xnb = lay.xnb >= 0 ? lay.xnb : c->xg.nb, xnrem = lay.xnb >= 0 ? lay.xnrem : c->xg.nrem;   // this chunk's share
-        main.d = nyl * 8; main.sb = nyl * 8; main.sl = 1; main.se = lay.se_in; main.nlines = xnb * nyl * 8;
-        main.kz0 = lay.kz0;
-        rem.d = nyl; rem.sb = nyl; rem.sl = 1; rem.se = lay.se_in; rem.nlines = xnrem * nyl;
-        if (main.nlines == 0) main.d = 1;
-        if (rem.nlines == 0) rem.d = 1;
-        gk.main_count = (long long)xnb * nyl * 8;          // offset of the plane part inside a record
-    } else {
-        pass_maps(c, 0, main, rem);
-    }
+    xpass_maps(c, lay, main, rem, gk);
     main.lf = rem.lf = Cfg::LPB;
-    int line0 = 0;
-    if (lay.kb1 > lay.kb0 && !lay.se_in) {              // a range of kz blocks; the remainder planes ride with the last one
-        const int per_block = c->gx.n1 * 8;
-        if (per_block % Cfg::LPB) return fail(c, OFDFT_EINVAL, "kz-range x pass needs whole workgroups per kz block");
-        line0 = lay.kb0 * per_block;
-        main.nlines = lay.kb1 * per_block;
-        if (lay.kb1 != c->gx.nzm / 8) rem.nlines = 0;
-    }
-    main.blk0 = line0 / Cfg::LPB;
-    const int mb = (main.nlines - line0 + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
+    const int mb = (main.nlines + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
     c->xpass_kinds |= OFDFT_XPASS_WAVE;
     c->xpass_blocks = mb + rb;
     OFDFT_LAUNCH(c, st, nm, (xw_kernel<LEN, NIN, NOUT, Mix>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, io, main, rem, mb, gk,
@@ -91,18 +66,7 @@ int launch_xc_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
     if (int rc = get_twiddle(c, LEN, &tw)) return rc;
     LineMap main, rem;
     SpecGeom gk = c->gx;
-    if (lay.se_in) {
-        const int nyl = c->xg.nyl;
-        const int xnb = lay.xnb >= 0 ? lay.xnb : c->xg.nb, xnrem = lay.xnb >= 0 ? lay.xnrem : c->xg.nrem;   // this chunk's share
-        main.d = nyl * 8; main.sb = nyl * 8; main.sl = 1; main.se = lay.se_in; main.nlines = xnb * nyl * 8;
-        main.kz0 = lay.kz0;
-        rem.d = nyl; rem.sb = nyl; rem.sl = 1; rem.se = lay.se_in; rem.nlines = xnrem * nyl;
-        if (main.nlines == 0) main.d = 1;
-        if (rem.nlines == 0) rem.d = 1;
-        gk.main_count = (long long)xnb * nyl * 8;          // offset of the plane part inside a record
-    } else {
-        pass_maps(c, 0, main, rem);
-    }
+    xpass_maps(c, lay, main, rem, gk);
     main.lf = rem.lf = Cfg::LPB;
     if constexpr (Cfg::NL > 1) {          // lanes own groups of memory-adjacent lines: whole groups only, else the wave-local kernel
         if (main.sl != 1 || rem.sl != 1 || main.d % Cfg::NL || rem.d % Cfg::NL || main.nlines % Cfg::NL || rem.nlines % Cfg::NL)
@@ -111,16 +75,7 @@ int launch_xc_t(ofdft_ctx* c, const XfIo& io, const Mix& mix, const XfLayout& la
             else return launch_xfused_t<LEN, NIN, NOUT, Mix>(c, io, mix, lay, st, nm);
         }
     }
-    int line0 = 0;
-    if (lay.kb1 > lay.kb0 && !lay.se_in) {              // a range of kz blocks; the remainder planes ride with the last one
-        const int per_block = c->gx.n1 * 8;
-        if (per_block % Cfg::LPB) return fail(c, OFDFT_EINVAL, "kz-range x pass needs whole workgroups per kz block");
-        line0 = lay.kb0 * per_block;
-        main.nlines = lay.kb1 * per_block;
-        if (lay.kb1 != c->gx.nzm / 8) rem.nlines = 0;
-    }
-    main.blk0 = line0 / Cfg::LPB;
-    const int mb = (main.nlines - line0 + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
+    const int mb = (main.nlines + Cfg::LPB - 1) / Cfg::LPB, rb = (rem.nlines + Cfg::LPB - 1) / Cfg::LPB;
     constexpr size_t lds = Cfg::lds_bytes(xc_one_buffer<LEN, NIN, NOUT>());
     if constexpr (lds > 64 * 1024) {          // more dynamic LDS than the default limit: declared once per kernel and device
         static bool declared[64] = {};

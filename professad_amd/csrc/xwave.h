@@ -171,7 +171,6 @@ __global__ __launch_bounds__(XwCfg<LEN>::TPB, (NIN + NOUT > 3 ? OFDFT_XW_WAVES :
         // round-robin over the 8 XCDs) -- speed only, never correctness
         bid = (bid & ~15) + ((bid & 7) << 1) + ((bid >> 3) & 1);
     }
-    if (!is_rem) bid += m.blk0;           // launch over a range of kz blocks
     const long long L0 = (long long)bid * LPB;
     const long long L = L0 + wave * LPWV + l;
     const bool valid = L < m.nlines;

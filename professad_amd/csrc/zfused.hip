@@ -25,20 +25,15 @@ int z_tables(ofdft_ctx* c, cplx** twM, cplx** twN) {
 }
 template <int M, int E> int z_blocks(const ofdft_ctx* c) { return (int)((c->g.nrows + ZW<M, E>::RPB - 1) / ZW<M, E>::RPB); }
 
-// The z launchers take (chunk, nchunks): the launch covers that share of the rows, i.e. the x planes
-// [chunk, chunk + 1) * n0 / nchunks (x-chunked pipeline); partial sums land where a full launch would put them.
-int launch_zf_density(ofdft_ctx* c, const DenSrc& ds, cplx* out_n, cplx* out_s, hipStream_t st, int chunk,
-                      int nchunks, real* dzn) {
+int launch_zf_density(ofdft_ctx* c, const DenSrc& ds, cplx* out_n, cplx* out_s, hipStream_t st, real* dzn) {
     cplx *twM, *twN;
     if (int rc = z_tables(c, &twM, &twN)) return rc;
-    if (chunk == 0) c->fft_count += (out_n ? 1 : 0) + (out_s ? 1 : 0);
-    SpecGeom gz = c->g;
+    c->fft_count += (out_n ? 1 : 0) + (out_s ? 1 : 0);
 #define X(M_)                                                                                                       \
     case M_: {                                                                                                      \
-        const int nb = z_blocks<M_, ZPick<M_, 8>::E>(c) / nchunks;                                                  \
-        gz.blk0 = chunk * nb;                                                                                       \
+        const int nb = z_blocks<M_, ZPick<M_, 8>::E>(c);                                                            \
         OFDFT_LAUNCH(c, st, "zf_density", (zf_density_kernel<M_, ZPick<M_, 8>::E>), dim3(nb), dim3(256),            \
-                     (ZW<M_, ZPick<M_, 8>::E>::LDS), ds, out_n, out_s, gz, twM, twN, dzn);                          \
+                     (ZW<M_, ZPick<M_, 8>::E>::LDS), ds, out_n, out_s, c->g, twM, twN, dzn);                        \
         return 0;                                                                                                   \
     }
     switch (c->n2 / 2) { OFDFT_ZCASES(X) }
@@ -46,22 +41,19 @@ int launch_zf_density(ofdft_ctx* c, const DenSrc& ds, cplx* out_n, cplx* out_s, 
     return fail(c, OFDFT_EINVAL, "bad n2");
 }
 
-int launch_zf_powers(ofdft_ctx* c, const DenSrc& ds, const PowersArgs& pa, hipStream_t st, int chunk, int nchunks) {
+int launch_zf_powers(ofdft_ctx* c, const DenSrc& ds, const PowersArgs& pa, hipStream_t st) {
     cplx *twM, *twN;
     if (int rc = z_tables(c, &twM, &twN)) return rc;
-    if (chunk == 0)
-        for (int i = 0; i < 6; ++i) c->fft_count += pa.out[i] ? 1 : 0;
-    SpecGeom gz = c->g;
+    for (int i = 0; i < 6; ++i) c->fft_count += pa.out[i] ? 1 : 0;
 #define X(M_)                                                                                                      \
     case M_: {                                                                                                     \
-        const int nb = z_blocks<M_, ZPick<M_, EZP>::E>(c) / nchunks;                                                \
-        gz.blk0 = chunk * nb;                                                                                      \
+        const int nb = z_blocks<M_, ZPick<M_, EZP>::E>(c);                                                         \
         if (pa.out[0] && !pa.out[1] && !pa.out[2] && !pa.out[3] && !pa.out[4] && !pa.out[5])                       \
             OFDFT_LAUNCH(c, st, "zf_powers", (zf_powers_kernel<M_, ZPick<M_, EZP>::E, true>), dim3(nb), dim3(256), \
-                         (ZW<M_, ZPick<M_, EZP>::E>::LDS), ds, pa, gz, twM, twN);                                   \
+                         (ZW<M_, ZPick<M_, EZP>::E>::LDS), ds, pa, c->g, twM, twN);                                 \
         else                                                                                                       \
             OFDFT_LAUNCH(c, st, "zf_powers", (zf_powers_kernel<M_, ZPick<M_, EZP>::E>), dim3(nb), dim3(256),       \
-                         (ZW<M_, ZPick<M_, EZP>::E>::LDS), ds, pa, gz, twM, twN);                                   \
+                         (ZW<M_, ZPick<M_, EZP>::E>::LDS), ds, pa, c->g, twM, twN);                                 \
         return 0;                                                                                                  \
     }
     switch (c->n2 / 2) { OFDFT_ZCASES(X) }
@@ -70,18 +62,15 @@ int launch_zf_powers(ofdft_ctx* c, const DenSrc& ds, const PowersArgs& pa, hipSt
 }
 
 int launch_zpbe(ofdft_ctx* c, const DenSrc& ds, cplx* gx, cplx* gy, cplx* gz, real* dfdn, double inv_n,
-                int* blocks_out, hipStream_t st, int chunk, int nchunks) {
+                int* blocks_out, hipStream_t st) {
     cplx *twM, *twN;
     if (int rc = z_tables(c, &twM, &twN)) return rc;
-    if (chunk == 0) c->fft_count += 6;    // three c2r finished + three r2c started on chip
-    SpecGeom gq = c->g;
+    c->fft_count += 6;    // three c2r finished + three r2c started on chip
 #define X(M_)                                                                                                   \
     case M_: {                                                                                                  \
         *blocks_out = z_blocks<M_, ZPick<M_, EZ>::E>(c);                                                        \
-        const int nb = *blocks_out / nchunks;                                                                   \
-        gq.blk0 = chunk * nb;                                                                                   \
-        OFDFT_LAUNCH(c, st, "zpbe", (zpbe_kernel<M_, ZPick<M_, EZ>::E>), dim3(nb), dim3(256),                   \
-                     (ZW<M_, ZPick<M_, EZ>::E>::LDS), ds, gx, gy, gz, dfdn, inv_n, gga_sel(c), gq, twM, twN,   \
+        OFDFT_LAUNCH(c, st, "zpbe", (zpbe_kernel<M_, ZPick<M_, EZ>::E>), dim3(*blocks_out), dim3(256),          \
+                     (ZW<M_, ZPick<M_, EZ>::E>::LDS), ds, gx, gy, gz, dfdn, inv_n, gga_sel(c), c->g, twM, twN, \
                      c->d_partial);                                                                             \
         return 0;                                                                                               \
     }
@@ -116,23 +105,20 @@ int launch_zpbe2(ofdft_ctx* c, const DenSrc& ds, cplx* A, cplx* B, const real* d
     return fail(c, OFDFT_EINVAL, "bad n2");
 }
 
-int launch_zi_combine(ofdft_ctx* c, const ZCombineArgs& a, int* blocks_out, hipStream_t st, int chunk, int nchunks) {
+int launch_zi_combine(ofdft_ctx* c, const ZCombineArgs& a, int* blocks_out, hipStream_t st) {
     cplx *twM, *twN;
     if (int rc = z_tables(c, &twM, &twN)) return rc;
-    SpecGeom gq = c->g;
     const size_t park = sizeof(real) * 256 * kParkSlots;
 #define X(M_)                                                                                                     \
     case M_: {                                                                                                    \
         using W = ZW<M_, ZPick<M_, EZ>::E>;                                                                       \
         *blocks_out = z_blocks<M_, W::E>(c);                                                                      \
-        const int nb = *blocks_out / nchunks;                                                                     \
-        gq.blk0 = chunk * nb;                                                                                     \
         if (a.v_part || !(a.mask & OFDFT_WGC99_NL))   /* no inline WGC99 section needed: the lean instantiation */  \
-            OFDFT_LAUNCH(c, st, "zi_combine", (zi_combine_kernel<M_, W::E, false>), dim3(nb), dim3(256),          \
-                         (W::LDS + park), a, gq, twM, twN, c->d_partial);                                         \
+            OFDFT_LAUNCH(c, st, "zi_combine", (zi_combine_kernel<M_, W::E, false>), dim3(*blocks_out), dim3(256), \
+                         (W::LDS + park), a, c->g, twM, twN, c->d_partial);                                       \
         else                                                                                                      \
-            OFDFT_LAUNCH(c, st, "zi_combine", (zi_combine_kernel<M_, W::E, true>), dim3(nb), dim3(256),           \
-                         (W::LDS + park), a, gq, twM, twN, c->d_partial);                                         \
+            OFDFT_LAUNCH(c, st, "zi_combine", (zi_combine_kernel<M_, W::E, true>), dim3(*blocks_out), dim3(256),  \
+                         (W::LDS + park), a, c->g, twM, twN, c->d_partial);                                       \
         return 0;                                                                                                 \
     }
     switch (c->n2 / 2) { OFDFT_ZCASES(X) }

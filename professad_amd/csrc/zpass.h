@@ -105,7 +105,7 @@ template <int M, int E> struct ZLane {
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         j = lane % W::P;
         rw = lane / W::P;
-        row_u = uniform64((long long)(blockIdx.x + g.blk0) * W::RPB + (long long)wave * W::RPWV);
+        row_u = uniform64((long long)blockIdx.x * W::RPB + (long long)wave * W::RPWV);
         row = row_u + rw;
         valid = row < g.nrows;
         mine = lds + (wave * W::RPWV + rw) * W::RS;
@@ -610,7 +610,7 @@ __global__ __launch_bounds__(256, (z_waves<M, E>(OFDFT_ZPBE_WAVES))) void zpbe_k
     z_forward_store<M, E>(b, z, gy, g, twM, twN);
     repattern_out_to_in<PL, true>(c, z.j, z.mine);
     z_forward_store<M, E>(c, z, gz, g, twM, twN);
-    block_reduce_store<kPbeScalars>(acc, partial + (long long)g.blk0 * kPbeScalars);
+    block_reduce_store<kPbeScalars>(acc, partial);
 }
 
 // Split-derivative form of the GGA mid stage.  With the index derivatives D_a, D_b, D_c (Cartesian d_j = sum_axis
@@ -737,7 +737,7 @@ __global__ __launch_bounds__(256, (z_waves<M, E, OFDFT_Z_EMAX_PBE>(2))) void zpb
 #pragma unroll
     for (int q = 0; q < E; ++q) d[q] = mkc(d[q].x - 2.0 * inv_nz * c[q].x, d[q].y - 2.0 * inv_nz * c[q].y);
     z_store_real<M, E>(d, z, dfdn);
-    block_reduce_store<kPbeScalars>(acc, partial + (long long)g.blk0 * kPbeScalars);
+    block_reduce_store<kPbeScalars>(acc, partial);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1088,12 +1088,12 @@ __global__ __launch_bounds__(256, (zi_combine_waves<M, E, WGC_INLINE>())) void z
 #pragma unroll
         for (int s = 0; s < kCombineScalars; ++s) acc[s] = 0.0;
     }
-    if (a.eh_part && g.blk0 + blockIdx.x == 0) {
-        // E_H from the divergence x pass: its partials join the Hartree slot of the first workgroup (the same order in an x-chunked loop)
+    if (a.eh_part && blockIdx.x == 0) {
+        // E_H from the divergence x pass: its partials join the Hartree slot of the first workgroup
         for (long long i = threadIdx.x; i < a.eh_rows; i += blockDim.x) acc[kSumHartree] += a.eh_part[i];
     }
     if (a.v_out) z_store_real<M, E>(vacc, z, a.v_out);
-    block_reduce_store<kCombineScalars>(acc, partial + (long long)g.blk0 * kCombineScalars);
+    block_reduce_store<kCombineScalars>(acc, partial);
 }
 
 // The WGC99 part of the combine on its own (split form): chi|n row + the six result spectra -> v_part rows and the
@@ -1127,7 +1127,7 @@ __global__ __launch_bounds__(256, (z_waves<M, E>(OFDFT_ZIWGC_WAVES))) void zi_wg
         if (PL::slot_out(q) && PL::lane_out(z.j, q)) acc[kVn] += vacc[q].x * n[q].x + vacc[q].y * n[q].y;
     if (!z.valid) acc[kE] = acc[kVn] = 0.0;
     z_store_real<M, E>(vacc, z, v_part);
-    block_reduce_store<2>(acc, partial + (long long)g.blk0 * 2);
+    block_reduce_store<2>(acc, partial);
 }
 
 }  // namespace ofdft
