@@ -30,7 +30,7 @@
  *   - precision: the ABI is built once per precision from the same sources -- libofdft_hip.so (OFDFT_F64, the
  *     reference's precision) and libofdft_hip_f32.so (OFDFT_F32, same symbols; grid arrays are float / float2, every
  *     host-visible scalar stays double).  ofdft_create refuses the dtype of the other build.  The fp32 library serves
- *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points are fp64-only and return OFDFT_EINVAL there.
+ *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points and ofdft_hessian_vector are fp64-only and return OFDFT_EINVAL there.
  *   - energies are Hartree; lengths bohr; box_vecs rows are the lattice vectors (reference layout).
  */
 #ifndef OFDFT_HIP_H
@@ -268,6 +268,26 @@ int  ofdft_stress(ofdft_ctx* ctx, const void* den_dev, double* sigma_terms_host,
 int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double* frac_coords_host, int nions,
                                const double* table_k_host, const double* table_v_host, int ntable, double z_ion,
                                int pme_order, double* sigma_host /*[9]*/, void* stream);
+
+/* ---- Hessian-vector product: the second functional derivative applied to a direction ---------------------------------
+ * hv(r) = d/d eps v[n + eps w](r) at eps = 0, v = dE/dn as ofdft_energy_potential returns it: with H_ij = d^2 E / dn_i dn_j of the
+ * grid values, hv = (H w) / dV.  It stands behind what the reference obtains by differentiating a potential a second time through
+ * autograd: get_inv_G (functional_tools.py:34-70), get_functional_derivative(..., requires_grad=True) (functional_tools.py:9-31) and the
+ * implicit-function solves of System's second-order derivative terms -- bulk modulus, elastic constants, force constants
+ * (system.py:1204-1367), each a linear system in this operator.  den_dev > 0, dir_dev any real grid, hv_dev receives hv;
+ * quad_terms_host[t] = sum_i w_i hv_t,i dV = int w (H_t w) per term bit (entries of unset terms 0; NULL skips the host read).
+ * Served: ion_electron (hv = 0, no vext needed), hartree, tf, vw, wt_nl (any alpha, beta), lda_x, pz_c, pw_c, chachiyo_c.  In wt_nl the
+ * n0 of the kernel is mean(den) vol of the den passed in and a CONSTANT of the differentiation (functionals.py:646-647 take it with
+ * .item()), so a finite difference of the potential along a w of non-zero mean differs.  Refused with OFDFT_EINVAL, the message
+ * naming the term: wgc99_nl, pbe_x, pbe_c, gga_k, vwgtf, nlk, OFDFT_P_WTS_KIND = 1; slab-decomposed contexts; the fp32 library.
+ * reuse_density: 0 computes everything and leaves the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) in workspaces of their
+ * own; 1 = the caller asserts den holds the values of the previous call made with 0 and those transforms are skipped (Hartree 1 + 1
+ * transforms either way; vW 2 + 2, with reuse 1 + 1; wt_nl 2 + 2 / 1 + 1 for alpha = beta, else 4 + 4 / 2 + 2) -- bitwise the same
+ * hv.  ofdft_set_cell, ofdft_set_terms, ofdft_set_option and every other evaluation (energy, stress, ofdft_dist_*, ofdft_rfftn /
+ * ofdft_irfftn) invalidate the retained fields; 1 with nothing valid retained returns OFDFT_ESTATE.  Sets OFDFT_Q_FFT_COUNT,
+ * OFDFT_Q_LAUNCH_COUNT and OFDFT_Q_KERNEL_MS as the energy calls do.  No atomics: bitwise reproducible. */
+int  ofdft_hessian_vector(ofdft_ctx* ctx, const void* den_dev, const void* dir_dev, void* hv_dev,
+                          double* quad_terms_host /* [OFDFT_NTERMS] or NULL */, int reuse_density, void* stream);
 
 /* Ion-ion interaction: the real-space damped pair sum in a neutralising background of
  * ion_interaction_sum (ion_utils.py:293-333) with System.__ion_ion_interaction's parameters (system.py:733-754);

@@ -7,6 +7,7 @@
 #include "ion_kernels.h"
 #include "ion_cells.h"
 #include "stress_kernels.h"
+#include "hvp_kernels.h"
 #endif
 
 namespace {
@@ -1092,6 +1093,7 @@ int ofdft_set_cell(ofdft_ctx* c, const double box[9]) {
     c->cell_set = true;
     c->wgc_valid = false;
     c->nlk_valid = false;
+    c->hvp_valid = false;
     return OFDFT_OK;
 }
 
@@ -1118,6 +1120,7 @@ int ofdft_set_terms(ofdft_ctx* c, uint32_t mask, const double* params, int npara
     }
     c->mask = mask;
     c->version++;
+    c->hvp_valid = false;
     return OFDFT_OK;
 }
 
@@ -1405,6 +1408,7 @@ int ofdft_rfftn(ofdft_ctx* c, const void* real_dev, void* spec_dev, void* stream
     hipStream_t st = (hipStream_t)stream;
     if (!c || !real_dev || !spec_dev) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
+    c->hvp_valid = false;
     cplx* s;
     if (int rc = spec_ws(c, "io", &s)) return rc;
     if (int rc = rfftn_internal(c, (const real*)real_dev, s, st)) return rc;
@@ -1420,6 +1424,7 @@ int ofdft_irfftn(ofdft_ctx* c, const void* spec_dev, void* real_dev, void* strea
     hipStream_t st = (hipStream_t)stream;
     if (!c || !real_dev || !spec_dev) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
+    c->hvp_valid = false;
     cplx* s;
     if (int rc = spec_ws(c, "io", &s)) return rc;
     OFDFT_LAUNCH(c, st, "spec_to_internal", spec_to_internal_kernel, dim3((unsigned)((c->g.total + 255) / 256)), dim3(256), 0,
@@ -1660,6 +1665,7 @@ int ofdft_dist_chi_grad(ofdft_ctx* c, const void* chi_local, const void* v_local
 #ifndef OFDFT_REAL_F32
 #include "engine_ions_stress.inc.h"
 #include "engine_ion_cells.inc.h"
+#include "engine_hvp.inc.h"
 #else
 // The fp32 build serves the density-optimisation hot path only.  The once-per-geometry-step quantities (ionic potential,
 // forces, stress, ion-ion sum) are fp64 work: callers run them on the fp64 library (professad_amd.ions does).
@@ -1677,6 +1683,7 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void*, const double*, int, con
                               double*, void*) {
     return OFDFT_F64_ONLY(c);
 }
+int ofdft_hessian_vector(ofdft_ctx* c, const void*, const void*, void*, double*, int, void*) { return OFDFT_F64_ONLY(c); }
 int ofdft_ion_ion(ofdft_ctx* c, const double*, const double*, int, double, double*, double*, double*, void*) {
     return OFDFT_F64_ONLY(c);
 }
@@ -1697,6 +1704,7 @@ int ofdft_set_collectives(ofdft_ctx* c, ofdft_all_to_all_fn all_to_all, ofdft_al
 int ofdft_set_option(ofdft_ctx* c, int option, double value) {
     if (!c) return OFDFT_EINVAL;
     c->version++;
+    c->hvp_valid = false;
     switch (option) {
         case OFDFT_OPT_GRAPH:
             c->use_graph = value != 0.0;

@@ -151,6 +151,10 @@ struct ofdft_ctx {
     ofdft_all_to_all_fn a2a = nullptr;
     ofdft_all_reduce_fn allreduce = nullptr;
     void* coll_user = nullptr;
+    // ofdft_hessian_vector: the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) of the last call made with reuse_density = 0
+    // stay in workspaces of their own ("hv:lap", "hv:A", "hv:B"); set_cell / set_terms / set_option and every other evaluation clear the flag
+    bool hvp_valid = false;
+    double hvp_nel = 0.0;              // mean(den) vol of that call: the n0 of the Wang-Teter kernel (functionals.py:646-647)
     char err[512] = "";
 };
 

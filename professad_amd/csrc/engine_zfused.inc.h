@@ -694,6 +694,7 @@ ZRun& zrun(ofdft_ctx* c) {
 int begin_call(ofdft_ctx* c, hipStream_t st, bool timed = true) {
     if (!c) return OFDFT_EINVAL;      // (the ABI function that called this holds the DeviceScope)
     if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    c->hvp_valid = false;      // an evaluation may reuse any workspace: ofdft_hessian_vector starts over (it restores the flag for itself)
     c->fft_count = 0;
     c->launch_count = 0;
     c->xpass_kinds = 0;

@@ -536,6 +536,10 @@ class DistEngine:
         vext = self.stages._grid_tensor(vext, 'v_ext')
         return run_potential(self.stages, self.comm, den, vext, self._vol, self.npts_global, torch.empty_like)
 
+    def hessian_vector(self, den, w, reuse_density=False, want_terms=False):
+        raise NotImplementedError('DistEngine.hessian_vector: the Hessian-vector product (ofdft_hessian_vector) is served by '
+                                  'single-GPU contexts; slab-decomposed contexts have no second derivative')
+
     def query(self, what):
         return self.stages.query(what)
 

@@ -168,6 +168,22 @@ class Engine:
                                                    _ptr(out), self._stream()), 'ofdft_energy_grad_chi')
         return N.per_term(E, self._mask()), mu.value, out
 
+    def hessian_vector(self, den, w, reuse_density=False, want_terms=False):
+        """Second functional derivative of the active terms applied to the direction ``w``: hv = d/d eps v[den + eps w] at
+        eps = 0 = (H w) / dV (ofdft_hessian_vector; what the reference gets from a second autograd pass, functional_tools.py:34-70).
+        -> hv, or with ``want_terms`` (dict term -> int w (H_t w), hv).  ``reuse_density=True``: ``den`` holds the values of the
+        previous call made without it; the density-only transforms are skipped and the result is bitwise the same."""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.hessian_vector: the Hessian-vector product is fp64 work (libofdft_hip.so); '
+                                      'an fp32 engine does not serve it')
+        den = self._grid_tensor(den, 'den')
+        w = self._grid_tensor(w, 'w')
+        out = torch.empty_like(den)
+        q = (C.c_double * N.NTERMS)() if want_terms else None
+        self._check(self.lib.ofdft_hessian_vector(self._ctx, _ptr(den), _ptr(w), _ptr(out), q, 1 if reuse_density else 0,
+                                                  self._stream()), 'ofdft_hessian_vector')
+        return (N.per_term(q, self._mask()), out) if want_terms else out
+
     # -- validation entry points
     def rfftn(self, x):
         x = self._grid_tensor(x, 'x')

@@ -3,8 +3,11 @@
 Every callable here has the reference protocol ``f(box_vecs, den) -> torch scalar`` (``IonElectron``
 takes ``v_ext`` as a third argument) of src/professad/functionals.py, keeps the reference's
 ``__name__``/``__qualname__`` (professad's System dispatches on them, system.py:199-203,761-771,
-917-921) and supports ``E.backward()`` / ``torch.autograd.grad`` w.r.t. ``den`` -- once-differentiable,
-with the analytic functional derivative computed by the engine (no autograd through FFTs).
+917-921) and supports ``E.backward()`` / ``torch.autograd.grad`` w.r.t. ``den``, with the analytic functional
+derivative computed by the engine (no autograd through FFTs).  Under ``create_graph=True`` that derivative is itself
+differentiable in ``den``: its backward is the engine's Hessian-vector product (``Engine.hessian_vector``), for the terms
+that have one (Hartree, TF, vW, the Wang-Teter family, the local XC terms); the others raise ``NotImplementedError`` there.
+``get_inv_G`` (functional_tools.py:34-70) rests on it.
 
 So ``terms=[IonElectron, Hartree, WangTeter, PerdewBurkeErnzerhof]`` built from THIS module can be
 handed to professad's ``System`` unchanged, and ``get_functional_derivative(box_vecs, den, f)``
@@ -83,18 +86,61 @@ class _NativeEnergy(torch.autograd.Function):
             vn = float((v * den.detach()).sum()) * dV
             g = torch.linalg.inv(torch.from_numpy(box_np)).T @ torch.as_tensor(vol * sig + vn * np.eye(3))
             ctx.g_box = g.to(box_vecs.device)
+        # The third entry is the input itself: whether a backward will run under create_graph is not known here, and that one
+        # differentiates with respect to it again.  A reference, no copy and no work -- but autograd's version check now covers
+        # den: an in-place change of den between this call and its backward raises instead of being ignored.
         ctx.save_for_backward(v if den.requires_grad else None,
-                              den.detach() if (v_ext is not None and v_ext.requires_grad) else None)
+                              den.detach() if (v_ext is not None and v_ext.requires_grad) else None,
+                              den if den.requires_grad else None)
         ctx.E_terms = E_terms
+        ctx.hvp_key = (box_np, term_names, params, need_box)
         return torch.tensor(sum(E_terms.values()), dtype=torch.double, device=den.device)
 
     @staticmethod
     def backward(ctx, gE):
-        v, den = ctx.saved_tensors
+        v, den, den_in = ctx.saved_tensors
+        if v is not None and torch.is_grad_enabled():       # create_graph=True: the potential stays differentiable in den
+            box_np, term_names, params, need_box = ctx.hvp_key
+            if need_box:
+                raise NotImplementedError('mixed second derivatives with respect to box_vecs are not served: the native terms '
+                                          'are twice differentiable in the density only')
+            g_den = _NativePotential.apply(den_in, gE, v, ctx.dV, box_np, term_names, params)
+            g_vext = gE * den * ctx.dV if den is not None else None
+            return None, g_den, g_vext, None, None
         g_den = gE * v * ctx.dV if v is not None else None
         g_vext = gE * den * ctx.dV if den is not None else None       # d/dv_ext of mean(n v) vol
         g_box = gE.to(ctx.g_box.device) * ctx.g_box if ctx.g_box is not None else None
         return g_box, g_den, g_vext, None, None
+
+
+class _NativePotential(torch.autograd.Function):
+    """The first derivative as a differentiable node (only built by a backward under ``create_graph=True``): forward returns
+    what ``_NativeEnergy.backward`` returns, gE * dE/dn * dV; its backward for an incoming ``u`` is the Hessian-vector product
+    gE * dV * hessian_vector(den, u) (ofdft_hessian_vector) -- what the reference's double autograd gives get_inv_G
+    (functional_tools.py:34-70) and the second-order derivative terms of System (system.py:1204-1367)."""
+
+    @staticmethod
+    def forward(ctx, den, gE, v, dV, box_np, term_names, params):
+        ctx.save_for_backward(den, gE, v)
+        ctx.key = (dV, box_np, term_names, params)
+        return gE * v * dV
+
+    @staticmethod
+    def backward(ctx, u):
+        den, gE, v = ctx.saved_tensors
+        dV, box_np, term_names, params = ctx.key
+        if torch.is_grad_enabled():
+            raise NotImplementedError('native terms are twice differentiable in the density: no third derivative')
+        eng = engine_for(den.shape, den.device)
+        eng.set_cell(box_np)                       # the shared engine may have served another term since the forward pass
+        eng.set_terms(term_names, params)
+        try:
+            hv = eng.hessian_vector(den, u.detach().contiguous())
+        except RuntimeError as e:
+            if 'no second derivative' in str(e):
+                raise NotImplementedError(str(e)) from None
+            raise
+        return gE * dV * hv, (u * v).sum() * dV, None, None, None, None, None
 
 
 def _evaluate(box_vecs, den, names, params=(), v_ext=None):
@@ -261,12 +307,48 @@ def PerdewBurkeErnzerhof(box_vecs, den):
     return _evaluate(box_vecs, den, ('pbe_x', 'pbe_c'))
 
 
-def get_functional_derivative(box_vecs, den, functional):
-    """functional_tools.py:9-31 for native terms (same result as autograd on them, one engine call)."""
-    den = den.detach().requires_grad_()
+def get_functional_derivative(box_vecs, den, functional, requires_grad=False):
+    """functional_tools.py:9-31 for native terms (same result as autograd on them, one engine call).  With
+    ``requires_grad=True`` the derivative returned can be differentiated once more with respect to ``den`` (which then is
+    the tensor passed in, as in the reference): its backward is a Hessian-vector product of the engine.  Unlike the
+    reference (functional_tools.py:28-30), which sets ``den.requires_grad`` back to False, ``den`` then keeps
+    ``requires_grad=True``: it is the leaf the caller differentiates the result with respect to."""
+    if requires_grad:
+        den.requires_grad_()
+    else:
+        den = den.detach().requires_grad_()
     E = functional(box_vecs, den)
-    (g,) = torch.autograd.grad(E, den)
+    (g,) = torch.autograd.grad(E, den, create_graph=requires_grad)
     return g / (torch.abs(torch.linalg.det(box_vecs)) / den.numel())
+
+
+def get_inv_G(box_vecs, den, kinetic_functional, requires_grad=False):
+    """functional_tools.py:34-70: the linear-response function G^-1(eta) = pi^2 / (k_F F[d^2 T / dn dn']) of a kinetic
+    functional at the uniform density n0 = round(mean(den) vol) / vol -> (eta, G_inv) on the half spectrum.  One
+    Hessian-vector product of every native term inside ``kinetic_functional`` (composites -- sums, a user's stabilisation
+    function -- go through autograd as in the reference); the transform of the response row is the engine's."""
+    if requires_grad or box_vecs.requires_grad:
+        raise NotImplementedError('get_inv_G: derivatives of the response function (third derivatives of the functional, or '
+                                  'mixed density-cell ones) are not served')
+    vol = float(torch.abs(torch.linalg.det(box_vecs.detach().double())))
+    n_elec = round(float(torch.mean(den)) * vol)
+    n0 = torch.full(den.shape, n_elec / vol, dtype=torch.double, device=den.device).requires_grad_()
+    k_F = (3 * np.pi * np.pi * n_elec / vol) ** (1 / 3)
+    dV = vol / den.numel()
+    dTdn = torch.autograd.grad(kinetic_functional(box_vecs, n0), n0, create_graph=True)[0] / dV
+    row = torch.autograd.grad(dTdn[0, 0, 0], n0)[0]
+    G_inv = np.pi * np.pi / k_F / engine_for(den.shape, den.device).rfftn(row.contiguous()).real
+    # |k| as functional_tools.py:135-162 (wavevecs) gives it
+    b = 2 * np.pi * torch.linalg.inv(box_vecs.detach().double().T).to(den.device)
+    f = [torch.fft.fftfreq(s, dtype=torch.double, device=den.device) * s for s in den.shape[:2]]
+    for a in (0, 1):                       # the Nyquist frequency of an even extent counts as positive (:152-154)
+        if den.shape[a] % 2 == 0:
+            f[a][den.shape[a] // 2] = den.shape[a] // 2
+    f.append(torch.fft.rfftfreq(den.shape[2], dtype=torch.double, device=den.device) * den.shape[2])
+    fa, fb, fc = torch.meshgrid(*f, indexing='ij')
+    k = [fa * b[0, j] + fb * b[1, j] + fc * b[2, j] for j in range(3)]
+    eta = torch.sqrt(k[0] ** 2 + k[1] ** 2 + k[2] ** 2) / (2 * k_F)
+    return eta, G_inv
 
 
 def vWGTF1(box_vecs, den):
