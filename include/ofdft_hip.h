@@ -30,7 +30,7 @@
  *   - precision: the ABI is built once per precision from the same sources -- libofdft_hip.so (OFDFT_F64, the
  *     reference's precision) and libofdft_hip_f32.so (OFDFT_F32, same symbols; grid arrays are float / float2, every
  *     host-visible scalar stays double).  ofdft_create refuses the dtype of the other build.  The fp32 library serves
- *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points and ofdft_hessian_vector are fp64-only and return OFDFT_EINVAL there.
+ *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points, ofdft_hessian_vector and ofdft_hessian_vector_chi are fp64-only and return OFDFT_EINVAL there.
  *   - energies are Hartree; lengths bohr; box_vecs rows are the lattice vectors (reference layout).
  */
 #ifndef OFDFT_HIP_H
@@ -289,6 +289,28 @@ int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double
 int  ofdft_hessian_vector(ofdft_ctx* ctx, const void* den_dev, const void* dir_dev, void* hv_dev,
                           double* quad_terms_host /* [OFDFT_NTERMS] or NULL */, int reuse_density, void* stream);
 
+/* The same second derivative in the optimiser's variable.  phi = chi_dev is the caller's chi at any scale,
+ * S = sum phi^2, c = N / (S dV), n = c phi^2, and g = 2 c phi (v - mu) dV is what ofdft_energy_grad_chi leaves in grad_dev
+ * (phi . g = 0).  For a direction d with a = phi . d the call writes the derivative of g along d,
+ *     dn = 2 c phi d - (2 a / S) n        dv = hv(n, dn)        dmu = (sum dv n dV + g . d) / N
+ *     (H d)_j = -(2 a / S) g_j + d_j g_j / phi_j + 2 c phi_j (dv_j - dmu) dV
+ * to out_dev.  Where phi_j = 0 the quotient d_j g_j / phi_j counts as 0: its exact value there, 2 c d_j (v_j - mu) dV, cannot be
+ * formed from g.  g_dev = NULL stands for a stationary point (g = 0; bitwise the result of a zero array).  scalars_host, if
+ * given, receives d . H d, phi . H d, a, S and dmu (OFDFT_HVC_*).  reuse_density = 1 asserts that phi holds the values of the
+ * previous call made with 0: n, S, c and the density-only fields are kept and the smaller transform count runs; what
+ * invalidates the retained fields of ofdft_hessian_vector invalidates these, and the two entries do not reuse each other's
+ * fields.  Single GPU and fp64; the same terms are refused, by name.  The chi-space arithmetic runs inside the product's head
+ * and combine kernels; the call adds one sweep over (phi, d) in front and one over (phi, out) behind.  No atomics. */
+#define OFDFT_HVC_DHD 0
+#define OFDFT_HVC_PHIHD 1
+#define OFDFT_HVC_A 2
+#define OFDFT_HVC_S 3
+#define OFDFT_HVC_DMU 4
+#define OFDFT_HVC_NSCALARS 5
+int  ofdft_hessian_vector_chi(ofdft_ctx* ctx, const void* chi_dev, const void* dir_dev, const void* g_dev /* or NULL */,
+                              double n_electrons, void* out_dev, double* scalars_host /* [OFDFT_HVC_NSCALARS] or NULL */,
+                              int reuse_density, void* stream);
+
 /* Ion-ion interaction: the real-space damped pair sum in a neutralising background of
  * ion_interaction_sum (ion_utils.py:293-333) with System.__ion_ion_interaction's parameters (system.py:733-754);
  * Rc <= 0 selects its default Rd = 2 h_max, Rc = 3 Rd^2 / h_max.  The pair list (torch-nl's neighbour list in the
@@ -342,6 +364,31 @@ int  ofdft_lbfgs_dots(ofdft_lbfgs* h, const void* g_dev, double* dots_host /* [6
 int  ofdft_lbfgs_commit(ofdft_lbfgs* h, int push);
 int  ofdft_lbfgs_update(ofdft_lbfgs* h, const double* coef_s, const double* coef_y, double coef_g, double t, void* x_dev,
                         const void* g_dev, double* abs_step_sum_host, void* stream);
+
+/* ---- conjugate gradients for P H P x = b, P = I - phi phi^T / (phi . phi), b perpendicular to phi ----------------
+ * The solve behind truncated Newton and the density response (professad_amd/optimize.py).  x, r, p, q live in the handle; the
+ * caller forms q = H p between the steps (ofdft_hessian_vector_chi with dir_dev = p, out_dev = q of ofdft_cg_vectors, whose
+ * scalars are the p . q and phi . q that ofdft_cg_step takes).
+ *   ofdft_cg_start  x = 0, r = p = b - phi (phi . b) / S; info_host [3] = |r|^2, S, phi . b.  rtol: stop at |r| <= rtol |r_0|.
+ *   ofdft_cg_step   p . q <= 0: reason OFDFT_CG_CURVATURE, x stays (before the first update x = p).  Otherwise one update sweep
+ *                   (x += alpha p, r -= alpha (q - phi (phi . q) / S); sums r . r, phi . r), the stopping rules, and one
+ *                   direction sweep (p = r - phi (phi . r) / S + beta p).  One stream synchronisation.
+ *   ofdft_cg_status iterations done, reason, |r| / |r_0|.        ofdft_cg_solution copies x to the caller's array.
+ * No atomics: bitwise reproducible. */
+#define OFDFT_CG_RUNNING   0
+#define OFDFT_CG_CONVERGED 1
+#define OFDFT_CG_MAXITER   2
+#define OFDFT_CG_CURVATURE 3
+typedef struct ofdft_cg ofdft_cg;
+int  ofdft_cg_create(ofdft_cg** out, long long n, int device_id);
+void ofdft_cg_destroy(ofdft_cg* h);
+const char* ofdft_cg_last_error(const ofdft_cg* h);
+int  ofdft_cg_start(ofdft_cg* h, const void* phi_dev, const void* b_dev, double rtol, int maxiter, double* info_host /* [3] or NULL */,
+                    void* stream);
+int  ofdft_cg_vectors(ofdft_cg* h, void** x_dev, void** r_dev, void** p_dev, void** q_dev);
+int  ofdft_cg_step(ofdft_cg* h, const void* phi_dev, double p_dot_q, double phi_dot_q, int* reason, void* stream);
+int  ofdft_cg_status(const ofdft_cg* h, int* iterations, int* reason, double* rel_residual);
+int  ofdft_cg_solution(ofdft_cg* h, void* x_out_dev, void* stream);
 
 /* Tuning / validation switches.  OFDFT_OPT_PIPELINE: 0 = automatic (power-of-two grids: fused x passes and z
  * passes that keep every real-space intermediate on chip), 1 = force the unfused pipeline (separate forward,

@@ -1684,6 +1684,7 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void*, const double*, int, con
     return OFDFT_F64_ONLY(c);
 }
 int ofdft_hessian_vector(ofdft_ctx* c, const void*, const void*, void*, double*, int, void*) { return OFDFT_F64_ONLY(c); }
+int ofdft_hessian_vector_chi(ofdft_ctx* c, const void*, const void*, const void*, double, void*, double*, int, void*) { return OFDFT_F64_ONLY(c); }
 int ofdft_ion_ion(ofdft_ctx* c, const double*, const double*, int, double, double*, double*, double*, void*) {
     return OFDFT_F64_ONLY(c);
 }
@@ -1825,3 +1826,4 @@ int ofdft_query(ofdft_ctx* c, int what, double* out) {
 }  // extern "C"
 
 #include "lbfgs_abi.h"
+#include "cg_abi.h"

@@ -153,7 +153,9 @@ struct ofdft_ctx {
     void* coll_user = nullptr;
     // ofdft_hessian_vector: the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) of the last call made with reuse_density = 0
     // stay in workspaces of their own ("hv:lap", "hv:A", "hv:B"); set_cell / set_terms / set_option and every other evaluation clear the flag
-    bool hvp_valid = false;
+    // (0: nothing retained; 1: by ofdft_hessian_vector; 2: by ofdft_hessian_vector_chi, whose fields belong to n[phi] -- engine_hvp.inc.h)
+    unsigned char hvp_valid = false;
+    double hvp_chi_S = 0.0;            // sum phi^2 of the chi-space call that retained them
     double hvp_nel = 0.0;              // mean(den) vol of that call: the n0 of the Wang-Teter kernel (functionals.py:646-647)
     char err[512] = "";
 };

@@ -1,39 +1,49 @@
-// C ABI of the Hessian-vector product (hvp_kernels.h).  Included once by engine.hip inside its extern "C" block (fp64 library).
+// C ABI of the Hessian-vector products (hvp_kernels.h).  Included once by engine.hip inside its extern "C" block (fp64 library).
 //
-// The call is three kernels around the batched whole-grid transforms of the unfused pipeline (rfftn_internal_multi /
+// A product is three kernels around the batched whole-grid transforms of the unfused pipeline (rfftn_internal_multi /
 // irfftn_internal_multi: powers of two, mixed-radix plans and chirp-z extents alike):
 //   head     n, w -> sqrt n, w / 2 sqrt n, n^beta, n^(beta-1) w [, n^alpha, n^(alpha-1) w]      (w itself is transformed from the caller's array)
 //   forward batch, one spectral kernel over every spectrum, inverse batch
 //   combine  n, w, the inverse-transformed fields -> hv, per-term sums of w hv_t
 // Density-only fields (lap sqrt n, K * n^beta, K * n^alpha) stay in "hv:lap", "hv:A", "hv:B" for calls with reuse_density = 1.
-int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev, void* hv_dev, double* quad_terms, int reuse_density,
-                         void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!c) return OFDFT_EINVAL;
-    OFDFT_ON_DEVICE(c, c->device);
-    const bool retained = c->hvp_valid;
-    if (int rc = begin_call(c, st)) return rc;         // (clears hvp_valid: a failed call leaves nothing to reuse)
-    if (!den_dev || !dir_dev || !hv_dev) return fail(c, OFDFT_EINVAL, "null argument");
-    if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
-    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector is served by single-GPU contexts: slab-decomposed contexts have no second derivative");
-    const unsigned mask = c->mask;
+//
+// hvp_core schedules this once for both entries.  ofdft_hessian_vector hands it (n, w); ofdft_hessian_vector_chi hands it
+// (phi, d) with HvpChi set: head and combine then run their chi-space instantiations, which form n and dn on the fly, and the
+// call adds one two-sum sweep over (phi, d) in front and one shift of the output by the constant d mu behind.
+namespace {
+
+// the retained fields belong to the entry that made them: hvp_valid is kHvpNone, kHvpDensity or kHvpChi (every `= false` elsewhere clears it)
+enum { kHvpNone = 0, kHvpDensity = 1, kHvpChi = 2 };
+
+struct HvpChi {                  // chi-space call: nullptr for the n-space product
+    const real* g;               // closure gradient or nullptr (stationary point)
+    double nel;                  // electron number N
+    double a, S, cs;             // phi.d, phi.phi, cs = N / (S dV)
+    double sums[kHvpChiScalars]; // out: sum dv n, g.d, d.P, phi.P (hvp_kernels.h), when `want`
+    bool want;
+};
+
+const char* hvp_refusal(ofdft_ctx* c) {
     static const struct { unsigned bit; const char* name; } refused[] = {
         {OFDFT_WGC99_NL, "wgc99_nl"}, {OFDFT_PBE_X, "pbe_x"}, {OFDFT_PBE_C, "pbe_c"}, {OFDFT_GGA_K, "gga_k"}, {OFDFT_VWGTF, "vwgtf"}, {OFDFT_NLK, "nlk"}};
     for (const auto& r : refused)
-        if (mask & r.bit) return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector: no second derivative of the term %s", r.name);
-    if (wts_active(c))
-        return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector: no second derivative of the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND = 1, wts_kind)");
-    if (reuse_density && !retained)
-        return fail(c, OFDFT_ESTATE, "ofdft_hessian_vector: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set");
-    const bool reuse = reuse_density != 0;
-    const real* den = (const real*)den_dev;
-    const real* w = (const real*)dir_dev;
+        if (c->mask & r.bit) return r.name;
+    return nullptr;
+}
+
+// `first` = n (or phi), `dir` = w (or d), `out` = hv (or H d before the shift).  The caller has run begin_call and the argument checks.
+int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double* quad_terms, bool reuse, HvpChi* chi, hipStream_t st) {
+    const unsigned mask = c->mask;
+    const real* den = first;
+    const real* w = dir;
     const long long npts = c->npts;
     const double inv_n = 1.0 / (double)npts;
     const bool has_h = mask & OFDFT_HARTREE, has_vw = mask & OFDFT_VW, has_wt = mask & OFDFT_WT_NL;
 
     double nel = c->hvp_nel;
-    if (has_wt && !reuse) {                // n0 = mean(den) vol of THIS density: a constant of the differentiation (functionals.py:646-647)
+    if (chi) {
+        nel = chi->nel;                    // sum n dV = N by construction
+    } else if (has_wt && !reuse) {         // n0 = mean(den) vol of THIS density: a constant of the differentiation (functionals.py:646-647)
         double nsum;
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
         nel = nsum * inv_n * c->vol;
@@ -48,16 +58,16 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
     int op[kHvpMaxSpectra];
     int ns = 0;
     real *vh = nullptr, *lap = nullptr, *dlap = nullptr, *A = nullptr, *Cb = nullptr, *B = nullptr, *Ca = nullptr;
-    auto item = [&](const real* in, const char* sname, int o, real* out) -> int {
+    auto item = [&](const real* in, const char* sname, int o, real* out_) -> int {
         if (int rc = spec_ws(c, sname, &spec[ns])) return rc;
         fin[ns] = in;
-        fout[ns] = out;
+        fout[ns] = out_;
         op[ns++] = o;
         return 0;
     };
     if (has_h) {
         if (int rc = real_ws(c, "hv:vh", &vh)) return rc;
-        if (int rc = item(w, "s0", SPEC_HARTREE, vh)) return rc;
+        if (int rc = item(chi ? vh : w, "s0", SPEC_HARTREE, vh)) return rc;      // chi space: the head writes dn into "hv:vh"; transformed in place
     }
     if (has_vw) {
         if (int rc = real_ws(c, "hv:lap", &lap)) return rc;
@@ -80,8 +90,8 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
             if (int rc = item(Ca, "s3", SPEC_LINDHARD, Ca)) return rc;
         }
     }
-    if (has_vw || has_wt) {
-        HvpHeadArgs ha{};
+    if (has_vw || has_wt || (chi && has_h)) {
+        HvpChiHeadArgs ha{};
         ha.n = den;
         ha.w = w;
         ha.chi = lap;  ha.dchi = dlap;
@@ -91,7 +101,14 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
         ha.al = ts.nlp.al;
         ha.be = ts.nlp.be;
         ha.flags = (has_vw ? HVP_VW : 0) | (has_wt ? HVP_WT : 0) | (two ? HVP_WT2 : 0) | (reuse ? HVP_REUSE : 0);
-        OFDFT_LAUNCH(c, st, "hvp_head", hvp_head_kernel, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, ha);
+        if (chi) {
+            ha.cs = chi->cs;
+            ha.k = 2.0 * chi->a / chi->S;
+            ha.dn = vh;
+            OFDFT_LAUNCH(c, st, "hvp_head", hvp_head_kernel<HvpChiHeadArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, ha);
+        } else {
+            OFDFT_LAUNCH(c, st, "hvp_head", hvp_head_kernel<HvpHeadArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, (HvpHeadArgs)ha);
+        }
     }
     if (ns) {
         for (int b0 = 0; b0 < ns; b0 += kBsBatch)
@@ -110,7 +127,7 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
         for (int b0 = 0; b0 < ns; b0 += kBsBatch)
             if (int rc = irfftn_internal_multi(c, spec + b0, fout + b0, std::min(kBsBatch, ns - b0), inv_n, st)) return rc;
     }
-    HvpCombineArgs ca{};
+    HvpChiCombineArgs ca{};
     ca.n = den;
     ca.w = w;
     ca.vh = vh ? vh : den;
@@ -120,21 +137,103 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
     ca.Cb = Cb ? Cb : den;
     ca.B = B ? B : den;
     ca.Ca = Ca ? Ca : den;
-    ca.hv = (real*)hv_dev;
+    ca.hv = out;
     ca.npts = npts;
     ca.mask = mask;
     ca.two = two ? 1 : 0;
     ca.al = ts.nlp.al;
     ca.be = ts.nlp.be;
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
-    OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
-    if (quad_terms) {
-        double sums[kHvpScalars];
-        if (int rc = fetch_partials(c, blocks, kHvpScalars, sums, st)) return rc;
-        for (int t = 0; t < OFDFT_NTERMS; ++t) quad_terms[t] = (t < kHvpScalars && ((mask >> t) & 1)) ? sums[t] * c->dV : 0.0;
+    if (chi) {
+        ca.g = chi->g;
+        ca.cs = chi->cs;
+        ca.k = 2.0 * chi->a / chi->S;
+        ca.c2 = 2.0 * chi->cs * c->dV;
+        OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpChiCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
+        OFDFT_REDUCE(c, st, c->d_partial, blocks, kHvpChiScalars, c->d_reduced);
+        OFDFT_LAUNCH(c, st, "hvp_chi_shift", hvp_chi_shift_kernel, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, first, out, npts,
+                     (const acc_t*)c->d_reduced, (real)c->dV, (real)(1.0 / chi->nel), ca.c2);
+        if (chi->want) HIP_TRY(c, hipMemcpyAsync(c->h_partial, c->d_reduced, sizeof(double) * kHvpChiScalars, hipMemcpyDeviceToHost, st));
+    } else {
+        OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca, c->d_partial);
+        if (quad_terms) {
+            double sums[kHvpScalars];
+            if (int rc = fetch_partials(c, blocks, kHvpScalars, sums, st)) return rc;
+            for (int t = 0; t < OFDFT_NTERMS; ++t) quad_terms[t] = (t < kHvpScalars && ((mask >> t) & 1)) ? sums[t] * c->dV : 0.0;
+        }
     }
     if (int rc = end_call(c, st)) return rc;
-    c->hvp_valid = true;
+    if (chi && chi->want)
+        for (int s = 0; s < kHvpChiScalars; ++s) chi->sums[s] = c->h_partial[s];
+    c->hvp_valid = chi ? kHvpChi : kHvpDensity;
     c->hvp_nel = nel;
+    return OFDFT_OK;
+}
+
+// the checks both entries share, after begin_call; `who` names the entry in the messages
+int hvp_checks(ofdft_ctx* c, const char* who) {
+    if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
+    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no second derivative", who);
+    if (const char* name = hvp_refusal(c)) return fail(c, OFDFT_EINVAL, "%s: no second derivative of the term %s", who, name);
+    if (wts_active(c))
+        return fail(c, OFDFT_EINVAL, "%s: no second derivative of the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND = 1, wts_kind)", who);
+    return 0;
+}
+
+}  // namespace
+
+int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev, void* hv_dev, double* quad_terms, int reuse_density,
+                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    const bool retained = c->hvp_valid == kHvpDensity;
+    if (int rc = begin_call(c, st)) return rc;         // (clears hvp_valid: a failed call leaves nothing to reuse)
+    if (!den_dev || !dir_dev || !hv_dev) return fail(c, OFDFT_EINVAL, "null argument");
+    if (int rc = hvp_checks(c, "ofdft_hessian_vector")) return rc;
+    if (reuse_density && !retained)
+        return fail(c, OFDFT_ESTATE, "ofdft_hessian_vector: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set");
+    return hvp_core(c, (const real*)den_dev, (const real*)dir_dev, (real*)hv_dev, quad_terms, reuse_density != 0, nullptr, st);
+}
+
+// H d in chi space (include/ofdft_hip.h): the derivative of the closure gradient g = 2 c phi (v - mu) dV along d.
+int ofdft_hessian_vector_chi(ofdft_ctx* c, const void* chi_dev, const void* dir_dev, const void* g_dev, double n_electrons, void* out_dev,
+                             double* scalars_host, int reuse_density, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    const bool retained = c->hvp_valid == kHvpChi;
+    const double S_kept = c->hvp_chi_S;
+    if (int rc = begin_call(c, st)) return rc;
+    if (!chi_dev || !dir_dev || !out_dev) return fail(c, OFDFT_EINVAL, "null argument");
+    if (!(n_electrons > 0.0)) return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector_chi: n_electrons must be positive");
+    if (int rc = hvp_checks(c, "ofdft_hessian_vector_chi")) return rc;
+    if (reuse_density && !retained)
+        return fail(c, OFDFT_ESTATE, "ofdft_hessian_vector_chi: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set");
+    const real* phi = (const real*)chi_dev;
+    const real* d = (const real*)dir_dev;
+    // a = phi.d (and S = phi.phi of a new phi): the head kernel needs both before it can form dn
+    const int blocks = grid_for(c->npts / 2 + 1, kRedThreads, kRedBlocks);
+    OFDFT_LAUNCH(c, st, "hvp_chi_dots", hvp_chi_dots_kernel, dim3(blocks), dim3(kRedThreads), 0, phi, d, c->npts, c->d_partial);
+    double pre[2];
+    if (int rc = fetch_partials(c, blocks, 2, pre, st)) return rc;
+    HvpChi x{};
+    x.g = (const real*)g_dev;
+    x.nel = n_electrons;
+    x.a = pre[0];
+    x.S = reuse_density ? S_kept : pre[1];
+    if (!(x.S > 0.0)) return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector_chi: chi is zero everywhere");
+    x.cs = n_electrons / (x.S * c->dV);
+    x.want = scalars_host != nullptr;
+    if (int rc = hvp_core(c, phi, d, (real*)out_dev, nullptr, reuse_density != 0, &x, st)) return rc;
+    c->hvp_chi_S = x.S;
+    if (scalars_host) {
+        const double dmu = (x.sums[0] * c->dV + x.sums[1]) / n_electrons, c2 = 2.0 * x.cs * c->dV;
+        scalars_host[0] = x.sums[2] - c2 * dmu * x.a;      // d . H d
+        scalars_host[1] = x.sums[3] - c2 * dmu * x.S;      // phi . H d
+        scalars_host[2] = x.a;
+        scalars_host[3] = x.S;
+        scalars_host[4] = dmu;
+    }
     return OFDFT_OK;
 }

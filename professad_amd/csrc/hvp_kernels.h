@@ -1,4 +1,5 @@
-// Kernels of the Hessian-vector product hv = d/d eps v[n + eps w] at eps = 0 (ofdft_hessian_vector; fp64, gfx950): one head
+// Kernels of the Hessian-vector product hv = d/d eps v[n + eps w] at eps = 0 (ofdft_hessian_vector and, in chi space,
+// ofdft_hessian_vector_chi; fp64, gfx950): one head
 // kernel that writes every real field to be transformed, one spectral kernel over all spectra of the call, one combine kernel
 // that adds the pointwise terms, writes hv once and reduces the per-term w . hv_t.  The operator forms are those of DESIGN.md
 // ("Hessian-vector products"); the reference obtains them by a second autograd pass (functional_tools.py:34-70).
@@ -13,6 +14,7 @@ enum { HVP_VW = 1, HVP_WT = 2, HVP_WT2 = 4, HVP_REUSE = 8 };
 
 // ---- head: n, w -> the real fields of the active terms (with HVP_REUSE only those that depend on w)
 struct HvpHeadArgs {
+    static constexpr bool kChi = false;
     const real* n;
     const real* w;
     real* chi;  real* dchi;      // sqrt n, w / (2 sqrt n)
@@ -41,12 +43,31 @@ __device__ __forceinline__ HvpHeadPoint hvp_head_point(const HvpHeadArgs& a, rea
     }
     return p;
 }
-static __global__ void hvp_head_kernel(HvpHeadArgs a) {
+// chi-space variant (ofdft_hessian_vector_chi): `n` holds phi and `w` the direction d; the density and its variation are formed
+// on the fly, n = cs phi^2 and dn = 2 cs phi d - k n (k = 2 phi.d / phi.phi, so sum dn = 0), and dn is written once where a
+// transform reads it as it stands (Hartree).  The n-space instantiation carries none of this.
+struct HvpChiHeadArgs : HvpHeadArgs {
+    static constexpr bool kChi = true;
+    real cs, k;
+    real* dn;                    // nullptr: no transform takes dn itself
+};
+__device__ __forceinline__ void hvp_chi_density(real cs, real k, real phi, real d, real& n, real& dn) {
+    n = cs * phi * phi;
+    dn = 2.0 * cs * phi * d - k * n;
+}
+template <class Args>
+static __global__ void hvp_head_kernel(Args a) {
     const bool vw = a.flags & HVP_VW, wt = a.flags & HVP_WT, wt2 = a.flags & HVP_WT2, dens = !(a.flags & HVP_REUSE);
     const long long n2 = a.npts >> 1;
 #define ST2(ptr, u, v) reinterpret_cast<cplx*>(ptr)[i] = mkc(u, v)
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
-        const cplx n = reinterpret_cast<const cplx*>(a.n)[i], w = reinterpret_cast<const cplx*>(a.w)[i];
+        cplx n = reinterpret_cast<const cplx*>(a.n)[i], w = reinterpret_cast<const cplx*>(a.w)[i];
+        if constexpr (Args::kChi) {
+            const cplx phi = n, d = w;
+            hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
+            hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
+            if (a.dn) ST2(a.dn, w.x, w.y);
+        }
         const HvpHeadPoint p0 = hvp_head_point(a, n.x, w.x), p1 = hvp_head_point(a, n.y, w.y);
         if (vw) {
             if (dens) ST2(a.chi, p0.chi, p1.chi);
@@ -64,7 +85,12 @@ static __global__ void hvp_head_kernel(HvpHeadArgs a) {
 #undef ST2
     if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const long long i = a.npts - 1;
-        const HvpHeadPoint p = hvp_head_point(a, a.n[i], a.w[i]);
+        real n = a.n[i], w = a.w[i];
+        if constexpr (Args::kChi) {
+            hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
+            if (a.dn) a.dn[i] = w;
+        }
+        const HvpHeadPoint p = hvp_head_point(a, n, w);
         if (vw) {
             if (dens) a.chi[i] = p.chi;
             a.dchi[i] = p.dchi;
@@ -149,6 +175,7 @@ __device__ __forceinline__ real hvp_corr_second(real n, unsigned mask) {
 
 // ---- combine: n, w and the inverse-transformed fields -> hv, and the per-term sums of w hv_t
 struct HvpCombineArgs {
+    static constexpr bool kChi = false;
     const real* n;
     const real* w;
     const real* vh;                       // F^-1[4 pi w^ / k^2]
@@ -216,26 +243,100 @@ __device__ __forceinline__ real hvp_combine_point(const HvpCombineArgs& a, const
     }
     return hv;
 }
+// chi-space variant: `n` holds phi, `w` the direction d, `hv` the output; per point dv = hv(n, dn) as above, then
+//   P_j = -k g_j + d_j g_j / phi_j + c2 phi_j dv_j        (c2 = 2 cs dV; the quotient counts as 0 where phi_j = 0)
+// is written, and sum dv n, g.d, d.P, phi.P are reduced (kHvpChiScalars, in this order): the constant d mu that still has to
+// come off dv is known only after this sum (hvp_chi_shift_kernel).  g = nullptr stands for a gradient of zeros.
+constexpr int kHvpChiScalars = 4;
+struct HvpChiCombineArgs : HvpCombineArgs {
+    static constexpr bool kChi = true;
+    const real* g;
+    real cs, k, c2;
+};
+__device__ __forceinline__ real hvp_chi_point(const HvpChiCombineArgs& a, real phi, real d, real g, real n, real dv,
+                                              acc_t (&acc)[kHvpChiScalars]) {
+    const real P = (phi != 0.0 ? d * g / phi : 0.0) - a.k * g + a.c2 * phi * dv;
+    acc[0] += dv * n;
+    acc[1] += g * d;
+    acc[2] += d * P;
+    acc[3] += phi * P;
+    return P;
+}
 // (every array pointer is valid: the host points the fields of absent terms at `n`, as for combine_kernel)
-static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(HvpCombineArgs a, acc_t* __restrict__ partial) {
+template <class Args>
+static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a, acc_t* __restrict__ partial) {
     acc_t acc[kHvpScalars];
 #pragma unroll
     for (int s = 0; s < kHvpScalars; ++s) acc[s] = 0.0;
+    acc_t cacc[kHvpChiScalars] = {0.0, 0.0, 0.0, 0.0};
+    (void)cacc;
     const long long n2 = a.npts >> 1;
 #define LD2(ptr) reinterpret_cast<const cplx*>(ptr)[i]
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
-        const cplx n = LD2(a.n), w = LD2(a.w), vh = LD2(a.vh), lp = LD2(a.lap), dl = LD2(a.dlap), A = LD2(a.A), Cb = LD2(a.Cb),
-                   B = LD2(a.B), Ca = LD2(a.Ca);
-        const real h0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc);
-        const real h1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc);
-        reinterpret_cast<cplx*>(a.hv)[i] = mkc(h0, h1);
+        cplx n = LD2(a.n), w = LD2(a.w);
+        const cplx vh = LD2(a.vh), lp = LD2(a.lap), dl = LD2(a.dlap), A = LD2(a.A), Cb = LD2(a.Cb), B = LD2(a.B), Ca = LD2(a.Ca);
+        if constexpr (Args::kChi) {
+            const cplx phi = n, d = w, g = a.g ? LD2(a.g) : mkc(0.0, 0.0);
+            hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
+            hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
+            const real v0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc);
+            const real v1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc);
+            const real h0 = hvp_chi_point(a, phi.x, d.x, g.x, n.x, v0, cacc);
+            const real h1 = hvp_chi_point(a, phi.y, d.y, g.y, n.y, v1, cacc);
+            reinterpret_cast<cplx*>(a.hv)[i] = mkc(h0, h1);
+        } else {
+            const real h0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc);
+            const real h1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc);
+            reinterpret_cast<cplx*>(a.hv)[i] = mkc(h0, h1);
+        }
     }
 #undef LD2
     if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const long long i = a.npts - 1;
-        a.hv[i] = hvp_combine_point(a, HvpPoint{a.n[i], a.w[i], a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc);
+        if constexpr (Args::kChi) {
+            real n, w;
+            hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
+            const real dv = hvp_combine_point(a, HvpPoint{n, w, a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc);
+            a.hv[i] = hvp_chi_point(a, a.n[i], a.w[i], a.g ? a.g[i] : (real)0.0, n, dv, cacc);
+        } else {
+            a.hv[i] = hvp_combine_point(a, HvpPoint{a.n[i], a.w[i], a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc);
+        }
     }
-    block_reduce_store<kHvpScalars>(acc, partial);
+    if constexpr (Args::kChi) block_reduce_store<kHvpChiScalars>(cacc, partial);      // (the per-term sums are not kept: dead code here)
+    else block_reduce_store<kHvpScalars>(acc, partial);
+}
+
+// ---- chi space, before the head: phi.d and phi.phi (fixed order, as every reduction here)
+static __global__ __launch_bounds__(kRedThreads) void hvp_chi_dots_kernel(const real* __restrict__ phi, const real* __restrict__ d,
+                                                                          long long npts, acc_t* __restrict__ partial) {
+    acc_t acc[2] = {0.0, 0.0};
+    const long long n2 = npts >> 1;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        const cplx p = reinterpret_cast<const cplx*>(phi)[i], q = reinterpret_cast<const cplx*>(d)[i];
+        acc[0] += p.x * q.x + p.y * q.y;
+        acc[1] += p.x * p.x + p.y * p.y;
+    }
+    if ((npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        acc[0] += phi[npts - 1] * d[npts - 1];
+        acc[1] += phi[npts - 1] * phi[npts - 1];
+    }
+    block_reduce_store<2>(acc, partial);
+}
+
+// ---- chi space, after the combine: out_j -= c2 phi_j d mu with d mu = (sums[0] dV + sums[1]) / N from the reduced sums of
+// the combine kernel (on the device: the call does not wait for the host in between)
+static __global__ void hvp_chi_shift_kernel(const real* __restrict__ phi, real* __restrict__ out, long long npts,
+                                            const acc_t* __restrict__ sums, real dV, real inv_nel, real c2) {
+    const real s = c2 * ((sums[0] * dV + sums[1]) * inv_nel);
+    const long long n2 = npts >> 1;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        const cplx p = reinterpret_cast<const cplx*>(phi)[i];
+        cplx o = reinterpret_cast<cplx*>(out)[i];
+        o.x -= s * p.x;
+        o.y -= s * p.y;
+        reinterpret_cast<cplx*>(out)[i] = o;
+    }
+    if ((npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[npts - 1] -= s * phi[npts - 1];
 }
 
 }  // namespace ofdft

@@ -540,6 +540,10 @@ class DistEngine:
         raise NotImplementedError('DistEngine.hessian_vector: the Hessian-vector product (ofdft_hessian_vector) is served by '
                                   'single-GPU contexts; slab-decomposed contexts have no second derivative')
 
+    def hessian_vector_chi(self, chi, d, g, n_elec, reuse_density=False, want_scalars=False):
+        raise NotImplementedError('DistEngine.hessian_vector_chi: the Hessian-vector product (ofdft_hessian_vector_chi) is served by '
+                                  'single-GPU contexts; slab-decomposed contexts have no second derivative')
+
     def query(self, what):
         return self.stages.query(what)
 

@@ -184,6 +184,35 @@ class Engine:
                                                   self._stream()), 'ofdft_hessian_vector')
         return (N.per_term(q, self._mask()), out) if want_terms else out
 
+    def hessian_vector_chi(self, chi, d, g, n_elec, reuse_density=False, want_scalars=False, out=None):
+        """The Hessian of the closure's E[chi] applied to the direction ``d``: the derivative of the gradient ``g`` that
+        ``energy_grad_chi`` returns, along ``d`` (ofdft_hessian_vector_chi).  ``chi`` at any scale; ``g`` is that
+        gradient or None at a stationary point (g = 0).  Where chi is exactly zero the term d g / chi counts as zero.
+        -> H d, or with ``want_scalars`` (dict with dHd = d.Hd, phiHd = chi.Hd, a = chi.d, S = chi.chi, dmu; H d).
+        ``reuse_density=True``: ``chi`` holds the values of the previous call made without it; the density-only transforms are
+        skipped and the result is bitwise the same.  Single GPU and fp64, the terms of ``hessian_vector``."""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.hessian_vector_chi: the Hessian-vector product is fp64 work (libofdft_hip.so); '
+                                      'an fp32 engine does not serve it')
+        chi = self._grid_tensor(chi, 'chi')
+        d = self._grid_tensor(d, 'd')
+        g = self._grid_tensor(g, 'g')
+        if out is None:
+            out = torch.empty_like(chi)
+        elif self._grid_tensor(out, 'out') is not out:
+            raise ValueError('out must be a contiguous grid tensor of this engine')
+        s = (C.c_double * N.HVC_NSCALARS)() if want_scalars else None
+        self._check(self.lib.ofdft_hessian_vector_chi(self._ctx, _ptr(chi), _ptr(d), _ptr(g), float(n_elec), _ptr(out), s,
+                                                      1 if reuse_density else 0, self._stream()), 'ofdft_hessian_vector_chi')
+        return (dict(zip(N.HVC_NAMES, s)), out) if want_scalars else out
+
+    @property
+    def volume(self):
+        """cell volume of the last set_cell"""
+        if self._box_key is None:
+            raise RuntimeError('set_cell has not been called')
+        return abs(float(np.linalg.det(np.frombuffer(self._box_key, dtype=np.float64).reshape(3, 3))))
+
     # -- validation entry points
     def rfftn(self, x):
         x = self._grid_tensor(x, 'x')

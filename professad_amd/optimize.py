@@ -16,6 +16,10 @@ two-loop dot products and updates are batched tensor ops on the GPU.
 stored pairs) plus ONE multi-axpy sweep (direction, chi update, gradient copy) -- about 40 grid-sized reads/writes
 instead of the ~135 of the op-by-op form -- while the two-loop recursion itself runs here on the (2m+1) coefficients
 of the direction in the basis {S_j, Y_j, g}.  On several ranks the sweep's local sums need one small all-reduce.
+
+`TruncatedNewton` (`n_method='TN'`, the optimiser PROFESS itself defaults to) and `density_response` are the second-order
+consumers: both solve with the Hessian of E[chi] by conjugate gradients whose vectors live behind `ofdft_cg_*` and whose
+products are `ofdft_hessian_vector_chi` (`HipCgBackend`, `solve_projected`).  Single GPU, fp64.
 """
 import ctypes as C
 import math
@@ -420,8 +424,188 @@ class TwoPointGradientDescent:
         return loss
 
 
+# ------------------------------------------------------------------------------------------------ second order
+CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_CURVATURE = 0, 1, 2, 3      # exit reasons of a solve (OFDFT_CG_*; _native.CG_REASONS)
+_UNSERVED = ('wgc99_nl', 'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk')    # terms without a second derivative (ofdft_hessian_vector)
+
+
+def second_order_refusal(engine):
+    """None, or why the engine cannot serve Hessian-vector products in chi (what ofdft_hessian_vector_chi itself refuses)"""
+    from . import _native as N
+    if getattr(engine, 'comm', None) is not None:
+        return 'the Hessian-vector product is served by single-GPU contexts; a slab-decomposed DistEngine has no second derivative'
+    if engine.dtype != torch.double:
+        return 'the Hessian-vector product is fp64 work (libofdft_hip.so); an fp32 engine does not serve it'
+    mask = engine._mask()
+    for name in _UNSERVED:
+        if mask & N.TERM_BITS[name]:
+            return 'no second derivative of the term %s' % name
+    if mask & N.TERM_BITS['wt_nl'] and np.frombuffer(engine._terms_key[1], dtype=np.float64)[12] != 0.0:
+        return 'no second derivative of the stabilised Wang-Teter style functional (wts_kind)'
+    return None
+
+
+def _vp(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class HipCgBackend:
+    """Conjugate gradients for P H P x = b on the device (ofdft_cg_* and ofdft_hessian_vector_chi in libofdft_hip.so; no CPU
+    fallback): x, r, p, q live behind the handle, the engine's product reads p and writes q in place."""
+
+    def __init__(self, engine):
+        why = second_order_refusal(engine)
+        if why:
+            raise NotImplementedError(why)
+        self.eng, self.lib = engine, engine.lib
+        self.dV = engine.volume / engine.npts
+        self._h = C.c_void_p(0)
+        rc = self.lib.ofdft_cg_create(C.byref(self._h), engine.npts, engine._dev_index)
+        if rc != 0:
+            raise RuntimeError('ofdft_cg_create failed with code %d' % rc)
+        self._p, self._q = C.c_void_p(0), C.c_void_p(0)
+        self._check(self.lib.ofdft_cg_vectors(self._h, None, None, C.byref(self._p), C.byref(self._q)), 'ofdft_cg_vectors')
+        self._scal = (C.c_double * 5)()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (what, rc, self.lib.ofdft_cg_last_error(self._h).decode()))
+
+    def start(self, phi, b, rtol, maxiter):
+        e = self.eng
+        phi, b = e._grid_tensor(phi, 'chi'), e._grid_tensor(b, 'b')          # (held until the call returns)
+        self._check(self.lib.ofdft_cg_start(self._h, _vp(phi), _vp(b), float(rtol), int(maxiter), None, e._stream()), 'ofdft_cg_start')
+
+    def product(self, phi, g, n_elec, reuse):
+        """q = H p -> (p.q, phi.q)"""
+        e = self.eng
+        phi, g = e._grid_tensor(phi, 'chi'), e._grid_tensor(g, 'g')
+        e._check(self.lib.ofdft_hessian_vector_chi(e._ctx, _vp(phi), self._p, _vp(g), float(n_elec), self._q, self._scal,
+                                                   1 if reuse else 0, e._stream()), 'ofdft_hessian_vector_chi')
+        return self._scal[0], self._scal[1]
+
+    def step(self, phi, p_dot_q, phi_dot_q):
+        reason = C.c_int(0)
+        phi = self.eng._grid_tensor(phi, 'chi')
+        self._check(self.lib.ofdft_cg_step(self._h, _vp(phi), float(p_dot_q), float(phi_dot_q), C.byref(reason), self.eng._stream()),
+                    'ofdft_cg_step')
+        return reason.value
+
+    def status(self):
+        it, reason, rel = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        self._check(self.lib.ofdft_cg_status(self._h, C.byref(it), C.byref(reason), C.byref(rel)), 'ofdft_cg_status')
+        return it.value, reason.value, rel.value
+
+    def solution(self):
+        x = torch.empty(self.eng.shape, dtype=self.eng.dtype, device=self.eng._dev_exact)
+        self._check(self.lib.ofdft_cg_solution(self._h, C.c_void_p(x.data_ptr()), self.eng._stream()), 'ofdft_cg_solution')
+        return x
+
+    def hv(self, den, w):
+        return self.eng.hessian_vector(den, w)
+
+    def close(self):
+        if self._h:
+            self.lib.ofdft_cg_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_projected(backend, phi, g, b, n_elec, rtol, maxiter):
+    """Conjugate gradients for P H P x = b at phi (P = I - phi phi^T / phi.phi; g: the closure gradient there, None at a stationary
+    point) until |r| <= rtol |b|, `maxiter` iterations or non-positive curvature.  The first product runs with reuse_density = 0,
+    the others with 1.  -> (x, iterations, exit reason CG_*, |r| / |b|, products)"""
+    backend.start(phi, b, rtol, maxiter)
+    _it, reason, _rel = backend.status()
+    products = 0
+    while reason == CG_RUNNING:
+        pq, phiq = backend.product(phi, g, n_elec, products > 0)
+        products += 1
+        reason = backend.step(phi, pq, phiq)
+    iters, reason, rel = backend.status()
+    return backend.solution(), iters, reason, rel, products
+
+
+class TruncatedNewton:
+    """Line-search truncated Newton on chi (the optimiser PROFESS itself defaults to), on a backend that solves the projected
+    Newton equation (`HipCgBackend`).  Per outer step: conjugate gradients for P H P x = -g down to the forcing term
+    |r| < min(0.5, sqrt|g|) |g| or `cg_maxiter` iterations, leaving at non-positive curvature with the current x (the steepest
+    descent direction if that happens at once); then Armijo backtracking on the closure energy from t = 1 (halving, c1 = 1e-4,
+    at most 20 trials; an energy within a few roundings of the bound passes, so that the last, tiny steps are not lost to the
+    noise of the energy sum).  The accepted trial's energy and gradient open the next step: one evaluation per step when the full
+    step is taken.  A step at |g|_2 <= `tolerance_grad` does nothing."""
+
+    def __init__(self, x, backend, n_elec, cg_maxiter=50, tolerance_grad=1e-10, c1=1e-4, max_trials=20):
+        self.x, self.b, self.n_elec = x, backend, float(n_elec)
+        self.cg_maxiter, self.tol_g, self.c1, self.max_trials = int(cg_maxiter), float(tolerance_grad), float(c1), int(max_trials)
+        self.func_evals = self.hvp_count = self.total_iter = 0
+        self.cg_log = []                 # per solve: (products, exit reason, |g|_2 before it)
+        self._at = None                  # (E, g) at the current x
+
+    def step(self, closure):
+        """closure() -> (E, gradient) at the current x, which is updated in place.  Returns the energy before the step."""
+        if self._at is None:
+            self._at = closure()
+            self.func_evals += 1
+        E, g = self._at
+        gnorm = math.sqrt(float((g * g).sum()))
+        if not gnorm > self.tol_g:
+            return E
+        dx, _it, reason, _rel, nprod = solve_projected(self.b, self.x, g, -g, self.n_elec, min(0.5, math.sqrt(gnorm)), self.cg_maxiter)
+        self.hvp_count += nprod
+        self.cg_log.append((nprod, reason, gnorm))
+        gtd = float((g * dx).sum())
+        if not gtd < 0.0:                # (cannot happen with a positive definite projected Hessian; never walk uphill)
+            dx, gtd = -g, -gnorm * gnorm
+        x0 = self.x + 0.0
+        slack = 4.0 * np.finfo(np.float64).eps * abs(E)
+        t = 1.0
+        for _trial in range(self.max_trials):
+            self.x[...] = x0 + t * dx
+            Et, gt = closure()
+            self.func_evals += 1
+            if Et <= E + self.c1 * t * gtd + slack:
+                self._at = (Et, gt)
+                break
+            t *= 0.5
+        else:                            # no acceptable step: stay where the step began; the closure's last call belongs to that point
+            self.x[...] = x0
+            self._at = closure()
+            self.func_evals += 1
+        self.total_iter += 1
+        return E
+
+
+def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=None):
+    """First-order change of the ground-state density under a perturbation `dv` of the external potential, at the ground state
+    `chi` (any scale) of the engine's terms: the implicit derivative of the minimiser, one conjugate-gradient solve with the
+    Hessian of E[chi],  P H P dchi = -2 c chi (dv - sum(dv n) dV / N) dV  with g = 0.  Returns a dict with dn = 2 c chi dchi
+    (sum dn = 0), dmu = sum n (hv(n, dn) + dv) dV / N, the iteration count, the relative residual and the exit reason.
+    Single GPU, fp64 and the terms `Engine.hessian_vector` serves; anything else raises NotImplementedError.  (`backend`: another
+    solver with HipCgBackend's methods -- the tests' numpy double.)"""
+    b = backend if backend is not None else HipCgBackend(engine)
+    dV = b.dV
+    S = float((chi * chi).sum())
+    c = n_elec / (S * dV)
+    n = c * chi * chi
+    shift = float((dv * n).sum()) * dV / n_elec
+    rhs = (-2.0 * c * dV) * chi * (dv - shift)
+    dchi, iters, reason, rel, nprod = solve_projected(b, chi, None, rhs, n_elec, rtol, maxiter)
+    dn = 2.0 * c * chi * dchi
+    dmu = float((n * (b.hv(n, dn) + dv)).sum()) * dV / n_elec
+    if backend is None:
+        b.close()
+    return dict(dn=dn, dmu=dmu, iterations=iters, rel_residual=rel, reason=reason, hvp_count=nprod)
+
+
 def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_cond_count=3, n_step_size=0.1,
-                     n_maxiter=1000, conv_target='dE', verbose=False, volume=None, optimizer='fused', n_method='LBFGS'):
+                     n_maxiter=1000, conv_target='dE', verbose=False, volume=None, optimizer='fused', n_method='LBFGS',
+                     tn_cg_maxiter=50, tn_gtol=1e-10):
     """Minimise E[n = N_e chi^2 / int chi^2] with the engine's terms.  Returns a dict with the converged density,
     chi, energy [Ha], iteration count and the convergence history.
 
@@ -431,11 +615,19 @@ def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_con
     System.optimize_density does after System.__init__).  `optimizer`: 'fused' (HIP sweeps, `VectorFreeLBFGS`) or
     'torch' (`FixedStepLBFGS` on torch tensors; single GPU only).
     With an fp32 engine the energies carry ~1e-6 relative round-off: choose `ntol` above that noise (the default 1e-7 eV
-    suits fp64) or the loop runs to `n_maxiter`."""
+    suits fp64) or the loop runs to `n_maxiter`.
+    `n_method`: 'LBFGS', 'TPGD' (the reference's two) or 'TN', truncated Newton (`TruncatedNewton`: at most `tn_cg_maxiter`
+    Hessian-vector products per Newton equation, no step once |g|_2 <= `tn_gtol`); 'TN' needs a single-GPU fp64 `Engine` whose
+    terms all have a second derivative, and raises NotImplementedError otherwise.  The result's `hvp_count` is the number of
+    Hessian-vector products taken (0 for the other methods)."""
     if conv_target not in ('dE', 'dEdchi', 'euler'):
         raise ValueError("Only 'dE', 'dEdchi' or 'euler' recognized as 'conv_target' argument")       # system.py:889-890
-    if n_method not in ('LBFGS', 'TPGD'):
-        raise ValueError("Only 'LBFGS' or 'TPGD' recognized for 'n_method' argument")                 # system.py:826
+    if n_method not in ('LBFGS', 'TPGD', 'TN'):
+        raise ValueError("Only 'LBFGS', 'TPGD' or 'TN' recognized for 'n_method' argument")           # system.py:826
+    if n_method == 'TN':
+        why = second_order_refusal(engine)
+        if why:
+            raise NotImplementedError("n_method='TN': " + why)
     if conv_target != 'dE' and volume is None:
         raise ValueError("conv_target=%r needs `volume` (the cell volume fixes dV)" % conv_target)
     comm = getattr(engine, 'comm', None)                    # DistEngine
@@ -474,7 +666,9 @@ def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_con
             state['chi_c'].copy_(chi)
         return state['E'], g
 
-    if n_method == 'TPGD':          # system.py:823-824
+    if n_method == 'TN':
+        opt = TruncatedNewton(chi, HipCgBackend(engine), n_elec, cg_maxiter=tn_cg_maxiter, tolerance_grad=tn_gtol)
+    elif n_method == 'TPGD':        # system.py:823-824
         hook = (lambda v: comm.all_reduce_sum(np.ascontiguousarray(v, dtype=np.float64), dev)) if multi else None
         opt = TwoPointGradientDescent(chi, lr=n_step_size, all_reduce=hook)
     elif optimizer == 'fused':      # device-resident history, two sweeps per inner iteration
@@ -518,5 +712,8 @@ def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_con
     E_terms, mu, g = engine.energy_grad_chi(chi, n_elec, vext)
     ntilde = gsum(float((chi.double() * chi.double()).sum())) / npts_global * (volume if volume is not None else 1.0)
     den = (n_elec / ntilde) * chi * chi if volume is not None else None
+    if n_method == 'TN':
+        opt.b.close()
     return dict(chi=chi, den=den, E_Ha=sum(E_terms.values()), E_terms=E_terms, mu=mu, iterations=it,
-                converged=conv == n_conv_cond_count, history=history, func_evals=opt.func_evals)
+                converged=conv == n_conv_cond_count, history=history, func_evals=opt.func_evals,
+                hvp_count=getattr(opt, 'hvp_count', 0))
