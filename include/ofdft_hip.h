@@ -333,6 +333,42 @@ int  ofdft_ion_ion_cells(ofdft_ctx* ctx, const double* frac_coords_host, const d
                          double Rd, int part, int nparts, double* E_host, double* forces_host /* [nions][3] or NULL */,
                          double* stress_host /* [9] or NULL */, void* stream);
 
+/* ---- second derivatives with respect to ion positions: the pieces of the interatomic force constants ----
+ * System.force_constants (system.py:695-717, 1340-1367) differentiates the forces F = -dE_tot/dR at the relaxed density once
+ * more by autograd:  Phi[p,b] = -dF_p/dR_b = Phi_ion-ion[p,b] + delta_pb D[p] - F_ie[dn_(p,i)][b], with dn_(p,i) the
+ * ground-state density response (a conjugate-gradient solve with ofdft_hessian_vector_chi) to dv = d v_ext / d R_{p,i} and F_ie
+ * the linear map of ofdft_ion_electron_forces.  The three entries below supply dv, D and Phi_ion-ion.  fp64 and single GPU;
+ * the fp32 library and slab-decomposed contexts return OFDFT_EINVAL.  Each clears the fields ofdft_hessian_vector[_chi] retain.
+ * No atomics: bitwise reproducible.
+ *
+ * ofdft_ionic_potential_gradient: the three grids d v_ext / d R_{a,x|y|z} of the ion a = ion_index of one species,
+ *     d v_ext / d R_{a,j} (r) = irfftn(-i k_j exp(-i k.R_a) v~(|k|), norm='forward') / vol,
+ * into dv_dev [3][n0][n1][n2]: the Jacobian autograd takes through lattice_sum + structure_factor (ion_utils.py:88-137), with
+ * the c2r semantics of ofdft_ionic_potential (imaginary parts at the self-conjugate k_z dropped).  Table arguments as there.
+ * One spectral kernel (phase and table value once per k-point), one batched inverse transform of three spectra.
+ * pme_order != 0 returns OFDFT_EINVAL, the message naming PME: the derivative of the B-spline spread is not built. */
+int  ofdft_ionic_potential_gradient(ofdft_ctx* ctx, const double* frac_coords_host, int nions, const double* table_k_host,
+                                    const double* table_v_host, int ntable, double z_ion, int pme_order, int ion_index,
+                                    void* dv_dev /* [3][n0][n1][n2] */, void* stream);
+
+/* D[a] = d^2 (dV sum_r n v_ext) / dR_a dR_a at fixed density for every ion of one species -- the diagonal blocks of the Hessian
+ * of U(R) = IonElectron(box, den, v_ext(R)) (functionals.py IonElectron over lattice_sum, ion_utils.py:88-137; the off-diagonal
+ * blocks vanish: v_ext is a sum over ions),
+ *     D[a]_ij = -(dV / vol) sum_k w_k v~(|k|) k_i k_j Re(exp(-i k.R_a) conj(n^_k)),   w_k = the half-spectrum multiplicities.
+ * curv_host [nions][6]: xx, yy, zz, xy, xz, yz (Ha/bohr^2).  One transform of the density, one reduction kernel.  PME refused. */
+int  ofdft_ion_electron_curvature(ofdft_ctx* ctx, const void* den_dev, const double* frac_coords_host, int nions,
+                                  const double* table_k_host, const double* table_v_host, int ntable, double z_ion,
+                                  int pme_order, double* curv_host /* [nions][6] */, void* stream);
+
+/* Second derivative of the ion-ion pair sum for the ions p of rows_host: hess_host [nrows][nions][3][3] = d^2 E / dR_p dR_b
+ * (Ha/bohr^2) at a fixed pair list -- a second autograd pass over ion_interaction_sum (ion_utils.py:293-333); the background term
+ * depends on the neighbour charge counts only and drops out.  Rd / Rc and the pair set 0 < r <= Rc are those of ofdft_ion_ion.
+ * With f(r) = Z_p Z_b erfc(r/Rd)/r and T(d) = (f'' - f'/r) d d^T / r^2 + (f'/r) I: block b != p is -sum over shifts of T, the
+ * diagonal block +sum over b != p and shifts (an ion's own images move with it).  A block depends on (p, b) and the geometry
+ * only: any subset of rows returns the same bits. */
+int  ofdft_ion_ion_hessian(ofdft_ctx* ctx, const double* frac_coords_host, const double* charges_host, int nions, double Rc,
+                           const int* rows_host, int nrows, double* hess_host /* [nrows][nions][3][3] */, void* stream);
+
 /* ---- limited-memory BFGS building blocks (the consumer of the closure) ----------------
  * The reference's fixed-step optimiser (_optimizers/lbfgs/lbfgsnew.py:594-663) forms y = g - g_prev and s = t d, keeps
  * the pair if y.s > 1e-10 |s|^2, and gets the direction from the two-loop recursion: 2m dependent dot / axpy pairs over

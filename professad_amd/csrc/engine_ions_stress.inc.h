@@ -453,16 +453,10 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void* den_dev, const double* f
     return OFDFT_OK;
 }
 
-// Ion-ion interaction energy, forces and stress (ion_utils.py:293-333 with the parameter heuristics of
-// System.__ion_ion_interaction, system.py:733-754; forces / stress = what autograd yields, system.py:913-935).
-// Rc <= 0 selects the reference's default (Rd = 2 h_max, Rc = 3 Rd^2 / h_max); forces_host [nions][3] and
-// stress_host [9] may be NULL.
-int ofdft_ion_ion(ofdft_ctx* c, const double* frac_host, const double* charges_host, int nions, double Rc, double* E_host,
-                  double* forces_host, double* stress_host, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!c || !frac_host || !charges_host || !E_host || nions < 1) return OFDFT_EINVAL;
-    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
-    OFDFT_ON_DEVICE(c, c->device);
+// Parameters and geometry of the direct pair scan, shared by ofdft_ion_ion and ofdft_ion_ion_hessian: Rd / Rc of
+// System.__ion_ion_interaction (system.py:744-750; Rc <= 0 selects its default), Cartesian coordinates, and the box of lattice
+// shifts that holds every pair within Rc.  Returns the number of shifts.
+static long long ion_ion_setup(ofdft_ctx* c, const double* frac_host, int nions, double Rc, IonIonGeom& g, std::vector<double>& cart) {
     const double* B = c->box;
     // interplanar spacings h_d = 1 / |row d of inv(B^T)| = vol / |cross of the other two lattice vectors|
     double h[3];
@@ -480,11 +474,10 @@ int ofdft_ion_ion(ofdft_ctx* c, const double* frac_host, const double* charges_h
     } else {
         Rd = std::sqrt(h_max * Rc / 3.0);
     }
-    IonIonGeom g{};
     std::memcpy(g.box, B, sizeof(g.box));
     g.Rc = Rc;
     g.Rd = Rd;
-    std::vector<double> cart(3 * (size_t)nions);
+    cart.resize(3 * (size_t)nions);
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int a = 0; a < nions; ++a)
         for (int d = 0; d < 3; ++d) {
@@ -497,6 +490,23 @@ int ofdft_ion_ion(ofdft_ctx* c, const double* frac_host, const double* charges_h
         g.nmax[d] = (int)std::ceil(Rc / h[d] + (hi[d] - lo[d]));
         nshift *= 2 * g.nmax[d] + 1;
     }
+    return nshift;
+}
+
+// Ion-ion interaction energy, forces and stress (ion_utils.py:293-333 with the parameter heuristics of
+// System.__ion_ion_interaction, system.py:733-754; forces / stress = what autograd yields, system.py:913-935).
+// Rc <= 0 selects the reference's default (Rd = 2 h_max, Rc = 3 Rd^2 / h_max); forces_host [nions][3] and
+// stress_host [9] may be NULL.
+int ofdft_ion_ion(ofdft_ctx* c, const double* frac_host, const double* charges_host, int nions, double Rc, double* E_host,
+                  double* forces_host, double* stress_host, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c || !frac_host || !charges_host || !E_host || nions < 1) return OFDFT_EINVAL;
+    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    OFDFT_ON_DEVICE(c, c->device);
+    IonIonGeom g{};
+    std::vector<double> cart;
+    const long long nshift = ion_ion_setup(c, frac_host, nions, Rc, g, cart);
+    const double Rd = g.Rd;
     const long long total = nshift * nions;
     const int chunks = (int)std::min<long long>(256, (total + kRedThreads * 8 - 1) / (kRedThreads * 8));
     double *d_cart, *d_z, *d_part;

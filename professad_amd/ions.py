@@ -216,3 +216,96 @@ def ion_ion(engine, box_vecs, frac, charges, Rc=None, Rd=None, method='direct', 
                                   engine._stream())
     engine._check(rc, 'ofdft_ion_ion')
     return E.value, F, S.reshape(3, 3)
+
+
+# ---------------------------------------------------------------------------------------------------- second derivatives
+def _species_arrays(frac, tab):
+    ks, v, z = tab
+    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
+    ks = np.ascontiguousarray(ks, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if ks.shape != v.shape or ks.ndim != 1:
+        raise ValueError('table k and v must be 1-D arrays of equal length')
+    return frac, ks, v, float(z)
+
+
+def locate_ion(species, ion):
+    """(species index, index within it) of the global ion index `ion` = position in the concatenation of the species"""
+    ion = int(ion)
+    left = ion
+    for s, (frac, _tab) in enumerate(species):
+        n = int(np.asarray(torch.as_tensor(frac).shape).prod()) // 3
+        if 0 <= left < n:
+            return s, left
+        left -= n
+    raise IndexError('ion index %d outside the %d ions of the species list' % (ion, ion - left))
+
+
+def ionic_potential_gradient(engine, box_vecs, species, ion, pme_order=None):
+    """d v_ext / d R_{ion, x|y|z} on the engine's grid -> [3, n0, n1, n2] (`ofdft_ionic_potential_gradient`: what autograd
+    through lattice_sum yields, ion_utils.py:88-137).  `ion` counts over the concatenated species.  Exact structure factor only:
+    a `pme_order` raises NotImplementedError (the derivative of the particle-mesh-Ewald spread is not built).  Plain fp64 work:
+    an fp32 engine hands it to its fp64 sibling and gets the grids narrowed."""
+    if pme_order:
+        raise NotImplementedError('ionic_potential_gradient: particle-mesh Ewald (PME, pme_order=%r) is not served; '
+                                  'use the exact structure factor (pme_order=None)' % (pme_order,))
+    s, a = locate_ion(species, ion)
+    want = engine.dtype
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    frac, ks, v, z = _species_arrays(*species[s])
+    out = torch.empty((3,) + tuple(engine.shape), dtype=torch.double, device=engine._dev_exact)
+    dp = C.POINTER(C.c_double)
+    rc = engine.lib.ofdft_ionic_potential_gradient(engine._ctx, frac.ctypes.data_as(dp), frac.shape[0], ks.ctypes.data_as(dp),
+                                                   v.ctypes.data_as(dp), ks.size, z, 0, a, C.c_void_p(out.data_ptr()), engine._stream())
+    engine._check(rc, 'ofdft_ionic_potential_gradient')
+    return out.to(want)
+
+
+def ion_electron_curvature(engine, box_vecs, den, species, pme_order=None):
+    """D[a] = d^2 (int n v_ext) / dR_a dR_a at fixed density for every ion, species by species -> list of [n, 3, 3] arrays
+    (Ha/bohr^2; `ofdft_ion_electron_curvature`: the diagonal blocks of the Hessian of IonElectron over lattice_sum, whose
+    off-diagonal blocks vanish).  fp64 engines only: the density is the engine's own, as for `Engine.stress`."""
+    if pme_order:
+        raise NotImplementedError('ion_electron_curvature: particle-mesh Ewald (PME, pme_order=%r) is not served; '
+                                  'use the exact structure factor (pme_order=None)' % (pme_order,))
+    if engine.dtype != torch.double:
+        raise NotImplementedError('ion_electron_curvature is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+    den = engine._grid_tensor(den, 'den')
+    engine.set_cell(box_vecs)
+    dp = C.POINTER(C.c_double)
+    out = []
+    for frac, tab in species:
+        frac, ks, v, z = _species_arrays(frac, tab)
+        c6 = np.zeros((frac.shape[0], 6))
+        rc = engine.lib.ofdft_ion_electron_curvature(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
+                                                     ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, z, 0, c6.ctypes.data_as(dp),
+                                                     engine._stream())
+        engine._check(rc, 'ofdft_ion_electron_curvature')
+        D = np.empty((frac.shape[0], 3, 3))
+        for k, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            D[:, i, j] = D[:, j, i] = c6[:, k]
+        out.append(D)
+    return out
+
+
+def ion_ion_hessian(engine, box_vecs, frac, charges, rows, Rc=None):
+    """d^2 E_ion-ion / dR_p dR_b for p in `rows` -> [len(rows), n, 3, 3] (Ha/bohr^2): a second autograd pass over
+    ion_interaction_sum (ion_utils.py:293-333) at a fixed pair list, with the Rd / Rc rules and the pair set of
+    `ion_ion(method='direct')` (`ofdft_ion_ion_hessian`).  Plain fp64 work: an fp32 engine hands it to its fp64 sibling."""
+    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
+    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
+    if z.size != frac.shape[0]:
+        raise ValueError('one charge per ion')
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+    if rows.size == 0 or rows.min() < 0 or rows.max() >= frac.shape[0]:
+        raise ValueError('rows must name at least one ion, each in [0, %d)' % frac.shape[0])
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    dp = C.POINTER(C.c_double)
+    H = np.zeros((rows.size, frac.shape[0], 3, 3))
+    rc = engine.lib.ofdft_ion_ion_hessian(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
+                                          float(Rc) if Rc else 0.0, rows.ctypes.data_as(C.POINTER(C.c_int)), rows.size,
+                                          H.ctypes.data_as(dp), engine._stream())
+    engine._check(rc, 'ofdft_ion_ion_hessian')
+    return H
