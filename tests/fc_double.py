@@ -5,6 +5,7 @@ device results can be compared on grids that have no golden (tests/test_force_co
 professad_amd imports it.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -16,6 +17,17 @@ from oracle import ions as O
 from oracle.closed_form import recip
 
 PAIRS6 = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))
+
+
+def two_species(seed):
+    """three ions of two species -- the recpot of tests/golden/ions.npz and a made-up second one with half the potential, as in
+    tests/test_force_constants_gpu.py -- with fractional coordinates partly outside [0, 1)"""
+    from professad_amd.ions import recpot_table
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ions.npz'))
+    tab = recpot_table(g['recpot_raw'], float(g['recpot_kmax']))
+    tab2 = (tab[0], 0.5 * tab[1], 0.5 * tab[2])
+    rng = np.random.default_rng(seed)
+    return [(rng.random((1, 3)), tab), (rng.random((2, 3)) * 1.5 - 0.25, tab2)]
 
 
 def table_on_grid(tab, kabs):

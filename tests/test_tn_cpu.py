@@ -119,15 +119,7 @@ def test_density_response_matches_the_golden(ground_state):
 
 def test_solver_exit_reasons():
     """iteration cap and non-positive curvature as solve_projected reports them (a 2 x 2 x 2 grid with a made-up operator)"""
-    class Diag(T.NumpyCgBackend):
-        def __init__(self, diag):
-            self.h, self.dV, self.products = diag, 1.0, 0
-
-        def product(self, phi, g, n_elec, reuse):
-            assert reuse == (self.products > 0)
-            self.q = self.h * self.p
-            self.products += 1
-            return float((self.p * self.q).sum()), float((phi * self.q).sum())
+    Diag = T.DiagCgBackend
     phi = np.ones((2, 2, 2))
     b = np.arange(8.0).reshape(2, 2, 2) - 3.5
     x, it, reason, rel, nprod = optimize.solve_projected(Diag(np.linspace(1, 2, 8).reshape(2, 2, 2)), phi, None, b, 1.0, 1e-12, 2)

@@ -2,7 +2,9 @@
 engine_hvp.inc.h) on top of tests/hvp_double.py, and a numpy backend with HipCgBackend's methods
 (professad_amd/csrc/cg_abi.h restated), so that the host logic of optimize.TruncatedNewton, optimize.solve_projected and
 optimize.density_response runs without a device (tests/test_tn_cpu.py) and the device product can be compared on grids that
-have no golden (tests/test_tn_gpu.py).  Not the product: nothing in professad_amd imports it.
+have no golden (tests/test_tn_gpu.py, tests/test_second_order_extents_gpu.py); DiagCgBackend puts the same sweeps around a made-up
+diagonal operator, the yardstick of the solver's own test (tests/test_cg_sweeps_gpu.py).  Not the product: nothing in professad_amd
+imports it.
 """
 import numpy as np
 
@@ -74,8 +76,12 @@ class NumpyCgBackend:
         elif self.iters >= self.maxiter:
             self.reason = CG_MAXITER
         else:
-            self.p = (self.r - phi * (float((phi * self.r).sum()) / self.S)) + (self.rr / rr_old) * self.p
+            self.direction(phi, rr_old)
         return self.reason
+
+    def direction(self, phi, rr_old):
+        """the direction sweep of a step, alone: p = P r + (r.r / r.r of the iteration before) p"""
+        self.p = (self.r - phi * (float((phi * self.r).sum()) / self.S)) + (self.rr / rr_old) * self.p
 
     def status(self):
         return self.iters, self.reason, (np.sqrt(self.rr / self.bb) if self.bb > 0 else 0.0)
@@ -85,3 +91,35 @@ class NumpyCgBackend:
 
     def hv(self, den, w):
         return D.hessian_vector(self.box, den, w, self.terms, self.al, self.be)[1]
+
+
+def diag_inputs(n, seed=0):
+    """phi, b, h of the made-up diagonal problem: magnitudes uniform in [0.5, 1.5], random signs for b, positive phi and h"""
+    rng = np.random.default_rng(1000003 * seed + n)
+    phi, h = 0.5 + rng.random(n), 0.5 + rng.random(n)
+    b = (0.5 + rng.random(n)) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    return phi, b, h
+
+
+class DiagCgBackend(NumpyCgBackend):
+    """the same sweeps around a made-up operator q = h * p with a fixed diagonal h: any vector length, no grid
+    (tests/test_cg_sweeps_gpu.py drives ofdft_cg_* with the same operator)"""
+
+    def __init__(self, diag):
+        self.h, self.dV, self.products = diag, 1.0, 0
+
+    def product(self, phi, g, n_elec, reuse):
+        assert reuse == (self.products > 0)
+        self.q = self.h * self.p
+        self.products += 1
+        return float((self.p * self.q).sum()), float((phi * self.q).sum())
+
+    def seed(self, x, r, p, q, S, bb, rr, iters, rtol=0.0, maxiter=1 << 30):
+        """the state in front of one `step`, taken from elsewhere (a device solver's): that step is then judged alone"""
+        self.x, self.r, self.p, self.q = x, r, p, q
+        self.S, self.bb, self.rr, self.iters = S, bb, rr, iters
+        self.rtol, self.maxiter, self.reason = rtol, maxiter, CG_RUNNING
+        return self
+
+    def hv(self, den, w):
+        raise NotImplementedError('a made-up operator has no density')
