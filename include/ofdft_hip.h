@@ -198,12 +198,31 @@ int  ofdft_set_collectives(ofdft_ctx* ctx, ofdft_all_to_all_fn all_to_all, ofdft
  * Rank r of P owns the real-space x-slab [n0/P][n1][n2].  The evaluation is cut at the four points where the
  * spectra change between the x-slab geometry (z, y passes) and the y-slab geometry (x pass); at each one the
  * engine's kernels leave the spectra in sendbuf in the exchange layout, the HOST does one equal-split all-to-all
- * (RCCL through torch.distributed) from sendbuf to recvbuf, and the next stage's kernels read recvbuf directly.
+ * (RCCL through torch.distributed) from sendbuf to recvbuf, and the next step's kernels read recvbuf directly.
  * The work is two independent chains (0: density / Hartree / vW / PBE, 1: nonlocal KEDF) with their own buffers, so
- * one chain's all-to-all can be in flight while the other chain computes.  Sequence per evaluation:
+ * one chain's all-to-all can be in flight while the other chain computes.
+ * The exchange buffers are chunk-major -- [chunk][peer][xl][array][...] over K = ofdft_query(OFDFT_Q_XCHG_CHUNKS) ranges of kz
+ * blocks -- so chunk k of an exchange is one contiguous equal-split all-to-all message, and an exchange also overlaps the kernels
+ * of its OWN chain ("overlap by z-chunks"; the reference is single-device, _optimizers/lbfgs/lbfgsnew.py:31-33, so
+ * this has no counterpart there).  Per chain, ofdft_dist_step(step, chain, chunk), each step for chunk = 0 .. K-1 in order:
+ *     1  [chunk 0: z kernels]  y-forward of the chunk into the send buffer                  -> exchange of the chunk
+ *     2  fused x passes of the chunk, receive buffer -> send buffer                          -> exchange of the chunk
+ *     3  y-inverse of the chunk out of the receive buffer
+ *     4  [chunk 0: whole-row kernels (GGA mid stage, WGC99 combine)]  y-forward of the flux  -> exchange (chain 0 with a GGA term)
+ *     5  fused x pass of the divergence                                                      -> exchange of the chunk
+ *     6  y-inverse of the divergence chunk
+ * then ofdft_dist_finish.  A call out of this order -- or chain 1 before step 1 of chain 0, or ofdft_dist_finish before step 6
+ * of both chains -- returns OFDFT_ESTATE and runs nothing; the next ofdft_dist_begin starts from a clean state.  The kernels of
+ * (step, chunk k) need only chunk k of the preceding exchange: the host keeps chunk k's all-to-all in flight while it enqueues
+ * chunk k + 1.  *bytes_per_peer = 0: nothing to exchange after this call; otherwise sendbuf / recvbuf address the chunk's
+ * region.  Results are bitwise those of the unchunked sequence (same kernels per line).
+ * ofdft_dist_stage(stage, chain) is the shorthand for K == 1 (with K > 1 it returns OFDFT_ESTATE): stage 1 = step 1,
+ * stage 2 = step 2, stage 3 = steps 3 + 4, stage 4 = step 5, returning the message of its last step; ofdft_dist_finish then runs
+ * step 6 itself.  Both calls advance the same progress, so they may be mixed within one evaluation.
+ * Sequence per evaluation:
  *     ofdft_dist_sumsq (closure form only) -> all-reduce -> c = N_e / (mean chi^2 vol)
- *     ofdft_dist_begin; for stage in 1..4, for chain in 0..1: [wait for the chain's previous all-to-all]
- *         ofdft_dist_stage(stage, chain) + all_to_all(bytes_per_peer)  (asynchronous if the transport allows);
+ *     ofdft_dist_begin; for step in 1..6, for chain in 0..1, for chunk in 0..K-1: [wait for that chunk of the chain's previous
+ *         all-to-all] ofdft_dist_step(step, chain, chunk) + all_to_all(bytes_per_peer)  (asynchronous if the transport allows);
  *     [wait for both] ofdft_dist_finish -> all-reduce of OFDFT_NSUMS local sums -> ofdft_dist_energies; ofdft_dist_chi_grad.
  * Device-resident scalars (no host round trip before the final sums): pass local_sum_host = NULL to
  * ofdft_dist_sumsq, all-reduce scalars[OFDFT_SCALAR_SUMSQ] in place (ofdft_dist_scalars), call ofdft_dist_begin with from_chi = 2
@@ -215,24 +234,10 @@ int  ofdft_create_dist(ofdft_ctx** out, int n0_global, int n1_global, int n2, in
 int  ofdft_dist_sumsq(ofdft_ctx* ctx, const void* x_local_dev, int square, double* local_sum_host, void* stream);
 int  ofdft_dist_begin(ofdft_ctx* ctx, const void* src_local_dev, int from_chi, double cscale, double n_electrons_global,
                       const void* vext_local_dev, void* v_out_local_dev, void* stream);
-int  ofdft_dist_stage(ofdft_ctx* ctx, int stage, int chain, void* stream, unsigned long long* bytes_per_peer, void** sendbuf_dev,
-                      void** recvbuf_dev);
-/* The same evaluation cut finer so that an exchange overlaps the kernels of its OWN chain ("overlap by z-chunks";
- * the reference is single-device, _optimizers/lbfgs/lbfgsnew.py:31-33, so this has no counterpart there).  The exchange buffers
- * are chunk-major -- [chunk][peer][xl][array][...] over K = ofdft_query(OFDFT_Q_XCHG_CHUNKS) ranges of kz blocks -- so chunk k of an
- * exchange is one contiguous equal-split all-to-all message.  Per chain, each step for chunk = 0 .. K-1 in order:
- *     1  [chunk 0: z kernels]  y-forward of the chunk into the send buffer                  -> exchange of the chunk
- *     2  fused x passes of the chunk, receive buffer -> send buffer                          -> exchange of the chunk
- *     3  y-inverse of the chunk out of the receive buffer
- *     4  [chunk 0: whole-row kernels (GGA mid stage, WGC99 combine)]  y-forward of the flux  -> exchange (chain 0 with a GGA term)
- *     5  fused x pass of the divergence                                                      -> exchange of the chunk
- *     6  y-inverse of the divergence chunk
- * then ofdft_dist_finish.  The kernels of (step, chunk k) need only chunk k of the preceding exchange: the host keeps chunk k's
- * all-to-all in flight while it enqueues chunk k + 1.  *bytes_per_peer = 0: nothing to exchange after this call; otherwise
- * sendbuf / recvbuf address the chunk's region.  Results are bitwise those of the unchunked sequence (same kernels per line).
- * ofdft_dist_stage serves K == 1 only. */
 int  ofdft_dist_step(ofdft_ctx* ctx, int step, int chain, int chunk, void* stream, unsigned long long* bytes_per_peer,
                      void** sendbuf_dev, void** recvbuf_dev);
+int  ofdft_dist_stage(ofdft_ctx* ctx, int stage, int chain, void* stream, unsigned long long* bytes_per_peer, void** sendbuf_dev,
+                      void** recvbuf_dev);
 int  ofdft_dist_finish(ofdft_ctx* ctx, double* local_sums_host /*[OFDFT_NSUMS] or NULL*/, void* stream);
 int  ofdft_dist_scalars(ofdft_ctx* ctx, void** scalars_dev /* OFDFT_NSCALARS doubles owned by the context */);
 int  ofdft_dist_energies(ofdft_ctx* ctx, const double* global_sums /*[OFDFT_NSUMS]*/, double* E_terms_host, double* vn_integral);

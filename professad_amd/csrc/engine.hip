@@ -135,7 +135,7 @@ size_t dist_buffer_bytes(ofdft_ctx* c, int chain) {
     return sizeof(cplx) * (size_t)c->g.total * narr;
 }
 // Two send and two receive buffers per chain, alternating from one exchange to the next (c->recv_parity[chain] = p, flipped by
-// whoever issues the last chunk of an exchange, reset when an evaluation begins): a stage READS the receive buffer R[p] of the
+// zstep after the last chunk of a step that sent, reset when an evaluation begins): a stage READS the receive buffer R[p] of the
 // exchange before it and WRITES the send buffer S[p ^ 1], whose exchange lands in the peers' R[p ^ 1].  With the kz-chunked
 // exchange a stage's first chunks are on their way back while its last chunks are still being read (and, on the send side,
 // still being sent) -- in ONE buffer chunk k's result region would overlap chunk k + 1's input region whenever the two
@@ -149,10 +149,10 @@ int dist_buffers(ofdft_ctx* c, int chain, cplx** send, cplx** recv) {
     if (int rc = get_ws(c, sn[chain][p ^ 1], bytes, (void**)send)) return rc;
     return get_ws(c, rn[chain][p], bytes, (void**)recv);
 }
-// the receive buffer the exchange of what is being written now (S[p ^ 1]) lands in
-int dist_recv_next(ofdft_ctx* c, int chain, cplx** recv) {
+// the chain's receive buffer of parity p (the exchange of what a step wrote into S[p] lands in R[p]: SlabMsg::land)
+int dist_recv_at(ofdft_ctx* c, int chain, int parity, cplx** recv) {
     const char* rn[2][2] = {{"x:recv0", "x:recv0b"}, {"x:recv1", "x:recv1b"}};
-    return get_ws(c, rn[chain][c->recv_parity[chain] ^ 1], dist_buffer_bytes(c, chain), (void**)recv);
+    return get_ws(c, rn[chain][parity], dist_buffer_bytes(c, chain), (void**)recv);
 }
 
 
@@ -1494,145 +1494,84 @@ int ofdft_dist_begin(ofdft_ctx* c, const void* src_local, int from_chi, double c
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
     if (int rc = begin_call(c, st)) return rc;
-    if (!src_local) return fail(c, OFDFT_EINVAL, "null argument");
-    if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
-    if ((c->mask & OFDFT_ION_ELECTRON) && !vext_local) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
-    if (!(c->fast && c->n2 / 2 <= 512)) return fail(c, OFDFT_EINVAL, "staged path needs the power-of-two fast path");
-    if (gga_needs_laplacian(c) && !c->gga_split)
-        return fail(c, OFDFT_EINVAL, "Laplacian-dependent Pauli-Gaussian members need the split-derivative GGA chain (OFDFT_OPT_GGA_SPLIT = 1)");
-    if (wts_active(c) && c->nranks > 1)
-        return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND) is served by single-GPU contexts");
-    ZRun& r = zrun(c);
-    if (from_chi == 2) {      // closure scale from the (all-reduced) sum of chi^2 in scalars[OFDFT_SCALAR_SUMSQ]; it never visits the host
+    // from_chi == 2: the closure scale is formed from the (all-reduced) sum of chi^2 in scalars[OFDFT_SCALAR_SUMSQ]; it never visits the host
+    const DenSrc ds = from_chi == 2 ? DenSrc{(const real*)src_local, 0.0, 1, c->d_scal + kScalClosure}
+                                    : DenSrc{(const real*)src_local, (real)cscale, from_chi, nullptr};
+    if (int rc = zrun_begin(c, ds, nel_global, (const real*)vext_local, (real*)v_out_local)) return rc;
+    if (from_chi == 2)
         OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal + kScalClosure,
                      nel_global, c->vol / (double)c->npts_g);
-        r.ds = DenSrc{(const real*)src_local, 0.0, 1, c->d_scal + kScalClosure};
-    } else {
-        r.ds = DenSrc{(const real*)src_local, (real)cscale, from_chi, nullptr};
-    }
-    r.nel = nel_global;
-    r.vext = (const real*)vext_local;
-    r.v_out = (real*)v_out_local;
-    r.setup_done = false;          // every evaluation sets up afresh (a failed earlier call must not leave its state behind)
-    r.stage[0] = r.stage[1] = 0;
-    c->recv_parity[0] = c->recv_parity[1] = 0;
-    r.step[0] = r.step[1] = 0;
-    r.step_chunk[0] = r.step_chunk[1] = 0;
-    r.forked = false;
-    r.closure = false;
-    r.vpart_deferred = false;
-    r.za.v_part_deferred = 0;
-    r.xlist[0].clear();
-    r.xlist[1].clear();
     return OFDFT_OK;
 }
 
-// Runs stage `stage` (1..4) of chain `chain` (0: density / Hartree / vW / PBE; 1: nonlocal KEDF).  Its kernels read
-// the chain's receive buffer of the previous exchange and write its send buffer directly (exchange layout, see
-// XchgGeom); there are no pack / un-pack copies.  On return *bytes_per_peer is the all-to-all message size (0:
-// nothing to exchange) and the buffers to use.  The chains are independent until ofdft_dist_finish, so the host
-// can keep one chain's all-to-all in flight while the other chain computes.
-int ofdft_dist_stage(ofdft_ctx* c, int stage, int chain, void* stream, unsigned long long* bytes_per_peer, void** sendbuf,
-                     void** recvbuf) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!c || !bytes_per_peer || !sendbuf || !recvbuf || chain < 0 || chain > 1) return OFDFT_EINVAL;
-    OFDFT_ON_DEVICE(c, c->device);
-    ZRun& r = zrun(c);
-    if (stage != r.stage[chain] + 1 || stage < 1 || stage > 4 || (chain == 1 && r.stage[0] < 1))
-        return fail(c, OFDFT_ESTATE, "stage %d of chain %d out of order", stage, chain);
-    if (c->xc.n > 1)
-        return fail(c, OFDFT_ESTATE, "the exchange buffers are cut into %d kz chunks (OFDFT_OPT_XCHG_CHUNKS): sequence the evaluation with ofdft_dist_step", c->xc.n);
-    int rc;
-    switch (stage) {
-        case 1: rc = zstage1(c, st, chain); break;
-        case 2: rc = zstage2(c, st, chain); break;
-        case 3: rc = zstage3(c, st, chain); break;
-        default: rc = zstage4(c, st, chain); break;
-    }
-    if (rc) return rc;
-    *bytes_per_peer = 0;
-    *sendbuf = *recvbuf = nullptr;
-    if (c->nranks > 1 && !r.xlist[chain].empty()) {
-        cplx *send, *recv;
-        if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
-        if ((rc = dist_recv_next(c, chain, &recv))) return rc;
-        *bytes_per_peer = (unsigned long long)(sizeof(cplx) * (size_t)c->xg.nxl * c->xg.arr_sz * r.xlist[chain].size());
-        *sendbuf = send;
-        *recvbuf = recv;
-        c->recv_parity[chain] ^= 1;         // the next stage reads what this exchange delivers
+}  // extern "C"
+namespace {
+// steps first..last of a chain on one chunk for the transport the host issues: zstep, then the last step's message in the
+// terms of the ABI -- its size per peer (0: nothing to exchange) and the chunk's regions of the send and the receive buffer
+int dist_steps(ofdft_ctx* c, hipStream_t st, int first, int last, int chain, int chunk, unsigned long long* bytes_per_peer, void** sendbuf,
+               void** recvbuf) {
+    SlabMsg m;
+    for (int step = first; step <= last; ++step)
+        if (int rc = zstep(c, st, step, chain, chunk, &m)) return rc;
+    *bytes_per_peer = (unsigned long long)m.bytes;
+    *sendbuf = m.send;
+    *recvbuf = nullptr;
+    if (m.bytes) {
+        cplx* recv;
+        if (int rc = dist_recv_at(c, chain, m.land, &recv)) return rc;
+        *recvbuf = recv + m.offset;
     }
     HIP_TRY(c, hipGetLastError());
     return OFDFT_OK;
 }
+}  // namespace
+extern "C" {
 
-// The same evaluation cut finer, for exchanges that overlap the chain's own kernels ("overlap by z-chunks").  The
-// exchange buffers are chunk-major, [chunk][peer][xl][array][...] over K = ofdft_query(OFDFT_Q_XCHG_CHUNKS) ranges of kz blocks, so chunk
-// k of an exchange is one contiguous equal-split all-to-all message.  Per chain the steps are, each for chunk = 0 .. K-1 in order:
-//   1  [chunk 0: z kernels]  y-forward of the chunk into the send buffer                         -> exchange (chunk)
-//   2  fused x passes on the chunk: receive buffer -> send buffer                                 -> exchange (chunk)
-//   3  y-inverse of the chunk out of the receive buffer
-//   4  [chunk 0: PBE mid stage / WGC99 combine on whole rows]  y-forward of the flux chunk        -> exchange (chunk; chain 0 with a GGA term)
-//   5  fused x pass of the divergence on the chunk                                                -> exchange (chunk)
-//   6  y-inverse of the divergence chunk
-// then ofdft_dist_finish.  A step's kernels for chunk k need only chunk k of the exchange before them, so the host may keep
-// the all-to-all of chunk k in flight while it enqueues chunk k + 1.  Results are bitwise those of the unchunked sequence.
-// On return *bytes_per_peer (0: nothing to exchange) and the chunk's regions of the send / receive buffers.
+// One (step, chunk) of chain `chain` (0: density / Hartree / vW / PBE; 1: nonlocal KEDF); the six steps and their order are
+// stated once, in include/ofdft_hip.h and at the head of engine_zfused.inc.h (zstep).  Its kernels read the chain's receive
+// buffer of the previous exchange and write its send buffer directly (exchange layout, see XchgGeom); there are no pack /
+// un-pack copies.  The exchange buffers are chunk-major, [chunk][peer][xl][array][...] over K = ofdft_query(OFDFT_Q_XCHG_CHUNKS)
+// ranges of kz blocks, so chunk k of an exchange is one contiguous equal-split all-to-all message, and a step's kernels for
+// chunk k need only chunk k of the exchange before them: the host may keep the all-to-all of chunk k in flight while it enqueues
+// chunk k + 1 ("overlap by z-chunks").  The chains are independent until ofdft_dist_finish, so one chain's all-to-all
+// can also be in flight while the other chain computes.  Results are bitwise those of the unchunked sequence.
 int ofdft_dist_step(ofdft_ctx* c, int step, int chain, int chunk, void* stream, unsigned long long* bytes_per_peer, void** sendbuf,
                     void** recvbuf) {
-    hipStream_t st = (hipStream_t)stream;
     if (!c || !bytes_per_peer || !sendbuf || !recvbuf || chain < 0 || chain > 1) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
-    ZRun& r = zrun(c);
-    const int K = c->xc.n;
-    const bool next_chunk = step == r.step[chain] && chunk == r.step_chunk[chain] + 1 && chunk < K;
-    const bool next_step = step == r.step[chain] + 1 && chunk == 0 && (r.step[chain] == 0 || r.step_chunk[chain] == K - 1);
-    if (step < 1 || step > 6 || !(next_chunk || next_step) || (chain == 1 && r.step[0] < 1))
-        return fail(c, OFDFT_ESTATE, "step %d chunk %d of chain %d out of order (last: step %d chunk %d of %d)", step, chunk, chain,
-                    r.step[chain], r.step_chunk[chain], K);
-    int rc;
-    switch (step) {
-        case 1: rc = zstage1(c, st, chain, chunk); break;
-        case 2: rc = zstage2(c, st, chain, chunk); break;
-        case 3: rc = zstage3(c, st, chain, 1, chunk); break;
-        case 4: rc = zstage3(c, st, chain, 2, chunk); break;
-        case 5: rc = zstage4(c, st, chain, chunk); break;
-        default: rc = chain == 0 ? zstage5(c, nullptr, st, false, 1, chunk) : 0; break;     // (the divergence belongs to chain 0)
-    }
-    if (rc) return rc;
-    r.step[chain] = step;
-    r.step_chunk[chain] = chunk;
-    *bytes_per_peer = 0;
-    *sendbuf = *recvbuf = nullptr;
-    const bool sends = step == 1 || step == 2 || step == 4 || step == 5;
-    if (sends && c->nranks > 1 && !r.xlist[chain].empty()) {
-        cplx *send, *recv;
-        if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
-        if ((rc = dist_recv_next(c, chain, &recv))) return rc;
-        const XcView v = xc_view(c, chunk);
-        const long long narr = (long long)r.xlist[chain].size();
-        *bytes_per_peer = (unsigned long long)(sizeof(cplx) * (size_t)c->xg.nxl * v.arr_sz * narr);
-        *sendbuf = send + narr * v.base1;
-        *recvbuf = recv + narr * v.base1;
-        if (chunk == K - 1) c->recv_parity[chain] ^= 1;      // the next step reads what this exchange delivers
-    }
-    if (step == 5 && chunk == K - 1) r.stage[chain] = 4;
-    HIP_TRY(c, hipGetLastError());
+    return dist_steps(c, (hipStream_t)stream, step, step, chain, chunk, bytes_per_peer, sendbuf, recvbuf);
+}
+
+// The one-chunk shorthand: stage 1 = step 1, 2 = step 2, 3 = steps 3 + 4, 4 = step 5 (ofdft_dist_finish then runs step 6); the
+// message is the last sub-step's.  Stage and step calls may be mixed within one evaluation: both advance the same counters.
+int ofdft_dist_stage(ofdft_ctx* c, int stage, int chain, void* stream, unsigned long long* bytes_per_peer, void** sendbuf,
+                     void** recvbuf) {
+    if (!c || !bytes_per_peer || !sendbuf || !recvbuf || chain < 0 || chain > 1) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    if (stage < 1 || stage > 4) return fail(c, OFDFT_ESTATE, "stage %d of chain %d out of order", stage, chain);
+    if (c->xc.n > 1)
+        return fail(c, OFDFT_ESTATE, "the exchange buffers are cut into %d kz chunks (OFDFT_OPT_XCHG_CHUNKS): sequence the evaluation with ofdft_dist_step", c->xc.n);
+    constexpr int first[5] = {0, kStepYFwd, kStepX, kStepYInv, kStepDivX}, last[5] = {0, kStepYFwd, kStepX, kStepMid, kStepDivX};
+    if (int rc = dist_steps(c, (hipStream_t)stream, first[stage], last[stage], chain, 0, bytes_per_peer, sendbuf, recvbuf)) return rc;
+    if (stage == 4) zrun(c).yinv_owed[chain] = true;
     return OFDFT_OK;
 }
 
-// Stage 5: y-inverse of the last exchange, combine; local_sums[OFDFT_NSUMS] = the combine sums + the GGA sums (to be summed over ranks
-// by the caller, then turned into energies by ofdft_dist_energies).
+// After step 6 of both chains (run here for a chain that ofdft_dist_stage left at step 5): the combine; local_sums[OFDFT_NSUMS] = the
+// combine sums + the GGA sums (to be summed over ranks by the caller, then turned into energies by ofdft_dist_energies).
 int ofdft_dist_finish(ofdft_ctx* c, double* local_sums, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
     ZRun& r = zrun(c);
-    if (r.stage[0] != 4 || r.stage[1] != 4) return fail(c, OFDFT_ESTATE, "ofdft_dist_finish called before stage 4 of both chains");
-    const bool stepped = r.step[0] > 0;           // sequenced with ofdft_dist_step: the divergence has been y-inverted chunk by chunk
-    if (stepped && !(r.step[0] == 6 && r.step_chunk[0] == c->xc.n - 1 && r.step[1] == 6 && r.step_chunk[1] == c->xc.n - 1))
-        return fail(c, OFDFT_ESTATE, "ofdft_dist_finish called before step 6 of both chains");
     int rc;
-    if ((rc = zstage5(c, local_sums, st, false, stepped ? 2 : 0))) return rc;
+    SlabMsg m;
+    for (int chain = 0; chain < 2; ++chain)
+        if (r.yinv_owed[chain] && r.step[chain] == kStepDivX && (rc = zstep(c, st, kStepDivYInv, chain, 0, &m))) return rc;
+    for (int chain = 0; chain < 2; ++chain)
+        if (r.step[chain] != kStepDivYInv || r.step_chunk[chain] != c->xc.n - 1)
+            return fail(c, OFDFT_ESTATE, "ofdft_dist_finish called before step 6 of both chains");
+    if ((rc = zcombine(c, local_sums, st))) return rc;
     if (!local_sums) {        // device-resident form: scalars[0 .. OFDFT_NSUMS - 1] hold the local sums, nothing waits here
         HIP_TRY(c, hipEventRecord(c->ev1, st));
         c->ms_pending = true;

@@ -418,7 +418,7 @@ int real_ws(ofdft_ctx* c, const char* name, real** out);
 int spec_ws(ofdft_ctx* c, const char* name, cplx** out);
 size_t dist_buffer_bytes(ofdft_ctx* c, int chain);
 int dist_buffers(ofdft_ctx* c, int chain, cplx** send, cplx** recv);
-int dist_recv_next(ofdft_ctx* c, int chain, cplx** recv);
+int dist_recv_at(ofdft_ctx* c, int chain, int parity, cplx** recv);
 int dist_exchange(ofdft_ctx* c, cplx* send, cplx* recv, hipStream_t st);
 int global_sums(ofdft_ctx* c, double* v, int n);
 
@@ -427,8 +427,8 @@ void pass_maps(const ofdft_ctx* c, int axis, LineMap& main, LineMap& rem);
 template <bool INV>
 int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, hipStream_t st);
 template <bool INV> int fast_axis_pass(ofdft_ctx* c, int axis, cplx* spec, hipStream_t st);
-// xk: chunk of the exchange layout (-1: every chunk, one launch each; kWholeXchg: the unchunked layout)
-template <bool INV> int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStream_t st, int xk = -1);
+// xk: chunk of the exchange layout (kWholeXchg: the unchunked layout)
+template <bool INV> int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStream_t st, int xk);
 // (fwd: also store the y-forward transform of `in` there -- in place when fwd == in; fft_kernels.h: yderiv_kernel)
 int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd = nullptr);
 // out = y-inverse of (i f_b scale y-forward(in) + add), add a y-forwarded spectrum of the same layout (add == out: in place)

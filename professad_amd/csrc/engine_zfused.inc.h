@@ -11,6 +11,15 @@
 //   stage 3  y-inverse of the results; PBE mid stage on chip; y-forward of the flux          -> exchange
 //   stage 4  fused x pass of the divergence                                                  -> exchange
 //   stage 5  y-inverse of the divergence; combine kernel (potential + energy integrands)
+// Every driver sequences the same six steps per chain, each on one kz chunk of the exchange layout (zstep; one GPU: chunk 0),
+// then zcombine.  A step that sends leaves its chunk in the chain's send buffer; a y-inverse step reads the receive buffer and
+// is a no-op on one GPU, where the mid stage and the combine y-invert in place instead:
+//   kStepYFwd     [chunk 0: z kernels]  y-forward of the chunk                              (stage 1)  sends
+//   kStepX        fused x passes of the chunk                                               (stage 2)  sends
+//   kStepYInv     y-inverse of the chunk                                                    (stage 3)
+//   kStepMid      [chunk 0: whole-row kernels: PBE mid stage, split WGC99 combine]  y-forward of the flux chunk  (stage 3)  sends
+//   kStepDivX     fused x pass of the divergence chunk                                      (stage 4)  sends
+//   kStepDivYInv  y-inverse of the divergence chunk                                         (stage 5)
 // Potential-spectrum form (one GPU, split-derivative GGA with Hartree; OFDFT_OPT_POT_SPECTRUM): stage 2 forms i f_a n^ only, stage 4
 // reads n^ beside G_a^ and returns i f_a G_a^ - v_H^ / 2 (+ E_H by Parseval), stage 5 adds D_b G_b inside the y-inverse of that
 // spectrum -- the combine kernel reads one spectrum for Hartree + divergence where it read three (v_H, D_a part, D_b part).
@@ -28,7 +37,7 @@ struct ZRun {
     cplx *s_n = nullptr, *s_s = nullptr, *s_vh = nullptr, *s_g[3] = {nullptr, nullptr, nullptr};
     cplx *s_b = nullptr, *s_a = nullptr, *sw[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     real* dfdn = nullptr;
-    TermScalars ts{};              // host scalars of the evaluation's terms (zsetup; the nonlocal chain's stage 1 adds the tables)
+    TermScalars ts{};              // host scalars of the evaluation's terms (zrun_begin; the nonlocal chain's step 1 adds the tables)
     // The evaluation is two independent chains that meet only in the combine kernel:
     //   chain 0: density spectrum -> Hartree, grad n -> PBE -> divergence;  sqrt(n) -> Laplacian (vW)
     //   chain 1: the nonlocal KEDF (Wang-Teter powers or the six WGC99 spectra)
@@ -46,12 +55,11 @@ struct ZRun {
     real* dzn = nullptr;
     bool wgc_split = false;        // the WGC99 potential was formed by zi_wgc_kernel (za.v_part)
     bool closure = false;          // single-GPU closure evaluation: only chi.grad leaves the call, so v may stay in two parts
-    bool setup_done = false;       // zsetup ran for the evaluation being enqueued (zstage1 of chain 0 consumes it)
     bool late_join = false;        // host-bound sums of a closure evaluation: the share of sum(v n) of the deferred part is added by chi_grad / the host
-    bool vpart_deferred = false;   // ... and does: zi_combine does not wait for zi_wgc, chi_grad adds v_part (zstage5)
-    int stage[2] = {0, 0};
-    // kz-chunked exchange (ofdft_dist_step): last (step, chunk) of each chain; what stage 1 sent (read again by every chunk of stage 2)
+    bool vpart_deferred = false;   // ... and does: zi_combine does not wait for zi_wgc, chi_grad adds v_part (zcombine)
+    // progress of the slab drivers (zstep): last (step, chunk) of each chain; what step 1 sent (read again by every chunk of step 2)
     int step[2] = {0, 0}, step_chunk[2] = {0, 0};
+    bool yinv_owed[2] = {false, false};      // ofdft_dist_stage(4) ran step 5: ofdft_dist_finish runs the chain's step 6
     std::vector<cplx*> in_list[2];
     int combine_blocks = 0, pbe_blocks = 0;
     hipStream_t sb = nullptr;      // stream of the nonlocal-KEDF chain (== the main stream unless forked)
@@ -68,16 +76,38 @@ ZRun& zrun(ofdft_ctx* c);
 // ---- all-to-all buffers of the slab-decomposed path, one pair per chain (both directions reuse the pair):
 // chain 0 carries at most 5 spectra (Hartree, grad n, vW leaving stage 2), chain 1 at most 8 (2 Wang-Teter + 6 WGC99)
 
-// Stage 1: z-forward (with the pointwise pre-ops) and y-forward of the chain's input spectra.
-// (xk: chunk of the kz-chunked exchange -- the z kernels run with chunk 0, every call y-transforms its chunk into the send
-// buffer; -1 = all chunks)
-// host-side state of an evaluation that both chains read (term flags, the combine kernel's arguments): first thing of stage 1
-// of chain 0 -- or, when the nonlocal chain's first kernels are enqueued first (zfused_enqueue), before either
+enum { kStepYFwd = 1, kStepX, kStepYInv, kStepMid, kStepDivX, kStepDivYInv, kStepDone };
+
 #ifndef OFDFT_YDERIV_FWD
 #define OFDFT_YDERIV_FWD 1
 #endif
-int zsetup(ofdft_ctx* c) {
+// One begin for every z-fused evaluation (ofdft_dist_begin, ofdft_dist_closure, zfused_enqueue): what the pipeline refuses, the
+// complete reset of the run -- a failed earlier call must not leave its state behind -- and the host-side state both chains
+// read (term flags, the combine kernel's arguments).
+int zrun_begin(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext, real* v_out) {
+    if (!ds.src) return fail(c, OFDFT_EINVAL, "null argument");
+    if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
+    if ((c->mask & OFDFT_ION_ELECTRON) && !vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
+    if (!(c->fast && c->n2 / 2 <= 512)) return fail(c, OFDFT_EINVAL, "staged path needs the power-of-two fast path");
+    if (gga_needs_laplacian(c) && !c->gga_split)
+        return fail(c, OFDFT_EINVAL, "Laplacian-dependent Pauli-Gaussian members need the split-derivative GGA chain (OFDFT_OPT_GGA_SPLIT = 1)");
+    if (wts_active(c) && c->nranks > 1)
+        return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND) is served by single-GPU contexts");
     ZRun& r = zrun(c);
+    r.ds = ds;
+    r.nel = nel;
+    r.vext = vext;
+    r.v_out = v_out;
+    for (int chain = 0; chain < 2; ++chain) {
+        r.step[chain] = r.step_chunk[chain] = 0;
+        r.yinv_owed[chain] = false;
+        r.xlist[chain].clear();
+        r.in_list[chain].clear();
+        c->recv_parity[chain] = 0;
+    }
+    r.forked = false;
+    r.closure = false;
+    r.vpart_deferred = false;
     const unsigned mask = c->mask;
     r.has_h = mask & OFDFT_HARTREE;
     r.has_g = mask & kGgaAny;
@@ -97,22 +127,20 @@ int zsetup(ofdft_ctx* c) {
     r.pspec = false;
     r.da_early = r.lap_split = false;
     r.s_sx = nullptr;
-    if ((mask & OFDFT_ION_ELECTRON) && !r.vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
-    r.setup_done = true;
     return 0;
 }
 
-int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
+// Step 1: [chunk 0: z-forward (with the pointwise pre-ops) of the chain's input spectra]  y-forward of the chunk -- in place on one
+// GPU, into the send buffer on slabs.
+int zstep_yfwd(ofdft_ctx* c, hipStream_t st, int chain, int chunk) {
     ZRun& r = zrun(c);
     int rc;
     hipStream_t sb = r.forked ? r.sb : st, sc = r.forked ? r.sc : st;
     const bool dx = c->nranks > 1;
     std::vector<cplx*>& xl = r.xlist[chain];
-    if (xk <= 0) {
+    if (chunk == 0) {
     xl.clear();
     if (chain == 0) {
-        if (!r.setup_done && (rc = zsetup(c))) return rc;
-        r.setup_done = false;         // (consumed: the next evaluation sets up again)
         if (r.has_h || r.has_g)
             if ((rc = spec_ws(c, "zn", &r.s_n))) return rc;
         if (r.has_vw)
@@ -203,36 +231,30 @@ int zstage1(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             }
         }
     }
-    }   // xk <= 0
+    }   // chunk == 0
     if (dx && !xl.empty()) {        // the chain's y-forwards in one launch (per chunk), written in the exchange layout
         cplx *send, *recv;
         if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
-        if ((rc = ypass_xchg<false>(c, xl, send, st, xk))) return rc;
+        if ((rc = ypass_xchg<false>(c, xl, send, st, chunk))) return rc;
     }
-    r.stage[chain] = 1;
     return 0;
 }
 
-// Stage 2: the fused x passes (forward x, k-space mixing, inverse x).
-int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
+// Step 2: the fused x passes (forward x, k-space mixing, inverse x) of the chunk.
+int zstep_x(ofdft_ctx* c, hipStream_t st, int chain, int chunk) {
     ZRun& r = zrun(c);
     int rc;
     hipStream_t sb = r.forked ? r.sb : st, sc = r.forked ? r.sc : st;
-    // several ranks: the inputs sit in the chain's receive buffer (slot = position in stage 1's list) and the
+    // several ranks: the inputs sit in the chain's receive buffer (slot = position in step 1's list) and the
     // outputs are written to its send buffer in the order they are listed here -- per kz chunk of the exchange layout
     const bool dx = c->nranks > 1;
-    if (dx && xk == -1 && c->xc.n > 1) {
-        for (int k = 0; k < c->xc.n; ++k)
-            if ((rc = zstage2(c, st, chain, k))) return rc;
-        return 0;
-    }
     std::vector<cplx*>& xl = r.xlist[chain];
-    if (xk <= 0) r.in_list[chain] = xl;           // what stage 1 sent: every chunk's pass reads the same slots
+    if (chunk == 0) r.in_list[chain] = xl;        // what step 1 sent: every chunk's pass reads the same slots
     const std::vector<cplx*>& in_list = r.in_list[chain];
     xl.clear();
     cplx *send = nullptr, *recv = nullptr;
     XfLayout lay{};
-    const XcView xv = xc_view(c, xk < 0 ? 0 : xk);
+    const XcView xv = xc_view(c, chunk);
     int nout = 0;
     if (dx) {
         if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
@@ -346,34 +368,35 @@ int zstage2(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
             }
         }
     }
-    r.stage[chain] = 2;
     return 0;
 }
 
-// Stage 3: y-inverse of what came back from the x passes (each completes one c2r except grad n); chain 0 then runs
-// the PBE mid stage on chip and starts the three r2c of the flux.
-// part 0: the whole stage; kz-chunked exchange: part 1 = the y-inverse of chunk xk only, part 2 = everything after the
-// y-inverses (the row kernels with chunk 0; every call y-transforms its chunk of the flux into the send buffer)
-int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) {
+// Steps 3 and 6, slabs only: y-inverse of the chunk of what the preceding x passes sent back (the results of step 2; the
+// divergence spectrum of step 5, chain 0), read from the exchange layout in one launch.  One GPU: nothing -- the mid stage and
+// the combine y-invert in place.
+int zstep_yinv(ofdft_ctx* c, hipStream_t st, int chain, int chunk) {
+    const std::vector<cplx*>& xl = zrun(c).xlist[chain];
+    if (c->nranks == 1 || xl.empty()) return 0;
+    cplx *send, *recv;
+    if (int rc = dist_buffers(c, chain, &send, &recv)) return rc;
+    return ypass_xchg<true>(c, xl, recv, st, chunk);
+}
+
+// Step 4: [chunk 0: the whole-row kernels -- one GPU: y-inverse of what came back from the x passes (each completes one c2r except
+// grad n); chain 0: the PBE mid stage on chip; chain 1: the split WGC99 combine]  y-forward of the chunk of the flux.
+int zstep_mid(ofdft_ctx* c, hipStream_t st, int chain, int chunk) {
     ZRun& r = zrun(c);
     int rc;
     hipStream_t sb = r.forked ? r.sb : st, sc = r.forked ? r.sc : st;
     const bool dx = c->nranks > 1;
     std::vector<cplx*>& xl = r.xlist[chain];
-    cplx *send = nullptr, *recv = nullptr;
-    if (dx && !xl.empty() && part != 2) {        // one launch (per chunk): the chain's y-inverses, read from the exchange layout
-        if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
-        if ((rc = ypass_xchg<true>(c, xl, recv, st, xk))) return rc;
-    }
-    if (part == 1) return 0;
-    if (part == 2 && xk > 0) {                   // a later chunk of the flux: the y-forward into the send buffer only
-        if (dx && chain == 0 && !xl.empty()) {
-            if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
-            if ((rc = ypass_xchg<false>(c, xl, send, st, xk))) return rc;
-        }
-        return 0;
-    }
-    const int yk = part == 2 ? 0 : -1;           // chunks the y-forwards below cover
+    auto send_flux = [&]() -> int {              // slabs: the chunk's y-forwards in one launch, written in the exchange layout
+        if (!dx || xl.empty()) return 0;
+        cplx *send, *recv;
+        if (int e = dist_buffers(c, chain, &send, &recv)) return e;
+        return ypass_xchg<false>(c, xl, send, st, chunk);
+    };
+    if (chunk > 0) return send_flux();           // (the row kernels ran with chunk 0, which left the flux in the list)
     const bool wbatch = !dx && c->ybatch && chain == 1 && r.has_wgc && xl.size() >= 6;
     if (wbatch) {           // the six WGC99 results: one batched y-inverse per half (see stage 1)
         if ((rc = fast_axis_pass_multi<true>(c, 1, r.sw, 3, sb))) return rc;
@@ -420,7 +443,6 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
             r.vpart_deferred = r.closure && r.forked && c->defer_vpart;
             r.za.v_part_deferred = r.vpart_deferred ? 1 : 0;
         }
-        r.stage[1] = 3;
         return 0;
     }
     if (r.has_h && !r.pspec) r.za.vh = r.s_vh;
@@ -440,10 +462,6 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
             if (!dx && (rc = fast_axis_pass<false>(c, 1, r.s_l, st))) return rc;
             xl.push_back(r.s_l);
         }
-        if (dx) {
-            if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
-            if ((rc = ypass_xchg<false>(c, xl, send, st, yk))) return rc;
-        }
     } else if (r.has_g) {
         if ((rc = real_ws(c, "dfdn", &r.dfdn))) return rc;
         if ((rc = launch_zpbe(c, r.ds, r.s_g[0], r.s_g[1], r.s_g[2], r.dfdn, r.za.inv_n, &r.pbe_blocks, st))) return rc;
@@ -453,25 +471,15 @@ int zstage3(ofdft_ctx* c, hipStream_t st, int chain, int part = 0, int xk = -1) 
             if (!dx && (rc = fast_axis_pass<false>(c, 1, r.s_g[k], st))) return rc;
             xl.push_back(r.s_g[k]);
         }
-        if (dx) {
-            if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
-            if ((rc = ypass_xchg<false>(c, xl, send, st, yk))) return rc;
-        }
     }
-    r.stage[0] = 3;
-    return 0;
+    return send_flux();
 }
 
-// Stage 4: fused x pass of the divergence (chain 0 only).
-int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
+// Step 5: fused x pass of the chunk of the divergence (chain 0 only).
+int zstep_divx(ofdft_ctx* c, hipStream_t st, int chain, int chunk) {
     ZRun& r = zrun(c);
-    if (c->nranks > 1 && xk == -1 && c->xc.n > 1) {
-        for (int k = 0; k < c->xc.n; ++k)
-            if (int rc = zstage4(c, st, chain, k)) return rc;
-        return 0;
-    }
     r.xlist[chain].clear();
-    const XcView xv = xc_view(c, xk < 0 ? 0 : xk);
+    const XcView xv = xc_view(c, chunk);
     if (chain == 0 && r.pspec) {
         // i f_a G_a^ [+ (k^2 / 2) (df/dL)^] - v_H^ / 2 in place of G_a^, and the partial sums of E_H (one per workgroup)
         acc_t* ehp;
@@ -530,7 +538,6 @@ int zstage4(ofdft_ctx* c, hipStream_t st, int chain, int xk = -1) {
         if (int rc = xfused<3, 1>(c, dio, MixDiv{c->kg}, st, "xfused_div", lay)) return rc;
         r.xlist[0].push_back(r.s_n);
     }
-    r.stage[chain] = 4;
     return 0;
 }
 
@@ -556,28 +563,15 @@ void zfused_collect(const ofdft_ctx* c, int flags, double* sums) {
 // `sums` == nullptr: the caller reduces the device-resident sums itself (slab-decomposed path).  `defer`: the sums are
 // copied to the pinned host mirror but nothing waits here (zfused_collect reads them after the caller's stream sync --
 // the graph-capturable form)
-// (part 1: only the y-inverse of kz chunk xk of the divergence out of the exchange buffer; part 2: everything else; 0: both)
-int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int part = 0, int xk = -1) {
+// (after step 6 of both chains: on slabs the divergence has been y-inverted chunk by chunk, one GPU does it here)
+int zcombine(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false) {
     ZRun& r = zrun(c);
     int rc;
-    if (part == 1) {
-        if (r.has_g && c->nranks > 1) {
-            cplx *send, *recv;
-            if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
-            if ((rc = ypass_xchg<true>(c, {r.gsplit ? r.s_g[0] : r.s_n}, recv, st, xk))) return rc;
-        }
-        return 0;
-    }
     if (r.has_g) {
         cplx* dsp = r.gsplit ? r.s_g[0] : r.s_n;       // the spectrum that carries the (x part of the) divergence
-        if (c->nranks > 1) {
-            cplx *send, *recv;
-            if ((rc = dist_buffers(c, 0, &send, &recv))) return rc;
-            if (part != 2 && (rc = ypass_xchg<true>(c, {dsp}, recv, st))) return rc;
-        } else if (r.pspec) {     // D_b G_b + the y-inverse of the divergence spectrum (+ v_H) in one pass, into that spectrum
-            if ((rc = yderiv_add(c, r.s_g[1], dsp, dsp, (double)c->n0g, st))) return rc;
-        } else if ((rc = fast_axis_pass<true>(c, 1, dsp, st))) {
-            return rc;
+        if (c->nranks == 1) {     // (pspec: D_b G_b + the y-inverse of the divergence spectrum (+ v_H) in one pass, into that spectrum)
+            rc = r.pspec ? yderiv_add(c, r.s_g[1], dsp, dsp, (double)c->n0g, st) : fast_axis_pass<true>(c, 1, dsp, st);
+            if (rc) return rc;
         }
         c->fft_count++;
         r.za.div = dsp;
@@ -620,7 +614,7 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
     }
     r.late_join = late_join && sums != nullptr;
     if (!r.has_g) HIP_TRY(c, hipMemsetAsync(c->d_reduced + kSumGga, 0, kPbeScalars * sizeof(double), st));
-    r.stage[0] = r.stage[1] = 5;
+    r.step[0] = r.step[1] = kStepDone;         // (a step or a second combine without a new begin is out of order)
     if (!sums) {                  // the caller reduces the device-resident sums (c->d_reduced) itself
         if (r.wgc_split)          // fold in the energy sum of the split WGC99 kernel
             OFDFT_LAUNCH(c, st, "reduce", (axpy_kernel<acc_t>), dim3(1), dim3(64), 0, (const acc_t*)(c->d_scal + kScalWgcSplit), c->d_reduced + kSumWgc,
@@ -634,21 +628,66 @@ int zstage5(ofdft_ctx* c, double* sums, hipStream_t st, bool defer = false, int 
     return 0;
 }
 
-// stages 1-5 of one evaluation enqueued on `st` (and the side streams forked from / joined to it); with `defer` nothing
-// touches the host: the sequence can be captured into a hipGraph
+// The kernels of one step of a chain on one kz chunk: the one statement of what a step is, for every driver.
+int zstep_kernels(ofdft_ctx* c, hipStream_t st, int step, int chain, int chunk) {
+    switch (step) {
+        case kStepYFwd: return zstep_yfwd(c, st, chain, chunk);
+        case kStepX: return zstep_x(c, st, chain, chunk);
+        case kStepYInv: return zstep_yinv(c, st, chain, chunk);
+        case kStepMid: return zstep_mid(c, st, chain, chunk);
+        case kStepDivX: return zstep_divx(c, st, chain, chunk);
+        case kStepDivYInv: return zstep_yinv(c, st, chain, chunk);          // (the divergence spectrum: chain 0's list after step 5)
+    }
+    return fail(c, OFDFT_EINVAL, "no step %d", step);
+}
+
+// what a step left to be exchanged: the chunk's region of the chain's send buffer, `offset` elements into it (the same region of
+// the receive buffer of parity `land` takes the delivery), `bytes` per peer -- 0: nothing crosses
+struct SlabMsg {
+    cplx* send = nullptr;
+    long long offset = 0;
+    size_t bytes = 0;
+    int land = 0;
+};
+
+// One step of a slab driver (ofdft_dist_step / _stage / _closure).  Order per chain: the next chunk of the same step, or chunk 0
+// of the next step after the last chunk of the previous one; chain 1 only after chain 0's step 1.  Runs the kernels, records the
+// progress, fills *msg, and after the last chunk of a step that sent turns the chain to the receive buffer the delivery lands in.
+int zstep(ofdft_ctx* c, hipStream_t st, int step, int chain, int chunk, SlabMsg* msg) {
+    ZRun& r = zrun(c);
+    const int K = c->xc.n;
+    const bool next_chunk = step == r.step[chain] && chunk == r.step_chunk[chain] + 1 && chunk < K;
+    const bool next_step = step == r.step[chain] + 1 && chunk == 0 && (r.step[chain] == 0 || r.step_chunk[chain] == K - 1);
+    if (step < kStepYFwd || step > kStepDivYInv || !(next_chunk || next_step) || (chain == 1 && r.step[0] < kStepYFwd))
+        return fail(c, OFDFT_ESTATE, "step %d chunk %d of chain %d out of order (last: step %d chunk %d of %d)", step, chunk, chain,
+                    r.step[chain], r.step_chunk[chain], K);
+    if (int rc = zstep_kernels(c, st, step, chain, chunk)) return rc;
+    r.step[chain] = step;
+    r.step_chunk[chain] = chunk;
+    *msg = SlabMsg{};
+    const bool sends = step == kStepYFwd || step == kStepX || step == kStepMid || step == kStepDivX;
+    if (sends && c->nranks > 1 && !r.xlist[chain].empty()) {
+        cplx *send, *recv;
+        if (int rc = dist_buffers(c, chain, &send, &recv)) return rc;
+        const XcView v = xc_view(c, chunk);
+        const long long narr = (long long)r.xlist[chain].size();
+        msg->offset = narr * v.base1;
+        msg->send = send + msg->offset;
+        msg->bytes = sizeof(cplx) * (size_t)c->xg.nxl * (size_t)v.arr_sz * (size_t)narr;
+        msg->land = c->recv_parity[chain] ^ 1;
+        if (chunk == K - 1) c->recv_parity[chain] ^= 1;          // the next step reads what this exchange delivers
+    }
+    return 0;
+}
+
+// one evaluation on one GPU enqueued on `st` (and the side streams forked from / joined to it): the six steps with chunk 0,
+// then the combine; with `defer` nothing touches the host: the sequence can be captured into a hipGraph
 int zfused_enqueue(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext, real* v_out, double* sums, hipStream_t st,
                    bool defer) {
-    if ((c->mask & OFDFT_ION_ELECTRON) && !vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
-    if (!ds.src) return fail(c, OFDFT_EINVAL, "null density pointer");
-    ZRun& r = zrun(c);
-    r.ds = ds;
-    r.nel = nel;
-    r.vext = vext;
-    r.v_out = v_out;
-    r.closure = defer;            // (only the closure enqueues in deferred form; its consumer is chi_grad)
-    r.vpart_deferred = false;
-    r.za.v_part_deferred = 0;
     int rc;
+    if ((rc = zrun_begin(c, ds, nel, vext, v_out))) return rc;
+    ZRun& r = zrun(c);
+    r.closure = defer;            // (only the closure enqueues in deferred form; its consumer is chi_grad)
     // Forking the nonlocal-KEDF chain (and the vW / second WGC99 half) onto their own streams lets their
     // latency-bound fused kernels overlap the other chain's bandwidth-bound passes.
     r.forked = c->use_side_stream && c->side_stream && c->side_stream2 && (c->mask & (OFDFT_WT_NL | OFDFT_WGC99_NL | OFDFT_NLK)) &&
@@ -662,18 +701,12 @@ int zfused_enqueue(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext,
     }
     // one GPU, forked: the nonlocal chain's first kernels go to the device BEFORE the other chain's four launches (its stream
     // sat idle for ~30 us of host enqueue time at the head of every evaluation; profiles/r04_timeline_*.md)
-    r.setup_done = false;
-    rc = zsetup(c);
+    // (the y-inverse steps are no-ops here, and nothing is exchanged: no zstep, whose chain order is the slab drivers')
     const bool nl_first = r.forked && c->nranks == 1;
-    for (int i = 0; i < 2 && !rc; ++i) rc = zstage1(c, st, nl_first ? 1 - i : i);
-    for (int chain = 0; chain < 2 && !rc; ++chain) rc = zstage2(c, st, chain);
-    for (int chain = 0; chain < 2 && !rc; ++chain) rc = zstage3(c, st, chain);
-    if (!rc) rc = zstage4(c, st, 0);
-    if (!rc) rc = zstage5(c, sums, st, defer);
-    // (a call that failed between zsetup and chain 0's stage 1 -- the nonlocal chain goes first here -- must not leave the
-    // flag set: a later staged evaluation entering through zstage1(chain 0) would skip its own set-up)
-    r.setup_done = false;
-    return rc;
+    for (int step = kStepYFwd; step <= kStepDivYInv; ++step)
+        for (int i = 0; i < 2; ++i)
+            if ((rc = zstep_kernels(c, st, step, (nl_first && step == kStepYFwd) ? 1 - i : i, 0))) return rc;
+    return zcombine(c, sums, st, defer);
 }
 
 int run_terms_zfused(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext, double* E_terms, real* v_out,

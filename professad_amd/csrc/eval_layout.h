@@ -32,7 +32,7 @@ constexpr int kMirrorResTimeout = kNSums;         // persistent kernel: 1.0 if o
 constexpr int kMirrorResClock = 16;               // persistent kernel built with OFDFT_RES_CLOCK: phase clock of workgroup 0,
 constexpr int kResClockCount = 12;                //   kResClockCount values in hundredths of a microsecond (100 MHz ticks)
 // kMirrorWgcSplit and kMirrorResTimeout are ONE slot.  No evaluation writes both: only the z-fused staged pipeline launches the
-// split kernel (zstage3), only the persistent kernel writes the flag, and an evaluation it serves runs no staged stage.  Each
+// split kernel (zstep_mid), only the persistent kernel writes the flag, and an evaluation it serves runs no staged stage.  Each
 // writes the slot before the host reads it: workgroup 0 stores the flag in phase D of every launch, ahead of the count-out the
 // host waits for, and the host reads it only straight after such a launch; a staged evaluation reads the slot only with
 // kCollectWgcSplit set, i.e. after its own split kernel's reduction.  (The ipc closure's copy also lands there; it reads neither.)

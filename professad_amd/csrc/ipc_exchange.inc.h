@@ -258,14 +258,14 @@ int ipc_arena(ofdft_ctx* c) {
 inline const unsigned* ipc_abort_word(const ofdft_ipc_state* s) { return s->flags + kIpcFlagWords; }
 inline unsigned long long ipc_limit_ticks(const ofdft_ctx* c) { return (unsigned long long)(c->ipc_wait_ms * 1e5); }   // 100 MHz
 
-// one chunk of an exchange: `bytes_per_peer` bytes per peer from `send_region` (the chunk's region of the send buffer S[p ^ 1],
-// [peer]-major) -> block [me] of the same region of every rank's receive buffer R[p ^ 1] (region_off bytes into it), the epoch
-// stamp behind the data.  Runs on the chain's communication stream behind `ready` (recorded on the compute stream after the
-// kernels that wrote the region).  Returns the epoch the consumers of the chunk wait for.
-int ipc_send_chunk(ofdft_ctx* c, int chain, const cplx* send_region, size_t bytes_per_peer, size_t region_off, hipStream_t cs,
-                   hipEvent_t ready, hipEvent_t sent, unsigned* epoch_out) {
+// one chunk of an exchange (the message zstep left): m.bytes per peer from m.send (the chunk's region of the send buffer S[m.land],
+// [peer]-major) -> block [me] of the same region of every rank's receive buffer R[m.land], the epoch stamp behind the data.
+// Runs on the chain's communication stream behind `ready` (recorded on the compute stream after the kernels that wrote the
+// region).  Returns the epoch the consumers of the chunk wait for.
+int ipc_send_chunk(ofdft_ctx* c, int chain, const SlabMsg& m, hipStream_t cs, hipEvent_t ready, hipEvent_t sent, unsigned* epoch_out) {
     ofdft_ipc_state* s = c->ipc;
-    const int w = 2 * chain + (c->recv_parity[chain] ^ 1);
+    const int w = 2 * chain + m.land;
+    const size_t bytes_per_peer = m.bytes, region_off = sizeof(cplx) * (size_t)m.offset;
     IpcPeers recv{}, mail{};
     for (int p = 0; p < s->P; ++p) {
         if (!s->peer[w][p]) return fail(c, OFDFT_ESTATE, "ipc transport: receive buffer %d of rank %d is not attached", w, p);
@@ -278,7 +278,7 @@ int ipc_send_chunk(ofdft_ctx* c, int chain, const cplx* send_region, size_t byte
     HIP_TRY(c, hipStreamWaitEvent(ms, ready, 0));
     const long long vec = (long long)(bytes_per_peer / 16);
     const int bx = (int)std::min<long long>(2048 / s->P + 1, (vec + 255) / 256);
-    OFDFT_LAUNCH(c, ms, "ipc_scatter", ipc_scatter_kernel, dim3(bx, s->P), dim3(256), 0, (const u32x4*)send_region, recv, s->me, vec);
+    OFDFT_LAUNCH(c, ms, "ipc_scatter", ipc_scatter_kernel, dim3(bx, s->P), dim3(256), 0, (const u32x4*)m.send, recv, s->me, vec);
     const unsigned e = s->eval_id * 128u + (++s->ordinal[chain]);
     OFDFT_LAUNCH(c, ms, "ipc_sync", ipc_stamp_kernel, dim3(1), dim3(64), 0, mail, s->P, s->me, chain * 16 + s->me, e);
     HIP_TRY(c, hipEventRecord(sent, ms));
@@ -394,24 +394,20 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
     if (int rc = begin_call(c, st)) return rc;
-    if (!chi_local || !E_terms || !grad_local || !v_work_local) return fail(c, OFDFT_EINVAL, "null argument");
-    if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
+    if (!E_terms || !grad_local || !v_work_local) return fail(c, OFDFT_EINVAL, "null argument");
+    const real* chi = (const real*)chi_local;
+    if (int rc = zrun_begin(c, DenSrc{chi, 0.0, 1, c->d_scal + kScalClosure}, n_electrons, (const real*)vext_local, (real*)v_work_local)) return rc;
     if (c->nranks < 2 || !c->ipc) return fail(c, OFDFT_ESTATE, "ofdft_dist_closure needs a slab-decomposed context with the ipc transport attached");
-    if ((c->mask & OFDFT_ION_ELECTRON) && !vext_local) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
-    if (gga_needs_laplacian(c) && !c->gga_split) return fail(c, OFDFT_EINVAL, "Laplacian-dependent Pauli-Gaussian members need OFDFT_OPT_GGA_SPLIT = 1");
-    if (wts_active(c)) return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional is served by single-GPU contexts");
     ofdft_ipc_state* s = c->ipc;
     for (int w = 0; w < 5; ++w)
         for (int p = 0; p < s->P; ++p)
             if (!s->peer[w][p]) return fail(c, OFDFT_ESTATE, "ipc transport: object %d of rank %d is not attached (ofdft_ipc_export / ofdft_ipc_attach)", w, p);
     if (!ipc_arena_current(c))          // a set_terms that needs bigger buffers than the exported arena invalidates the peers' mappings
         return fail(c, OFDFT_ESTATE, "ipc transport: exchange buffers changed since ofdft_ipc_export (export and attach again on every rank)");
-    const real* chi = (const real*)chi_local;
     // a new evaluation: its number (the same on every rank) seeds every epoch; parities and ordinals start over, so ranks are in
     // step again even after an evaluation that failed half-way
     s->eval_id++;
     s->ordinal[0] = s->ordinal[1] = 0;
-    c->recv_parity[0] = c->recv_parity[1] = 0;
     HIP_TRY(c, hipMemsetAsync(s->d_err, 0, sizeof(int), st));
     // ---- sum chi^2 over all ranks -> closure scale on the device
     const int blocks = enqueue_sum(c, chi, true, st);
@@ -419,57 +415,25 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
     if (int rc = ipc_allreduce(c, 0, c->d_reduced + kSumsqSlot, 1, c->d_reduced + kSumsqSlot, st)) return rc;
     OFDFT_LAUNCH(c, st, "reduce", closure_scale_kernel, dim3(1), dim3(64), 0, c->d_reduced + kSumsqSlot, c->d_scal + kScalClosure,
                  n_electrons, c->vol / (double)c->npts_g);
-    ZRun& r = zrun(c);
-    r.ds = DenSrc{chi, 0.0, 1, c->d_scal + kScalClosure};
-    r.nel = n_electrons;
-    r.vext = (const real*)vext_local;
-    r.v_out = (real*)v_work_local;
-    r.stage[0] = r.stage[1] = 0;
-    r.forked = false;
-    r.closure = false;
-    r.vpart_deferred = false;
-    r.za.v_part_deferred = 0;
-    r.xlist[0].clear();
-    r.xlist[1].clear();
     // ---- the two chains on their own compute streams, each with a communication stream: the scatter of chunk k is enqueued
     // behind the kernels that produced it and runs while the compute stream works on chunk k + 1; consumers wait per chunk
     HIP_TRY(c, hipEventRecord(s->ev_fork, st));
     HIP_TRY(c, hipStreamWaitEvent(s->side, s->ev_fork, 0));
     const int K = c->xc.n;
     unsigned pend[2][16] = {};                  // epoch of the chunk delivery the chain's next consuming step waits for (0: none)
-    for (int step = 1; step <= 6; ++step)
+    for (int step = kStepYFwd; step <= kStepDivYInv; ++step)
         for (int chain = 0; chain < 2; ++chain) {
             hipStream_t cs = chain == 0 ? st : s->side;
-            const bool sends = step == 1 || step == 2 || step == 4 || step == 5;
-            bool sent = false;
             for (int k = 0; k < K; ++k) {
                 if (pend[chain][k]) {           // chunk k of the exchange this step consumes
                     if (int rc = ipc_wait_chunk(c, chain, pend[chain][k], cs, s->ev_sent[chain][k])) return rc;
                     pend[chain][k] = 0;
                 }
-                int rc;
-                switch (step) {
-                    case 1: rc = zstage1(c, cs, chain, k); break;
-                    case 2: rc = zstage2(c, cs, chain, k); break;
-                    case 3: rc = zstage3(c, cs, chain, 1, k); break;
-                    case 4: rc = zstage3(c, cs, chain, 2, k); break;
-                    case 5: rc = zstage4(c, cs, chain, k); break;
-                    default: rc = chain == 0 ? zstage5(c, nullptr, cs, false, 1, k) : 0; break;     // (the divergence belongs to chain 0)
-                }
-                if (rc) return rc;
-                if (sends && !r.xlist[chain].empty()) {
-                    cplx *send, *recv;
-                    if ((rc = dist_buffers(c, chain, &send, &recv))) return rc;
-                    const XcView v = xc_view(c, k);
-                    const size_t narr = r.xlist[chain].size();
-                    const size_t bytes = sizeof(cplx) * (size_t)c->xg.nxl * (size_t)v.arr_sz * narr;
-                    if ((rc = ipc_send_chunk(c, chain, send + narr * v.base1, bytes, sizeof(cplx) * narr * (size_t)v.base1, cs,
-                                             s->ev_ready[chain][k], s->ev_sent[chain][k], &pend[chain][k])))
-                        return rc;
-                    sent = true;
-                }
+                SlabMsg m;
+                if (int rc = zstep(c, cs, step, chain, k, &m)) return rc;
+                if (m.bytes)
+                    if (int rc = ipc_send_chunk(c, chain, m, cs, s->ev_ready[chain][k], s->ev_sent[chain][k], &pend[chain][k])) return rc;
             }
-            if (sent) c->recv_parity[chain] ^= 1;      // the chain's next step reads what was just sent
         }
     // the divergence (chain 0, step 6) has been y-inverted chunk by chunk; join the nonlocal chain and the communication streams
     HIP_TRY(c, hipEventRecord(s->ev_join, s->side));
@@ -478,9 +442,9 @@ int ofdft_dist_closure(ofdft_ctx* c, const void* chi_local, const void* vext_loc
         HIP_TRY(c, hipEventRecord(s->ev_cjoin[ch], s->comm[ch]));
         HIP_TRY(c, hipStreamWaitEvent(st, s->ev_cjoin[ch], 0));
     }
-    if (int rc = zstage5(c, nullptr, st, false, 2)) return rc;     // combine; local sums -> d_reduced[0 .. kNSums - 1]
+    if (int rc = zcombine(c, nullptr, st)) return rc;     // combine; local sums -> d_reduced[0 .. kNSums - 1]
     // one double more than the sums, as since the commit that added this routine (kNSums was 13 then too; only its comment said
-    // "(12)"); it carries nothing: zstage5 folds the split WGC99 sum into d_reduced[kSumWgc], nothing writes d_reduced[kNSums]
+    // "(12)"); it carries nothing: zcombine folds the split WGC99 sum into d_reduced[kSumWgc], nothing writes d_reduced[kNSums]
     constexpr int kIpcReducedCount = kNSums + 1;
     if (int rc = ipc_allreduce(c, 1, c->d_reduced, kIpcReducedCount, c->d_reduced, st)) return rc;
     enqueue_chi_grad(c, ChiGrad{chi, (const real*)v_work_local, (real*)grad_local, 0.0, 0.0, n_electrons}, st);

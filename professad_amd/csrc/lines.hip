@@ -101,12 +101,6 @@ int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStrea
     if (narr > 16) return fail(c, OFDFT_EINVAL, "too many spectra in one exchange (%d)", narr);
     ArrList arrs{};
     for (int a = 0; a < narr; ++a) arrs.p[a] = list[a];
-    if (xk == -1 && c->xc.n > 1) {          // every chunk, one launch each
-        for (int k = 0; k < c->xc.n; ++k)
-            if (int rc = ypass_xchg<INV>(c, list, buf, st, k)) return rc;
-        return 0;
-    }
-    if (xk == -1) xk = 0;
 #define OFDFT_CASE(L) case L: return launch_ypass_xchg_t<L, INV>(c, arrs, narr, buf, st, xk);
     switch (c->n1) {
         OFDFT_CASE(8) OFDFT_CASE(16) OFDFT_CASE(32) OFDFT_CASE(64) OFDFT_CASE(128) OFDFT_CASE(256) OFDFT_CASE(512)

@@ -320,11 +320,11 @@ class HipStages(Engine):
                                               C.c_void_p(v_out.data_ptr() if v_out is not None else 0), self._stream()),
                     'ofdft_dist_begin')
 
-    def stage(self, k, chain):
-        """-> None or (send, recv) flat uint8 device tensors of nranks * bytes_per_peer bytes"""
+    def _advance(self, name, *where):
+        """ofdft_dist_step / ofdft_dist_stage -> None or (send, recv) flat uint8 device tensors over the region to exchange,
+        nranks * bytes_per_peer bytes each"""
         nbytes, sp, rp = C.c_ulonglong(0), C.c_void_p(0), C.c_void_p(0)
-        self._check(self.lib.ofdft_dist_stage(self._ctx, int(k), int(chain), self._stream(), C.byref(nbytes), C.byref(sp),
-                                              C.byref(rp)), 'ofdft_dist_stage')
+        self._check(getattr(self.lib, name)(self._ctx, *map(int, where), self._stream(), C.byref(nbytes), C.byref(sp), C.byref(rp)), name)
         if nbytes.value == 0:
             return None
         tot = nbytes.value * self.plan.nranks
@@ -334,6 +334,10 @@ class HipStages(Engine):
             ex = self._xbuf[key] = (torch.as_tensor(_RawDeviceBuffer(sp.value, tot), device=self.device),
                                     torch.as_tensor(_RawDeviceBuffer(rp.value, tot), device=self.device))
         return ex
+
+    def stage(self, k, chain):
+        """whole stage k = 1..4 of a chain, the one-chunk shorthand (ofdft_dist_stage: steps 1, 2, 3 + 4, 5; see include/ofdft_hip.h)"""
+        return self._advance('ofdft_dist_stage', k, chain)
 
     @property
     def nchunks(self):
@@ -349,19 +353,8 @@ class HipStages(Engine):
 
     def step(self, step, chain, chunk):
         """one (step, chunk) of a chain of the kz-chunked evaluation (ofdft_dist_step; steps 1..6, see include/ofdft_hip.h)
-        -> None or (send, recv) flat uint8 device tensors over the chunk's region, nranks * bytes_per_peer bytes each"""
-        nbytes, sp, rp = C.c_ulonglong(0), C.c_void_p(0), C.c_void_p(0)
-        self._check(self.lib.ofdft_dist_step(self._ctx, int(step), int(chain), int(chunk), self._stream(), C.byref(nbytes), C.byref(sp),
-                                             C.byref(rp)), 'ofdft_dist_step')
-        if nbytes.value == 0:
-            return None
-        tot = nbytes.value * self.plan.nranks
-        key = (sp.value, rp.value, tot)
-        ex = self._xbuf.get(key)
-        if ex is None:           # the engine reuses its buffers: wrap each (pointer, size) once
-            ex = self._xbuf[key] = (torch.as_tensor(_RawDeviceBuffer(sp.value, tot), device=self.device),
-                                    torch.as_tensor(_RawDeviceBuffer(rp.value, tot), device=self.device))
-        return ex
+        -> None or (send, recv) over the chunk's region"""
+        return self._advance('ofdft_dist_step', step, chain, chunk)
 
     def finish(self, on_device=False):
         """the NSUMS local sums: as a numpy vector, or left in device_scalars[0:NSUMS] without a host sync"""

@@ -178,40 +178,34 @@ class LocalRanks:
 
     legacy_stage_api = False      # True: sequence with ofdft_dist_stage (whole stages; one chunk only) instead of ofdft_dist_step
 
-    def _stages_legacy(self):
+    def advance(self, how, *where):
+        """`how` = 'step' (step, chain, chunk) or 'stage' (stage, chain) on every rank, then the equal-split all-to-all over the
+        region the ranks returned (nothing when nothing crosses)"""
         P = self.P
-        for k in (1, 2, 3, 4):
-            for chain in (0, 1):
-                ex = [self._timed(r, s.stage, k, chain) for r, s in enumerate(self.st)]
-                if ex[0] is None:
-                    continue
-                self.exchanged_bytes += sum(e[0].numel() for e in ex)
-                for r in range(P):
-                    rc = ex[r][1].chunk(P)
-                    for p in range(P):
-                        rc[p].copy_(ex[p][0].chunk(P)[r])
+        ex = [self._timed(r, getattr(s, how), *where) for r, s in enumerate(self.st)]
+        if ex[0] is None:
+            return
+        self.exchanged_bytes += sum(e[0].numel() for e in ex)
+        for r in range(P):
+            rc = ex[r][1].chunk(P)
+            for p in range(P):
+                rc[p].copy_(ex[p][0].chunk(P)[r])
+
+    def finish(self):
         return sum(self._timed(r, s.finish) for r, s in enumerate(self.st))
 
     def _stages(self):
         if self.legacy_stage_api:
-            return self._stages_legacy()
-        P = self.P
-        K = self.st[0].nchunks
-        for step in (1, 2, 3, 4, 5, 6):
-            for chain in (0, 1):
-                for k in range(K):         # chunk k of the exchange: one equal-split all-to-all over the chunk's region
-                    ex = [self._timed(r, s.step, step, chain, k) for r, s in enumerate(self.st)]
-                    if ex[0] is None:
-                        continue
-                    self.exchanged_bytes += sum(e[0].numel() for e in ex)
-                    for r in range(P):
-                        rc = ex[r][1].chunk(P)
-                        for p in range(P):
-                            rc[p].copy_(ex[p][0].chunk(P)[r])
-        return sum(self._timed(r, s.finish) for r, s in enumerate(self.st))
+            calls = [('stage', k, chain) for k in (1, 2, 3, 4) for chain in (0, 1)]
+        else:              # chunk k of the exchange: one equal-split all-to-all over the chunk's region
+            calls = [('step', step, chain, k) for step in (1, 2, 3, 4, 5, 6) for chain in (0, 1) for k in range(self.st[0].nchunks)]
+        for call in calls:
+            self.advance(*call)
+        return self.finish()
 
-    def closure(self, chi, n_elec, vext):
-        """full-grid chi / v_ext (device tensors) -> (E_terms, mu, full-grid dE/dchi)"""
+    def closure(self, chi, n_elec, vext, sequence=None):
+        """full-grid chi / v_ext (device tensors) -> (E_terms, mu, full-grid dE/dchi); `sequence`: what runs between the ranks'
+        begin and the energies in place of `_stages` (calls of `advance`, then `finish`, whose sums it returns)"""
         sl = [s.plan.x_range() for s in self.st]
         chis = [chi[x].contiguous() for x in sl]
         vexts = [vext[x].contiguous() if vext is not None else None for x in sl]
@@ -220,7 +214,7 @@ class LocalRanks:
         vs = [torch.empty_like(c) for c in chis]
         for r, s in enumerate(self.st):
             self._timed(r, s.begin, chis[r], True, cscale, n_elec, vexts[r], vs[r])
-        gs = self._stages()
+        gs = (sequence or self._stages)()
         out = []
         for r, s in enumerate(self.st):
             E, vn = s.energies(gs)

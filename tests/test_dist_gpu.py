@@ -241,6 +241,123 @@ def test_whole_stage_entry_point_equals_the_step_sequence():
     loc.close()
 
 
+# ---- the step sequencer (zstep): order checks, the shared reset, stage / step mixing, pinned launch sequence.  Two emulated ranks
+# on 64^3 -- the smallest grid on which two kz chunks are honoured (nxl, nyl multiples of 32; four kz blocks) -- with both chains
+# and a GGA term, so that steps 4 to 6 carry data.
+SEQ_SHAPE, SEQ_RANKS = (64, 64, 64), 2
+_SEQ = {}
+
+
+def _seq_case():
+    """inputs and term set of the sequencer tests (built once)"""
+    if 'case' not in _SEQ:
+        import numpy as np
+        import torch
+        sys.path.insert(0, os.path.join(HERE, 'golden'))
+        import cases
+        from professad_amd import synth
+        from professad_amd.functionals import NativeTerms
+        dev = torch.device('cuda:0')
+        box = torch.as_tensor(cases.make_cell(('tri', SEQ_SHAPE[0] / 16.0)))
+        den = synth.random_density(SEQ_SHAPE, seed=41)
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.double, device=dev)  # noqa: E731
+        chi = t(np.sqrt(den) * (1 + 0.1 * np.random.default_rng(43).random(SEQ_SHAPE)))
+        vext = t(synth.random_potential(SEQ_SHAPE, seed=42))
+        n_elec = float(np.floor(den.mean() * abs(np.linalg.det(box.numpy()))) + 0.3)
+        _SEQ['case'] = (dev, box, chi, vext, n_elec, NativeTerms(['ion_electron', 'hartree', 'wgc99', 'pbe']).names)
+    return _SEQ['case']
+
+
+def _seq_ranks(K):
+    from local_ranks import LocalRanks
+    dev, box, _, _, _, names = _seq_case()
+    loc = LocalRanks(SEQ_SHAPE, dev, SEQ_RANKS).set_cell(box).set_terms(names).set_xchg_chunks(K)
+    assert loc.st[0].nchunks == K
+    return loc
+
+
+def _seq_fresh(K):
+    """the closure on fresh emulated ranks with K chunks -> ((E, mu, grad), rank 0's (launches, FFTs, y passes)); computed once"""
+    if K not in _SEQ:
+        _, _, chi, vext, n_elec, _ = _seq_case()
+        loc = _seq_ranks(K)
+        res = loc.closure(chi, n_elec, vext)
+        _SEQ[K] = (res, tuple(round(loc.st[0].query(q)) for q in (4, 0, 5)))      # OFDFT_Q_LAUNCH_COUNT, _FFT_COUNT, _YPASS_COUNT
+        loc.close()
+    return _SEQ[K]
+
+
+class _Abandoned(Exception):
+    pass
+
+
+def _seq_same(a, b):
+    import torch
+    return all(a[0][k] == b[0][k] for k in a[0]) and a[1] == b[1] and torch.equal(a[2], b[2])
+
+
+def test_out_of_order_calls_are_refused_and_leave_nothing_behind():
+    """ofdft_dist_step / ofdft_dist_finish out of order return OFDFT_ESTATE with the message that names the order; after every
+    refusal a complete evaluation on the SAME contexts is bitwise the one of fresh contexts (the one reset, zrun_begin)"""
+    K = 2
+    _, _, chi, vext, n_elec, _ = _seq_case()
+    fresh, _ = _seq_fresh(K)
+    loc = _seq_ranks(K)
+    upto5 = [('step', step, chain, k) for step in (1, 2, 3, 4, 5) for chain in (0, 1) for k in range(K)]
+    refused = {
+        'step 2 before step 1': ([], ('step', 2, 0, 0), 'out of order'),
+        'chunk 1 before chunk 0': ([], ('step', 1, 0, 1), 'out of order'),
+        'chain 1 before step 1 of chain 0': ([], ('step', 1, 1, 0), 'out of order'),
+        'finish after step 5': (upto5, None, 'before step 6'),
+        'finish before any step': ([], None, 'before step 6'),
+    }
+    for what, (calls, bad, msg) in refused.items():
+        def sequence():
+            for call in calls:
+                loc.advance(*call)
+            with pytest.raises(RuntimeError, match=msg):
+                loc.advance(*bad) if bad else loc.finish()
+            raise _Abandoned          # (nothing to turn into energies: leave `closure` here)
+        with pytest.raises(_Abandoned):
+            loc.closure(chi, n_elec, vext, sequence)
+        assert _seq_same(loc.closure(chi, n_elec, vext), fresh), what
+    loc.close()
+
+
+def test_stage_and_step_calls_mix_within_one_evaluation():
+    """stages 1 and 2 through ofdft_dist_stage, steps 3 to 6 through ofdft_dist_step, then finish: bitwise the pure step sequence"""
+    _, _, chi, vext, n_elec, _ = _seq_case()
+    pure, _ = _seq_fresh(1)
+    loc = _seq_ranks(1)
+
+    def sequence():
+        for call in ([('stage', k, chain) for k in (1, 2) for chain in (0, 1)]
+                     + [('step', step, chain, 0) for step in (3, 4, 5, 6) for chain in (0, 1)]):
+            loc.advance(*call)
+        return loc.finish()
+    assert _seq_same(loc.closure(chi, n_elec, vext, sequence), pure)
+    assert _seq_same(loc.closure(chi, n_elec, vext), pure)          # ... and the plain sequence after it
+    loc.close()
+
+
+def test_launch_sequence_of_the_slab_and_the_single_gpu_evaluation_is_pinned():
+    """(launches, FFTs, y passes) of one closure evaluation as the build of commit a59865a reports them -- the last before the
+    drivers shared one sequencer: rank 0 of two ranks with one and two kz chunks, and one engine on the same grid with the
+    persistent kernel and the graph off"""
+    from professad_amd import _native as N
+    from professad_amd.engine import Engine
+    dev, box, chi, vext, n_elec, names = _seq_case()
+    assert _seq_fresh(1)[1] == (23, 23, 19)
+    assert _seq_fresh(2)[1] == (34, 23, 19)          # (eleven more launches: the chunked y passes and x passes)
+    ref = Engine(SEQ_SHAPE, dev).set_cell(box).set_terms(names)
+    ref.set_option(N.OPT_GRAPH, 0).set_option(N.OPT_RESIDENT, 0)
+    ref.energy_grad_chi(chi, n_elec, vext)
+    one = tuple(round(ref.query(q)) for q in (N.Q_LAUNCH_COUNT, N.Q_FFT_COUNT, N.Q_YPASS_COUNT))
+    ref.close()
+    assert one == (26, 23, 15)
+    assert _seq_fresh(1)[1][1] == one[1] and _seq_fresh(2)[1][1] == one[1]
+
+
 def test_eight_rank_geometry_with_the_laplacian_dependent_pauli_gaussian():
     """PGSL0.25 + Hartree + PBE over 8 emulated slab ranks (lap n and df/dL cross the exchange beside the GGA spectra)"""
     import numpy as np
