@@ -216,8 +216,21 @@ __device__ __forceinline__ void kvec(const KGeom& kg, long long i, real& kx, rea
 
 // 1/G^-1(eta) - 3 eta^2 - 1 (functionals.py:617-628,648), fp64: the reference's own form, with the lean logarithm and
 // reciprocal of fastmath.h (the library log + two IEEE quotients were ~200 fp64 instructions per k-point of the
-// Wang-Teter x pass; this is ~60)
+// Wang-Teter x pass; this is ~60).  For large eta that form cancels twice -- G^-1 = 0.5 + (-0.5 + O(eta^-2)), then 1 / G^-1 against
+// 3 eta^2 -- and carries an absolute error that grows as eta^4: 1e-13 at eta = 3, 2e-12 at 6, 6.5e-11 at 12 (a rough density on a
+// 0.24 bohr grid reaches 12), which was 5-8e-12 of the potential of the nonlocal term taken alone.  From eta = 3 on the series of
+// the fp32 form below is used instead, f = -3 V / R - 1 in z = eta^-2 <= 1/9 with 18 terms (tail 9^-18): no cancellation, a few ulp.
 __device__ __forceinline__ double lindhard_shape(double eta) {
+    if (eta >= 3.0) {
+        const double z = fm::rcp(eta * eta);
+        double r = 1.0 / (4.0 * 18 * 18 - 1.0), v = 1.0 / (4.0 * 19 * 19 - 1.0);
+#pragma unroll
+        for (int j = 17; j >= 1; --j) {
+            r = __builtin_fma(r, z, 1.0 / (4.0 * j * j - 1.0));                   // R = c_1 + c_2 z + ... + c_18 z^17,  c_j = 1 / (4 j^2 - 1)
+            v = __builtin_fma(v, z, 1.0 / (4.0 * (j + 1) * (j + 1) - 1.0));       // V = c_2 + c_3 z + ... + c_19 z^17
+        }
+        return __builtin_fma(-3.0 * v, fm::rcp(r), -1.0);
+    }
     double ginv;
     if (eta == 0.0) ginv = 1.0;
     else if (eta == 1.0) ginv = 0.5;
