@@ -374,6 +374,48 @@ int  ofdft_ion_electron_curvature(ofdft_ctx* ctx, const void* den_dev, const dou
 int  ofdft_ion_ion_hessian(ofdft_ctx* ctx, const double* frac_coords_host, const double* charges_host, int nions, double Rc,
                            const int* rows_host, int nrows, double* hess_host /* [nrows][nions][3][3] */, void* stream);
 
+/* ---- second strain derivative at fixed chi (the fixed-chi part of the elastic constants) --------------------------
+ * The cell is strained as h -> h (I + eps) with a general eps at fixed fractional ion coordinates, fixed grid values of chi and
+ * fixed N, so the density scales as 1 / det(I + eps).  Each entry returns d^2 E / d eps_mn d eps_pq at eps = 0 as [3][3][3][3]
+ * row-major in (m, n, p, q), Ha -- what torch.autograd.functional.hessian gives in eps through the closure of
+ * System.__compute_elastic_constants (system.py:1266-1273) with chi held fixed.  fp64, single GPU, exact structure factor;
+ * reductions by wavefront shuffles and a fixed-order host sum: bitwise reproducible.  Each clears the retained fields of
+ * ofdft_hessian_vector.
+ *
+ * ofdft_strain_hessian: the reciprocal-space terms of the active set (hartree, vw, wt_nl) at the density den_dev; the other
+ * entries of w2_terms_host are zero (tf, lda_x and the LDA correlations depend on det(I + eps) alone: E_J from the trace of
+ * ofdft_stress, E_JJ = n.H_t n from ofdft_hessian_vector).  Refuses what ofdft_hessian_vector refuses, by name. */
+int  ofdft_strain_hessian(ofdft_ctx* ctx, const void* den_dev, double* w2_terms_host /* [OFDFT_NTERMS][81] */, void* stream);
+
+/* ---- strain gradient of the potential (the coupling of the strain to the density response) ------------------------
+ * v_eps,kl(r), kl = xx, yy, zz, yz, xz, xy: the derivative of the potential v = dE/dn of the active terms with respect to
+ * eps_kl at FIXED grid values of the density, the mean density of the Wang-Teter kernel following the cell (n0 = N / vol):
+ *   hartree  F^-1[8 pi k_k k_l n^ / k^4];   vw  -F^-1[k_k k_l chi^] / chi;
+ *   wt_nl    c_TF [alpha n^(alpha-1) K'_kl * n^beta + beta n^(beta-1) K'_kl * n^alpha],
+ *            K'_kl = pref [delta_kl ((alpha + beta - 5/3) F + eta F' / 3) - eta F' k_k k_l / k^2];
+ * tf, lda_x and the LDA correlations have no explicit part.  The total strain derivative of the potential at fixed chi is
+ * V_kl = v_eps,kl - delta_kl hv(n, n) (ofdft_hessian_vector), since n ~ 1 / det(I + eps).  One forward and six inverse
+ * transforms per family (OFDFT_Q_FFT_COUNT: 3 + 18 for hartree + vw + wt_nl with alpha = beta).  Refuses what
+ * ofdft_hessian_vector refuses. */
+int  ofdft_potential_strain_gradient(ofdft_ctx* ctx, const void* den_dev, void* out6_dev /* [6][n0][n1][n2] */, void* stream);
+
+/* The same for v_ext of one species at fixed fractional coordinates (arguments of ofdft_ionic_potential):
+ *   -delta_kl v_ext + F^-1[S v~'(|k|) (-k_k k_l / |k|)] / vol,  v~' = 0 past the table end.  PME refused. */
+int  ofdft_ionic_potential_strain_gradient(ofdft_ctx* ctx, const double* frac_coords_host, int nions, const double* table_k_host,
+                                           const double* table_v_host, int ntable, double z_ion, int pme_order,
+                                           void* out6_dev /* [6][n0][n1][n2] */, void* stream);
+
+/* The ion-electron energy of one species, the potential rebuilt from the ions in the strained cell (arguments of
+ * ofdft_ion_electron_stress).  PME refused. */
+int  ofdft_ion_electron_strain_hessian(ofdft_ctx* ctx, const void* den_dev, const double* frac_coords_host, int nions,
+                                       const double* table_k_host, const double* table_v_host, int ntable, double z_ion,
+                                       int pme_order, double* w2_host /* [81] */, void* stream);
+
+/* The ion-ion energy over the fixed pair list of ofdft_ion_ion; Rd and Rc are constants of the differentiation (the reference
+ * takes h_max from box_vecs.detach()), the background term varies through rho ~ 1/J and R_a ~ J^(1/3). */
+int  ofdft_ion_ion_strain_hessian(ofdft_ctx* ctx, const double* frac_coords_host, const double* charges_host, int nions, double Rc,
+                                  double* w2_host /* [81] */, void* stream);
+
 /* ---- limited-memory BFGS building blocks (the consumer of the closure) ----------------
  * The reference's fixed-step optimiser (_optimizers/lbfgs/lbfgsnew.py:594-663) forms y = g - g_prev and s = t d, keeps
  * the pair if y.s > 1e-10 |s|^2, and gets the direction from the two-loop recursion: 2m dependent dot / axpy pairs over

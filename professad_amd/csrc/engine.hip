@@ -9,6 +9,7 @@
 #include "stress_kernels.h"
 #include "hvp_kernels.h"
 #include "fc_kernels.h"
+#include "strain2_kernels.h"
 #endif
 
 namespace {
@@ -1607,6 +1608,7 @@ int ofdft_dist_chi_grad(ofdft_ctx* c, const void* chi_local, const void* v_local
 #include "engine_ion_cells.inc.h"
 #include "engine_hvp.inc.h"
 #include "engine_force_constants.inc.h"
+#include "engine_strain.inc.h"
 #else
 // The fp32 build serves the density-optimisation hot path only.  The once-per-geometry-step quantities (ionic potential,
 // forces, stress, ion-ion sum) are fp64 work: callers run them on the fp64 library (professad_amd.ions does).
@@ -1642,6 +1644,16 @@ int ofdft_ion_electron_curvature(ofdft_ctx* c, const void*, const double*, int, 
 int ofdft_ion_ion_hessian(ofdft_ctx* c, const double*, const double*, int, double, const int*, int, double*, void*) {
     return OFDFT_F64_ONLY(c);
 }
+int ofdft_potential_strain_gradient(ofdft_ctx* c, const void*, void*, void*) { return OFDFT_F64_ONLY(c); }
+int ofdft_ionic_potential_strain_gradient(ofdft_ctx* c, const double*, int, const double*, const double*, int, double, int, void*, void*) {
+    return OFDFT_F64_ONLY(c);
+}
+int ofdft_strain_hessian(ofdft_ctx* c, const void*, double*, void*) { return OFDFT_F64_ONLY(c); }
+int ofdft_ion_electron_strain_hessian(ofdft_ctx* c, const void*, const double*, int, const double*, const double*, int, double, int, double*,
+                                      void*) {
+    return OFDFT_F64_ONLY(c);
+}
+int ofdft_ion_ion_strain_hessian(ofdft_ctx* c, const double*, const double*, int, double, double*, void*) { return OFDFT_F64_ONLY(c); }
 }
 #endif
 

@@ -268,6 +268,43 @@ class Engine:
         a = np.array(list(buf), dtype=np.float64).reshape(N.NTERMS, 3, 3)
         return N.per_term(a, self._mask())
 
+    def potential_strain_gradient(self, den):
+        """v_eps,kl, kl = xx, yy, zz, yz, xz, xy -> [6, n0, n1, n2]: the derivative of the potential dE/dn of the active terms
+        with respect to the strain eps_kl (h -> h (I + eps)) at fixed grid values of ``den``, the mean density of the
+        Wang-Teter kernel following the cell (ofdft_potential_strain_gradient).  ion_electron contributes
+        nothing here (ions.ionic_potential_strain_gradient).  Single GPU and fp64, the terms of ``hessian_vector``."""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.potential_strain_gradient is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+        den = self._grid_tensor(den, 'den')
+        out = torch.empty((6,) + tuple(den.shape), dtype=den.dtype, device=den.device)
+        self._check(self.lib.ofdft_potential_strain_gradient(self._ctx, _ptr(den), _ptr(out), self._stream()),
+                    'ofdft_potential_strain_gradient')
+        return out
+
+    def strain_hessian(self, den):
+        """{term name: [3, 3, 3, 3] numpy array, Ha}: d^2 E_t / d eps_mn d eps_pq at eps = 0 under h -> h (I + eps) at fixed grid
+        values of chi and fixed N, so that the density scales as 1 / det(I + eps).  hartree, vw and wt_nl come
+        from ofdft_strain_hessian; tf, lda_x and the LDA correlations depend on J = det(I + eps) alone:
+        E_J (d_mn d_pq - d_mq d_np) + E_JJ d_mn d_pq with E_J = vol tr(sigma_t) / 3 (``stress``) and E_JJ = int n (H_t n)
+        (``hessian_vector``); with several correlation terms active their entries carry the shares ``stress`` gives them, and only
+        their sum is meaningful.  The ion_electron entry is zero (ions.ion_electron_strain_hessian).  Single GPU and fp64."""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.strain_hessian is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+        den = self._grid_tensor(den, 'den')
+        buf = (C.c_double * (N.NTERMS * 81))()
+        self._check(self.lib.ofdft_strain_hessian(self._ctx, _ptr(den), buf, self._stream()), 'ofdft_strain_hessian')
+        out = N.per_term(np.array(list(buf), dtype=np.float64).reshape(N.NTERMS, 3, 3, 3, 3), self._mask())
+        local = [t for t in ('tf', 'lda_x', 'pz_c', 'pw_c', 'chachiyo_c') if self._mask() & N.TERM_BITS[t]]
+        if local:
+            sig = self.stress(den)
+            q, _hv = self.hessian_vector(den, den, want_terms=True)
+            eye = np.eye(3)
+            dd, dx = np.einsum('mn,pq->mnpq', eye, eye), np.einsum('mq,np->mnpq', eye, eye)
+            for t in local:
+                E_J = self.volume * float(np.trace(sig[t])) / 3.0
+                out[t] = E_J * (dd - dx) + float(q[t]) * dd
+        return out
+
     def set_profiling(self, on):
         self._check(self.lib.ofdft_set_profiling(self._ctx, 1 if on else 0), 'ofdft_set_profiling')
 

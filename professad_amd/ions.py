@@ -309,3 +309,71 @@ def ion_ion_hessian(engine, box_vecs, frac, charges, rows, Rc=None):
                                           H.ctypes.data_as(dp), engine._stream())
     engine._check(rc, 'ofdft_ion_ion_hessian')
     return H
+
+
+# ---------------------------------------------------------------------------------------------------- strain derivatives
+def _pme_refusal(who, pme_order):
+    if pme_order:
+        raise NotImplementedError('%s: particle-mesh Ewald (PME, pme_order=%r) is not served; use the exact structure factor '
+                                  '(pme_order=None)' % (who, pme_order))
+
+
+def ionic_potential_strain_gradient(engine, box_vecs, species, pme_order=None):
+    """d v_ext / d eps_kl, kl = xx, yy, zz, yz, xz, xy, under h -> h (I + eps) at fixed fractional coordinates -> [6, n0, n1, n2]:
+    -delta_kl v_ext + F^-1[S v~'(|k|) (-k_k k_l / |k|)] / vol summed over the species (`ofdft_ionic_potential_strain_gradient`;
+    DESIGN.md §9e).  Exact structure factor only.  Plain fp64 work: an fp32 engine hands it to its fp64 sibling."""
+    _pme_refusal('ionic_potential_strain_gradient', pme_order)
+    want = engine.dtype
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    total = None
+    dp = C.POINTER(C.c_double)
+    for frac, tab in species:
+        frac, ks, v, z = _species_arrays(frac, tab)
+        out = torch.empty((6,) + tuple(engine.shape), dtype=torch.double, device=engine._dev_exact)
+        rc = engine.lib.ofdft_ionic_potential_strain_gradient(engine._ctx, frac.ctypes.data_as(dp), frac.shape[0], ks.ctypes.data_as(dp),
+                                                              v.ctypes.data_as(dp), ks.size, z, 0, C.c_void_p(out.data_ptr()),
+                                                              engine._stream())
+        engine._check(rc, 'ofdft_ionic_potential_strain_gradient')
+        total = out if total is None else total + out
+    return total.to(want)
+
+
+def ion_electron_strain_hessian(engine, box_vecs, den, species, pme_order=None):
+    """d^2 (int n v_ext) / d eps_mn d eps_pq -> [3, 3, 3, 3] (Ha) at fixed grid values of chi (n ~ 1 / det(I + eps)) and fixed
+    fractional coordinates, the potential rebuilt from the ions in the strained cell, summed over the species
+    (`ofdft_ion_electron_strain_hessian`).  fp64 engines only: the density is the engine's own, as for `Engine.stress`."""
+    _pme_refusal('ion_electron_strain_hessian', pme_order)
+    if engine.dtype != torch.double:
+        raise NotImplementedError('ion_electron_strain_hessian is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+    den = engine._grid_tensor(den, 'den')
+    engine.set_cell(box_vecs)
+    dp = C.POINTER(C.c_double)
+    total = np.zeros(81)
+    for frac, tab in species:
+        frac, ks, v, z = _species_arrays(frac, tab)
+        w = np.zeros(81)
+        rc = engine.lib.ofdft_ion_electron_strain_hessian(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
+                                                          ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, z, 0, w.ctypes.data_as(dp),
+                                                          engine._stream())
+        engine._check(rc, 'ofdft_ion_electron_strain_hessian')
+        total += w
+    return total.reshape(3, 3, 3, 3)
+
+
+def ion_ion_strain_hessian(engine, box_vecs, frac, charges, Rc=None):
+    """d^2 E_ion-ion / d eps_mn d eps_pq -> [3, 3, 3, 3] (Ha) at fixed fractional coordinates: the pair sum over the fixed pair list
+    of `ion_ion(method='direct')` with Rd and Rc held (the reference takes h_max from box_vecs.detach()), plus the background
+    term through rho ~ 1/J and R_a ~ J^(1/3) (`ofdft_ion_ion_strain_hessian`).  Plain fp64 work."""
+    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
+    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
+    if z.size != frac.shape[0]:
+        raise ValueError('one charge per ion')
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    dp = C.POINTER(C.c_double)
+    w = np.zeros(81)
+    rc = engine.lib.ofdft_ion_ion_strain_hessian(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
+                                                 float(Rc) if Rc else 0.0, w.ctypes.data_as(dp), engine._stream())
+    engine._check(rc, 'ofdft_ion_ion_strain_hessian')
+    return w.reshape(3, 3, 3, 3)
