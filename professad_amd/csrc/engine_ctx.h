@@ -152,7 +152,10 @@ struct ofdft_ctx {
     ofdft_all_reduce_fn allreduce = nullptr;
     void* coll_user = nullptr;
     // ofdft_hessian_vector: the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) of the last call made with reuse_density = 0
-    // stay in workspaces of their own ("hv:lap", "hv:A", "hv:B"); set_cell / set_terms / set_option and every other evaluation clear the flag
+    // stay in workspaces of their own ("hv:lap", "hv:A", "hv:B").  set_cell / set_terms / set_option clear the flag, and so does every
+    // entry that goes through begin_call (the evaluations, ofdft_stress) and every second-order entry (force constants, strain).  The
+    // first-order ion entries (ofdft_ionic_potential, ofdft_ion_electron_forces, ofdft_ion_electron_stress, ofdft_ion_ion,
+    // ofdft_ion_ion_cells) leave it: they write no "hv:*" workspace, so the fields stay good.  Table: DESIGN.md §9f.
     // (0: nothing retained; 1: by ofdft_hessian_vector; 2: by ofdft_hessian_vector_chi, whose fields belong to n[phi] -- engine_hvp.inc.h)
     unsigned char hvp_valid = false;
     double hvp_chi_S = 0.0;            // sum phi^2 of the chi-space call that retained them
@@ -272,6 +275,28 @@ inline TermScalars term_scalars(const ofdft_ctx* c, double nel) {
         t.tc.wgc_sum_53 = (std::fabs(al + be - kFiveThirds) < 4e-16) ? 1 : 0;
     }
     return t;
+}
+// C_TF = 0.3 (3 pi^2)^(2/3) as the host forms it.  (The kernels' literal kCtf may differ from it in the last bit: no substitute.)
+inline double ctf_host() { return 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0); }
+// Host scalars of the Wang-Teter moment sections of the per-geometry-step entries (ofdft_stress, ofdft_strain_hessian,
+// ofdft_potential_strain_gradient).  nbar is the caller's nsum / N, straight from the device sum: ts.nbar = (nsum dV) / vol may
+// differ from it in the last bit, which is also why wt_kf / wt_pref above do not serve here.
+struct WtMoment {
+    double q = 0.0;            // alpha + beta - 5/3: nbar's exponent in the prefactor
+    double kf = 0.0;           // (3 pi^2 nbar)^(1/3)
+    double inv2kf = 0.0;       // eta = |k| inv2kf
+    double pref = 0.0;         // 5 / (9 alpha beta nbar^q)
+    double pref_ctf = 0.0;     // C_TF 5 / (9 alpha beta nbar^q), C_TF multiplied in first (not C_TF pref: another rounding)
+};
+inline WtMoment wt_moment(const TermScalars& ts, double nbar) {
+    const double al = ts.nlp.al, be = ts.nlp.be;
+    WtMoment w;
+    w.q = al + be - 5.0 / 3.0;
+    w.kf = std::cbrt(3.0 * kPi * kPi * nbar);
+    w.inv2kf = 1.0 / (2.0 * w.kf);
+    w.pref = 5.0 / (9.0 * al * be * std::pow(nbar, w.q));
+    w.pref_ctf = ctf_host() * 5.0 / (9.0 * al * be * std::pow(nbar, w.q));
+    return w;
 }
 inline bool zfused_serves(const ofdft_ctx* c) {
     return c->fast && c->pipeline == 0 && c->n2 / 2 <= 512 && (!gga_needs_laplacian(c) || c->gga_split);

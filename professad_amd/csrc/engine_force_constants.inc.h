@@ -1,19 +1,8 @@
 // C ABI of the ion-position second derivatives behind the interatomic force constants (fc_kernels.h): the gradient
 // of the ionic potential with respect to one ion, the ion-electron curvature at fixed density and the ion-ion Hessian.  Included
-// once by engine.hip inside its extern "C" block (fp64 library), after engine_ions_stress.inc.h (ion_prepare, ion_ion_setup).
-// Single GPU, exact structure factor; each entry clears hvp_valid, as every evaluation does (the transforms share workspaces).
-namespace {
-
-// the refusals the two potential entries share, before any device work; `who` names the entry in the messages
-int fc_checks(ofdft_ctx* c, int pme_order, const char* who) {
-    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no force constants", who);
-    if (pme_order != 0)
-        return fail(c, OFDFT_EINVAL, "%s: particle-mesh Ewald (PME, pme_order = %d) is not served: the derivative of the B-spline spread "
-                    "is not built; pass pme_order = 0 (exact structure factor)", who, pme_order);
-    return 0;
-}
-
-}  // namespace
+// once by engine.hip inside its extern "C" block (fp64 library), after engine_ions_stress.inc.h (the frames of the ion entries).
+// Single GPU, exact structure factor.  Each entry clears hvp_valid, the fields ofdft_hessian_vector retains for reuse_density = 1,
+// as every second-order entry does: the ABI's convention, not a need (none writes an "hv:*" workspace; table in DESIGN.md §9f).
 
 // d v_ext / d R_{a,j}, j = x, y, z, of the ion a = ion_index of one species (what autograd through lattice_sum yields,
 // ion_utils.py:88-137): one spectral kernel, one batched inverse transform.
@@ -21,12 +10,9 @@ int ofdft_ionic_potential_gradient(ofdft_ctx* c, const double* frac_host, int ni
                                    double z_ion, int pme_order, int ion_index, void* dv_dev, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !tab_k || !tab_v || !dv_dev) return OFDFT_EINVAL;
-    c->hvp_valid = false;
-    if (int rc = fc_checks(c, pme_order, "ofdft_ionic_potential_gradient")) return rc;
-    OFDFT_ON_DEVICE(c, c->device);
-    if (ion_index < 0 || ion_index >= nions) return fail(c, OFDFT_EINVAL, "ofdft_ionic_potential_gradient: ion_index %d outside [0, %d)", ion_index, nions);
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, 0, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ionic_potential_gradient", true, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st, &ion_index))
+        return rc;
     cplx* spec[3];
     real* out[3];
     const char* names[3] = {"fc:g0", "fc:g1", "fc:g2"};
@@ -38,10 +24,7 @@ int ofdft_ionic_potential_gradient(ofdft_ctx* c, const double* frac_host, int ni
     OFDFT_LAUNCH(c, st, "ion_grad_spec", ion_potential_grad_spec_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, spec[0], spec[1], spec[2],
                  c->kg, R[0], R[1], R[2], p.tab, 1.0 / c->vol);
     if (int rc = irfftn_internal_multi(c, spec, out, 3, 1.0, st)) return rc;      // norm='forward': no 1/N  (ion_utils.py:118)
-    HIP_TRY(c, hipStreamSynchronize(st));      // `p` (host staging) must outlive the async copies
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
 // D[a] = d^2 (dV sum_r n v_ext) / dR_a dR_a at fixed n for every ion of one species: one transform of the density, one reduction
@@ -50,11 +33,8 @@ int ofdft_ion_electron_curvature(ofdft_ctx* c, const void* den_dev, const double
                                  const double* tab_v, int ntab, double z_ion, int pme_order, double* curv_host, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !den_dev || !frac_host || !tab_k || !tab_v || !curv_host) return OFDFT_EINVAL;
-    c->hvp_valid = false;
-    if (int rc = fc_checks(c, pme_order, "ofdft_ion_electron_curvature")) return rc;
-    OFDFT_ON_DEVICE(c, c->device);
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, 0, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ion_electron_curvature", true, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
     cplx* sN;
     if (int rc = spec_ws(c, "i:Q", &sN)) return rc;
     if (int rc = rfftn_internal(c, (const double*)den_dev, sN, st)) return rc;
@@ -65,16 +45,10 @@ int ofdft_ion_electron_curvature(ofdft_ctx* c, const void* den_dev, const double
     OFDFT_LAUNCH(c, st, "ion_curvature", ion_curvature_kernel, dim3(kb, nions), dim3(kRedThreads), 0, (const cplx*)sN, c->kg,
                  (const double*)p.d_cart, p.tab, d_part);
     HIP_TRY(c, hipMemcpyAsync(h.data(), d_part, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipGetLastError());
+    if (int rc = ion_finish(c, st)) return rc;
     const double pref = -c->dV / c->vol;
     for (int a = 0; a < nions; ++a)
-        for (int s = 0; s < kIonCurvScalars; ++s) {
-            long double t = 0.0L;
-            for (int b = 0; b < kb; ++b) t += h[((size_t)a * kb + b) * kIonCurvScalars + s];
-            curv_host[kIonCurvScalars * a + s] = pref * (double)t;
-        }
-    if (c->profiling) prof_collect(c);
+        for (int s = 0; s < kIonCurvScalars; ++s) curv_host[kIonCurvScalars * a + s] = pref * (double)chunk_sum(h.data(), a, kb, kIonCurvScalars, s);
     return OFDFT_OK;
 }
 
@@ -86,40 +60,28 @@ int ofdft_ion_ion_hessian(ofdft_ctx* c, const double* frac_host, const double* c
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !charges_host || !rows_host || !hess_host || nions < 1 || nrows < 1) return OFDFT_EINVAL;
     c->hvp_valid = false;
-    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
-    for (int q = 0; q < nrows; ++q)
-        if (rows_host[q] < 0 || rows_host[q] >= nions) return fail(c, OFDFT_EINVAL, "ofdft_ion_ion_hessian: row %d outside [0, %d)", rows_host[q], nions);
+    IonIonCall ii;
+    if (int rc = ion_ion_begin(c, ii, frac_host, nions, Rc)) return rc;
+    for (int k = 0; k < nrows; ++k)
+        if (rows_host[k] < 0 || rows_host[k] >= nions) return fail(c, OFDFT_EINVAL, "ofdft_ion_ion_hessian: row %d outside [0, %d)", rows_host[k], nions);
     if (nrows > 65535) return fail(c, OFDFT_EINVAL, "ofdft_ion_ion_hessian: at most 65535 rows per call");
     OFDFT_ON_DEVICE(c, c->device);
-    IonIonGeom g{};
-    std::vector<double> cart;
-    const long long nshift = ion_ion_setup(c, frac_host, nions, Rc, g, cart);
-    const int chunks = (int)std::min<long long>(256, (nshift + kRedThreads * 8 - 1) / (kRedThreads * 8));
-    double *d_cart, *d_z, *d_part;
+    const int chunks = ion_ion_chunks(ii.nshift);       // one (row, ion) pair per (grid.z, grid.y): the chunks split the shifts alone
     int* d_rows;
-    const size_t np = (size_t)nrows * nions * chunks * kIonHessScalars;
-    if (int rc = get_ws(c, "ii:cart", sizeof(double) * cart.size(), (void**)&d_cart)) return rc;
-    if (int rc = get_ws(c, "ii:z", sizeof(double) * nions, (void**)&d_z)) return rc;
     if (int rc = get_ws(c, "fc:rows", sizeof(int) * nrows, (void**)&d_rows)) return rc;
-    if (int rc = get_ws(c, "fc:hpart", sizeof(double) * np, (void**)&d_part)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(d_cart, cart.data(), sizeof(double) * cart.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(d_z, charges_host, sizeof(double) * nions, hipMemcpyHostToDevice, st));
+    if (int rc = ion_ion_upload(c, ii, charges_host, nions, "fc:hpart", (size_t)nrows * nions, chunks, kIonHessScalars, st)) return rc;
     HIP_TRY(c, hipMemcpyAsync(d_rows, rows_host, sizeof(int) * nrows, hipMemcpyHostToDevice, st));
-    OFDFT_LAUNCH(c, st, "ion_ion_hessian", ion_ion_hessian_kernel, dim3(chunks, nions, nrows), dim3(kRedThreads), 0, (const double*)d_cart,
-                 (const double*)d_z, nions, g, (const int*)d_rows, d_part);
-    std::vector<double> hp(np);
-    HIP_TRY(c, hipMemcpyAsync(hp.data(), d_part, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipGetLastError());
-    for (int q = 0; q < nrows; ++q) {
-        const int p = rows_host[q];
-        double* row = hess_host + (size_t)q * nions * 9;
+    OFDFT_LAUNCH(c, st, "ion_ion_hessian", ion_ion_hessian_kernel, dim3(chunks, nions, nrows), dim3(kRedThreads), 0, (const double*)ii.d_cart,
+                 (const double*)ii.d_z, nions, ii.g, (const int*)d_rows, ii.d_part);
+    if (int rc = ion_ion_fetch(c, ii, st)) return rc;
+    for (int k = 0; k < nrows; ++k) {
+        const int p = rows_host[k];
+        double* row = hess_host + (size_t)k * nions * 9;
         long double diag[kIonHessScalars] = {0, 0, 0, 0, 0, 0};
         for (int b = 0; b < nions; ++b) {
             double t6[kIonHessScalars];
             for (int s = 0; s < kIonHessScalars; ++s) {
-                long double t = 0.0L;
-                for (int k = 0; k < chunks; ++k) t += hp[(((size_t)q * nions + b) * chunks + k) * kIonHessScalars + s];
+                const long double t = chunk_sum(ii.part.data(), (size_t)k * nions + b, chunks, kIonHessScalars, s);
                 diag[s] += t;                       // (b == p: zeros)
                 t6[s] = -(double)t;                 // off-diagonal block: -sum over shifts of T
             }

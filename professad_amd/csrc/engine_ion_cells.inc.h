@@ -1,5 +1,5 @@
 // C ABI of the cell-list ion-ion sum (ion_cells.h).  Included once by engine.hip inside its extern "C" block, after
-// engine_ions_stress.inc.h (sym_store).
+// engine_ions_stress.inc.h (sym_store, ion_ion_radii).  A first-order entry: it leaves the retained Hessian fields (hvp_valid).
 namespace {
 
 // Smallest |sum_d v_d u_d| over the box v_d in [o_d - 1, o_d + 1]: the distance between the closest points of two cells whose
@@ -66,21 +66,8 @@ int ofdft_ion_ion_cells(ofdft_ctx* c, const double* frac_host, const double* cha
     if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
     OFDFT_ON_DEVICE(c, c->device);
     const double* B = c->box;
-    // interplanar spacings h_d = vol / |cross of the other two lattice vectors| (as ofdft_ion_ion)
     double h[3];
-    for (int d = 0; d < 3; ++d) {
-        const double* u = B + 3 * ((d + 1) % 3);
-        const double* v = B + 3 * ((d + 2) % 3);
-        const double cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
-        h[d] = c->vol / std::sqrt(cx * cx + cy * cy + cz * cz);
-    }
-    const double h_max = std::max(h[0], std::max(h[1], h[2]));
-    if (Rc <= 0.0) {
-        Rd = 2.0 * h_max;
-        Rc = 3.0 * Rd * Rd / h_max;
-    } else if (Rd <= 0.0) {
-        Rd = std::sqrt(h_max * Rc / 3.0);
-    }
+    ion_ion_radii(c, h, Rc, Rd);
     // Cells per axis: roughly cubic cells of kIonCellOccupancy ions on average, m_d = round(h_d / edge) with
     // edge = cbrt(occupancy vol / nions), at least one.  32 ions per cell keep a tile of target ions (below) mostly full while
     // the cells stay small against Rc, so the cells kept by the distance test hug the cutoff sphere; a cell with few ions

@@ -1,17 +1,24 @@
 // C ABI of the routines around the hot path: ionic potential, ion-electron forces, per-term stress, ion-electron stress and
 // the ion-ion sum.  Included once by engine.hip inside its extern "C" block (one
 // translation unit: the kernels in the headers are not inline); uses the engine's context, workspaces and FFT drivers.
+// Also the frames every per-geometry-step entry is written in.  Of the fields ofdft_hessian_vector retains for
+// reuse_density = 1 (hvp_valid): ofdft_stress clears them (begin_call); the first-order ion entries of this file leave them,
+// which is sound, because no entry here writes an "hv:*" workspace.
 // ------------------------------------------------------------------------------ ionic potential
+// One ion-electron entry in flight.  The entry owns it for the whole call: the device scope covers every workspace, launch and
+// copy (ion_begin reports its error), and the host staging lives until ion_finish has synchronised.
 struct IonPrep {
+    DeviceScope dev;
     std::vector<double> frac, cart, slopes;
     std::vector<cplx> hb;
     double *d_frac = nullptr, *d_cart = nullptr;
     cplx *d_b0 = nullptr, *d_b1 = nullptr, *d_b2 = nullptr;
     RecpotTable tab{};
+    explicit IonPrep(const ofdft_ctx* c) : dev(c->device) {}
 };
 
 // shared host-side preparation of the ionic-potential entry points: wrapped fractional coordinates, Cartesian
-// coordinates, Hermite slopes, PME b factors; uploads everything on `st` (caller syncs before `p` dies)
+// coordinates, Hermite slopes, PME b factors; uploads everything on `st`, on the device `p` selected
 static int ion_prepare(ofdft_ctx* c, IonPrep& p, const double* frac_host, int nions, const double* tab_k,
                        const double* tab_v, int ntab, double z_ion, int pme_order, hipStream_t st) {
     if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
@@ -20,7 +27,6 @@ static int ion_prepare(ofdft_ctx* c, IonPrep& p, const double* frac_host, int ni
     if (nions < 1 || ntab < 2) return fail(c, OFDFT_EINVAL, "need at least one ion and two table points");
     if (pme_order != 0 && (pme_order < 2 || pme_order > kMaxPmeOrder || (pme_order & 1)))
         return fail(c, OFDFT_EINVAL, "Requires even order n >= 2 (<= %d)", kMaxPmeOrder);       // ion_utils.py:116
-    OFDFT_ON_DEVICE(c, c->device);
     p.frac.resize(3 * (size_t)nions);
     p.cart.resize(3 * (size_t)nions);
     for (int a = 0; a < nions; ++a) {
@@ -89,12 +95,70 @@ static int ion_prepare(ofdft_ctx* c, IonPrep& p, const double* frac_host, int ni
     return 0;
 }
 
+// ---- the frame of the seven ion-electron entries: IonPrep p(c), ion_begin, the entry's body, ion_finish
+// the refusals the second-order entries share, before any device work; `who` names the entry in the messages
+static int fc_checks(ofdft_ctx* c, int pme_order, const char* who) {
+    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no force constants", who);
+    if (pme_order != 0)
+        return fail(c, OFDFT_EINVAL, "%s: particle-mesh Ewald (PME, pme_order = %d) is not served: the derivative of the B-spline spread "
+                    "is not built; pass pme_order = 0 (exact structure factor)", who, pme_order);
+    return 0;
+}
+
+// The refusals in the order the entries have always had, then ion_prepare.  A second-order entry clears the retained Hessian
+// fields and refuses slab contexts and PME before anything else (so a slab context hears "single-GPU" before "ofdft_set_cell").
+// one_ion: the entry works on this ion alone, refused when outside [0, nions).
+static int ion_begin(ofdft_ctx* c, IonPrep& p, const char* who, bool second_order, const double* frac_host, int nions, const double* tab_k,
+                     const double* tab_v, int ntab, double z_ion, int pme_order, hipStream_t st, const int* one_ion = nullptr) {
+    if (second_order) {
+        c->hvp_valid = false;
+        if (int rc = fc_checks(c, pme_order, who)) return rc;
+    }
+    if (p.dev.err != hipSuccess) return fail(c, OFDFT_EHIP, "cannot select device %d: %s", c->device, hipGetErrorString(p.dev.err));
+    if (one_ion && (*one_ion < 0 || *one_ion >= nions)) return fail(c, OFDFT_EINVAL, "%s: ion_index %d outside [0, %d)", who, *one_ion, nions);
+    return ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st);
+}
+
+static int ion_finish(ofdft_ctx* c, hipStream_t st) {
+    HIP_TRY(c, hipStreamSynchronize(st));      // `p` (host staging) must outlive the async copies
+    HIP_TRY(c, hipGetLastError());
+    if (c->profiling) prof_collect(c);
+    return OFDFT_OK;
+}
+
+// ---- sums every per-geometry-step entry forms the same way
+// sum over the chunks of scalar s of row `row` of the partials part[rows][chunks][ns]: fixed order, long double
+static long double chunk_sum(const double* part, size_t row, int chunks, int ns, int s) {
+    long double t = 0.0L;
+    for (int b = 0; b < chunks; ++b) t += part[(row * chunks + b) * ns + s];
+    return t;
+}
+
+// the `ns` sums of a moment kernel's `blocks` rows in c->d_partial, over the blocks and (slab contexts) over the ranks; one
+// GPU: global_sums returns at once, so the single-GPU entries call this too
+static int moment_sums(ofdft_ctx* c, int blocks, int ns, double* sums, hipStream_t st) {
+    if (int rc = fetch_partials(c, blocks, ns, sums, st)) return rc;
+    return global_sums(c, sums, ns);
+}
+
+// spec = F[n^e] (op = MAP_POW) or F[sqrt n] (MAP_SQRT: the reference's sqrt(0) = 0; e unused) through the scratch field "t0"
+static int density_power_spectrum(ofdft_ctx* c, const double* den, int op, double e, cplx* spec, hipStream_t st) {
+    const int grid = grid_for(c->npts / 2 + 1);
+    double* tmp;
+    if (int rc = real_ws(c, "t0", &tmp)) return rc;
+    if (op == MAP_SQRT)
+        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_SQRT>), dim3(grid), dim3(256), 0, den, tmp, c->npts, 0.0);
+    else
+        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(grid), dim3(256), 0, den, tmp, c->npts, e);
+    return rfftn_internal(c, tmp, spec, st);
+}
+
 int ofdft_ionic_potential(ofdft_ctx* c, const double* frac_host, int nions, const double* tab_k, const double* tab_v,
                           int ntab, double z_ion, int pme_order, void* vext_dev, int accumulate, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !tab_k || !tab_v || !vext_dev) return OFDFT_EINVAL;
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ionic_potential", false, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
     cplx *sQ, *sF;
     double* tmp;
     if (int rc = spec_ws(c, "i:F", &sF)) return rc;
@@ -117,10 +181,7 @@ int ofdft_ionic_potential(ofdft_ctx* c, const double* frac_host, int nions, cons
     if (int rc = irfftn_internal(c, sF, tmp, 1.0, st)) return rc;              // norm='forward': no 1/N  (ion_utils.py:118)
     OFDFT_LAUNCH(c, st, "axpy", (axpy_kernel<double>), dim3(grid_for(c->npts)), dim3(256), 0, (const double*)tmp, (double*)vext_dev,
                  c->npts, accumulate);
-    HIP_TRY(c, hipStreamSynchronize(st));      // `p` (host staging) must outlive the async copies
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
 // F_a = -dU/dR_a, U = int n v_ext for one species (the ion-electron part of System.forces, system.py:913-923)
@@ -129,8 +190,8 @@ int ofdft_ion_electron_forces(ofdft_ctx* c, const void* den_dev, const double* f
                               void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !den_dev || !frac_host || !tab_k || !tab_v || !forces_host) return OFDFT_EINVAL;
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ion_electron_forces", false, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
     cplx *sN, *sT;
     if (int rc = spec_ws(c, "i:Q", &sN)) return rc;
     if (int rc = rfftn_internal(c, (const double*)den_dev, sN, st)) return rc;
@@ -145,11 +206,7 @@ int ofdft_ion_electron_forces(ofdft_ctx* c, const void* den_dev, const double* f
         HIP_TRY(c, hipMemcpyAsync(h.data(), d_part, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (int a = 0; a < nions; ++a)
-            for (int s3 = 0; s3 < 3; ++s3) {
-                long double t = 0.0L;
-                for (int b = 0; b < kb; ++b) t += h[((size_t)a * kb + b) * 3 + s3];
-                forces_host[3 * a + s3] = pref * (double)t;
-            }
+            for (int s3 = 0; s3 < 3; ++s3) forces_host[3 * a + s3] = pref * (double)chunk_sum(h.data(), a, kb, 3, s3);
         if (int rc = global_sums(c, forces_host, 3 * nions)) return rc;      // each rank summed its own k-points
     } else {
         double *theta, *d_G;
@@ -187,9 +244,7 @@ int ofdft_ion_electron_forces(ofdft_ctx* c, const void* den_dev, const double* f
                 forces_host[3 * a + j] = -c->dV * t;
             }
     }
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
 // ------------------------------------------------------------------------------ stress
@@ -244,8 +299,7 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         if (mask & OFDFT_HARTREE) {
             OFDFT_LAUNCH(c, st, "stress_spec", (stress_spec_kernel<STRESS_HARTREE>), dim3(sp_blocks), dim3(kRedThreads), 0,
                          (const cplx*)s0, (const cplx*)nullptr, c->kg, invN2, 0.0, c->d_partial);
-            if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
-            if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
+            if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
             sym_store(sig + 9 * 1, s7, -0.5 * s7[6]);                 // -E_H / vol on the diagonal
         }
         if (mask & kGgaAny) {
@@ -273,10 +327,9 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
                      (const double*)gy, (const double*)gz, npts, mask, gga_sel(c),
                      ts.tc.gtf_inv_n0, ts.tc.gtf_kind,
                      c->d_partial, lapn);
-        if (int rc = fetch_partials(c, blocks, kStressRealScalars, r, st)) return rc;
-        if (int rc = global_sums(c, r, kStressRealScalars)) return rc;
+        if (int rc = moment_sums(c, blocks, kStressRealScalars, r, st)) return rc;
         const double zero6[6] = {0, 0, 0, 0, 0, 0};
-        const double ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
+        const double ctf = ctf_host();
         if (mask & OFDFT_TF) sym_store(sig + 9 * 2, zero6, -2.0 / 3.0 * ctf * r[0] * invN);      // tools_for_tests.py:241-243
         if (mask & OFDFT_VWGTF) sym_store(sig + 9 * 13, zero6, -2.0 / 3.0 * r[27] * invN);      // E ~ J^(-2/3) at fixed n / n0
         if (mask & OFDFT_LDA_X) sym_store(sig + 9 * 6, zero6, r[1] * invN);                    // :367-370
@@ -296,8 +349,7 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
             if (int rc = rfftn_internal(c, lapn, s1, st)) return rc;          // lapn now holds f_l = df/d(lap n)
             OFDFT_LAUNCH(c, st, "stress_spec", (stress_spec_kernel<STRESS_HESS>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0,
                          (const cplx*)s1, c->kg, invN2, 0.0, c->d_partial);
-            if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
-            if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
+            if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
             double* o = sig + 9 * 12;
             o[0] += 2.0 * s7[0]; o[4] += 2.0 * s7[1]; o[8] += 2.0 * s7[2];
             o[1] += 2.0 * s7[3]; o[3] += 2.0 * s7[3];
@@ -306,35 +358,25 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         }
     }
     if (mask & OFDFT_VW) {
-        double* tmp;
-        if (int rc = real_ws(c, "t0", &tmp)) return rc;
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_SQRT>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, 0.0);
-        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        if (int rc = density_power_spectrum(c, den, MAP_SQRT, 0.0, s0, st)) return rc;
         OFDFT_LAUNCH(c, st, "stress_spec", (stress_spec_kernel<STRESS_VW>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0,
                      (const cplx*)nullptr, c->kg, invN2, 0.0, c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
-        if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
+        if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
         sym_store(sig + 9 * 3, s7, 0.0);
     }
-    if (mask & OFDFT_WT_NL) {
+    if (mask & OFDFT_WT_NL) {        // n^beta first, n^alpha second
         const double al = ts.nlp.al, be = ts.nlp.be;
-        const double kf = std::cbrt(3.0 * kPi * kPi * nbar);
-        const double ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
-        const double pref = ctf * 5.0 / (9.0 * al * be * std::pow(nbar, al + be - 5.0 / 3.0));
-        double* tmp;
-        if (int rc = real_ws(c, "t0", &tmp)) return rc;
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, be);
-        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        const WtMoment wt = wt_moment(ts, nbar);
+        const double pref = wt.pref_ctf;
+        if (int rc = density_power_spectrum(c, den, MAP_POW, be, s0, st)) return rc;
         cplx* sa = s0;
         if (al != be) {
-            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, al);
-            if (int rc = rfftn_internal(c, tmp, s1, st)) return rc;
+            if (int rc = density_power_spectrum(c, den, MAP_POW, al, s1, st)) return rc;
             sa = s1;
         }
         OFDFT_LAUNCH(c, st, "stress_spec", (stress_spec_kernel<STRESS_WT>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)sa,
-                     (const cplx*)s0, c->kg, invN2, 1.0 / (2.0 * kf), c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
-        if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
+                     (const cplx*)s0, c->kg, invN2, wt.inv2kf, c->d_partial);
+        if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
         double c6[6];
         for (int k = 0; k < 6; ++k) c6[k] = pref * s7[k];
         sym_store(sig + 9 * 4, c6, -2.0 / 3.0 * pref * s7[6]);                                  // -2/3 T_NL / vol
@@ -342,7 +384,7 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
     if (mask & OFDFT_NLK) {          // KGAP / XWM (stress_kernels.h: stress_nlk_kernel); n0 = round(N_e) / vol
         const NlPow& nlp = ts.nlp;
         const double n0 = ts.n0_r, x0 = c->params[OFDFT_P_NLK_P0];
-        const double kf = std::cbrt(3.0 * kPi * kPi * n0), ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
+        const double kf = std::cbrt(3.0 * kPi * kPi * n0), ctf = ctf_host();
         NlkStress t{};
         t.kind = nlp.kind;
         t.inv2kf = 1.0 / (2.0 * kf);
@@ -356,19 +398,15 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
             t.c1 = -n0 / (nlp.al * nlp.al) * k1;
             t.c2 = k1 / (nlp.al * nlp.be);
         }
-        double* tmp;
-        if (int rc = real_ws(c, "t0", &tmp)) return rc;
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.al);
-        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        if (int rc = density_power_spectrum(c, den, MAP_POW, nlp.al, s0, st)) return rc;      // n^alpha first, n^beta second
         cplx* sb = s0;
         if (nlp.two) {
-            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, npts, nlp.be);
-            if (int rc = rfftn_internal(c, tmp, s1, st)) return rc;
+            if (int rc = density_power_spectrum(c, den, MAP_POW, nlp.be, s1, st)) return rc;
             sb = s1;
         }
         OFDFT_LAUNCH(c, st, "stress_spec", stress_nlk_kernel, dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0, (const cplx*)sb,
                      c->kg, invN2, t, c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
+        if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;      // (single-GPU contexts only: set_terms)
         sym_store(sig + 9 * 14, s7, -2.0 / 3.0 * s7[6]);                                         // -2/3 T_NL / vol
     }
     if (wts_active(c)) {      // T = T_TF f(X): sigma = sigma_TF (f - f' X) + sigma_NL f'(X) / f'(0)   (tools_for_tests.py:310-364), f = exp
@@ -407,9 +445,8 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         }
         OFDFT_LAUNCH(c, st, "stress_wgc", stress_wgc_kernel, dim3(sp_blocks), dim3(kRedThreads), 0, sp, c->kg, ser, invN2,
                      c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
-        if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
-        const double ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
+        if (int rc = moment_sums(c, sp_blocks, kStressSpecScalars, s7, st)) return rc;
+        const double ctf = ctf_host();
         double c6[6];
         for (int k = 0; k < 6; ++k) c6[k] = ctf * s7[k];
         sym_store(sig + 9 * 5, c6, -2.0 / 3.0 * ctf * s7[6]);
@@ -423,8 +460,8 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void* den_dev, const double* f
                               const double* tab_v, int ntab, double z_ion, int pme_order, double* sigma_host, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !den_dev || !frac_host || !tab_k || !tab_v || !sigma_host) return OFDFT_EINVAL;
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ion_electron_stress", false, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st)) return rc;
     cplx *sN, *sQ = nullptr;
     if (int rc = spec_ws(c, "i:F", &sN)) return rc;
     if (int rc = rfftn_internal(c, (const double*)den_dev, sN, st)) return rc;
@@ -442,24 +479,19 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void* den_dev, const double* f
                  c->kg, (const cplx*)p.d_b0, (const cplx*)p.d_b1, (const cplx*)p.d_b2,
                  pme_order == 0 ? (const double*)p.d_cart : (const double*)nullptr, nions, p.tab, c->d_partial);
     double s7[kStressSpecScalars];
-    if (int rc = fetch_partials(c, blocks, kStressSpecScalars, s7, st)) return rc;
-    if (int rc = global_sums(c, s7, kStressSpecScalars)) return rc;
+    if (int rc = moment_sums(c, blocks, kStressSpecScalars, s7, st)) return rc;
     const double invN = 1.0 / (double)c->npts_g;
     double c6[6];
     for (int k = 0; k < 6; ++k) c6[k] = -s7[k] * invN / c->vol;
     sym_store(sigma_host, c6, -s7[6] * invN / c->vol);
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
-// Parameters and geometry of the direct pair scan, shared by ofdft_ion_ion and ofdft_ion_ion_hessian: Rd / Rc of
-// System.__ion_ion_interaction (system.py:744-750; Rc <= 0 selects its default), Cartesian coordinates, and the box of lattice
-// shifts that holds every pair within Rc.  Returns the number of shifts.
-static long long ion_ion_setup(ofdft_ctx* c, const double* frac_host, int nions, double Rc, IonIonGeom& g, std::vector<double>& cart) {
+// Interplanar spacings h_d = 1 / |row d of inv(B^T)| = vol / |cross of the other two lattice vectors| and the radii of
+// System.__ion_ion_interaction (system.py:744-750), for the direct scan and the cell list alike: Rc <= 0 selects the reference's
+// default (Rd = 2 h_max, Rc = 3 Rd^2 / h_max); Rc > 0 with Rd <= 0: Rd = sqrt(h_max Rc / 3); both > 0: as given
+static void ion_ion_radii(const ofdft_ctx* c, double h[3], double& Rc, double& Rd) {
     const double* B = c->box;
-    // interplanar spacings h_d = 1 / |row d of inv(B^T)| = vol / |cross of the other two lattice vectors|
-    double h[3];
     for (int d = 0; d < 3; ++d) {
         const double* u = B + 3 * ((d + 1) % 3);
         const double* v = B + 3 * ((d + 2) % 3);
@@ -467,13 +499,21 @@ static long long ion_ion_setup(ofdft_ctx* c, const double* frac_host, int nions,
         h[d] = c->vol / std::sqrt(cx * cx + cy * cy + cz * cz);
     }
     const double h_max = std::max(h[0], std::max(h[1], h[2]));
-    double Rd;
     if (Rc <= 0.0) {
         Rd = 2.0 * h_max;
         Rc = 3.0 * Rd * Rd / h_max;
-    } else {
+    } else if (Rd <= 0.0) {
         Rd = std::sqrt(h_max * Rc / 3.0);
     }
+}
+
+// Parameters and geometry of the direct pair scan, shared by ofdft_ion_ion and ofdft_ion_ion_hessian: Rd / Rc of
+// System.__ion_ion_interaction (system.py:744-750; Rc <= 0 selects its default), Cartesian coordinates, and the box of lattice
+// shifts that holds every pair within Rc.  Returns the number of shifts.
+static long long ion_ion_setup(ofdft_ctx* c, const double* frac_host, int nions, double Rc, IonIonGeom& g, std::vector<double>& cart) {
+    const double* B = c->box;
+    double h[3], Rd = 0.0;
+    ion_ion_radii(c, h, Rc, Rd);
     std::memcpy(g.box, B, sizeof(g.box));
     g.Rc = Rc;
     g.Rd = Rd;
@@ -493,6 +533,54 @@ static long long ion_ion_setup(ofdft_ctx* c, const double* frac_host, int nions,
     return nshift;
 }
 
+// ---- the frame of the three direct ion-ion entries: ion_ion_begin, the entry's own refusals, ion_ion_upload,
+// the entry's launch over (chunks, ...), ion_ion_fetch, then chunk_sum over ii.part
+struct IonIonCall {
+    IonIonGeom g{};
+    long long nshift = 0;
+    std::vector<double> cart, part;      // Cartesian coordinates; the partials [rows][chunks][ns] as ion_ion_fetch leaves them
+    double *d_cart = nullptr, *d_z = nullptr, *d_part = nullptr;
+};
+// what needs no device: the "ofdft_set_cell" refusal, which every entry raises before its own, and the geometry
+static int ion_ion_begin(ofdft_ctx* c, IonIonCall& ii, const double* frac_host, int nions, double Rc) {
+    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    ii.nshift = ion_ion_setup(c, frac_host, nions, Rc, ii.g, ii.cart);
+    return 0;
+}
+// Chunks (grid.x) of a scan over `work` items.  The entries differ in `work` (nshift * nions, or nshift for the Hessian), and
+// the launch geometry sets the summation order and with it the bits: the count is the entry's to pass on.
+static int ion_ion_chunks(long long work) { return (int)std::min<long long>(256, (work + kRedThreads * 8 - 1) / (kRedThreads * 8)); }
+// "ii:cart" / "ii:z" uploaded on `st`; the partials workspace `part_name` of rows x chunks x ns doubles
+static int ion_ion_upload(ofdft_ctx* c, IonIonCall& ii, const double* charges_host, int nions, const char* part_name, size_t rows, int chunks,
+                          int ns, hipStream_t st) {
+    ii.part.resize(rows * chunks * ns);
+    if (int rc = get_ws(c, "ii:cart", sizeof(double) * ii.cart.size(), (void**)&ii.d_cart)) return rc;
+    if (int rc = get_ws(c, "ii:z", sizeof(double) * nions, (void**)&ii.d_z)) return rc;
+    if (int rc = get_ws(c, part_name, sizeof(double) * ii.part.size(), (void**)&ii.d_part)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(ii.d_cart, ii.cart.data(), sizeof(double) * ii.cart.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(ii.d_z, charges_host, sizeof(double) * nions, hipMemcpyHostToDevice, st));
+    return 0;
+}
+static int ion_ion_fetch(ofdft_ctx* c, IonIonCall& ii, hipStream_t st) {
+    HIP_TRY(c, hipMemcpyAsync(ii.part.data(), ii.d_part, sizeof(double) * ii.part.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// The background term of one ion, as ofdft_ion_ion and ofdft_ion_ion_strain_hessian both form it: R_a from the charge Q within
+// Rc and the mean charge density rho, erf, exp, and h(R_a) = e_a / rho
+struct IonBackground { double Ra, er, ex, h; };
+static IonBackground ion_background(double Z, double Q, double rho, double Rd) {
+    const double spi = std::sqrt(kPi);
+    IonBackground b;
+    b.Ra = std::cbrt(0.75 / kPi * Q / rho);
+    b.ex = std::exp(-b.Ra * b.Ra / (Rd * Rd));
+    b.er = std::erf(b.Ra / Rd);
+    b.h = -kPi * Z * b.Ra * b.Ra + kPi * Z * (b.Ra * b.Ra - 0.5 * Rd * Rd) * b.er + spi * Z * b.Ra * Rd * b.ex;
+    return b;
+}
+
 // Ion-ion interaction energy, forces and stress (ion_utils.py:293-333 with the parameter heuristics of
 // System.__ion_ion_interaction, system.py:733-754; forces / stress = what autograd yields, system.py:913-935).
 // Rc <= 0 selects the reference's default (Rd = 2 h_max, Rc = 3 Rd^2 / h_max); forces_host [nions][3] and
@@ -501,48 +589,32 @@ int ofdft_ion_ion(ofdft_ctx* c, const double* frac_host, const double* charges_h
                   double* forces_host, double* stress_host, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !charges_host || !E_host || nions < 1) return OFDFT_EINVAL;
-    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    IonIonCall ii;
+    if (int rc = ion_ion_begin(c, ii, frac_host, nions, Rc)) return rc;
     OFDFT_ON_DEVICE(c, c->device);
-    IonIonGeom g{};
-    std::vector<double> cart;
-    const long long nshift = ion_ion_setup(c, frac_host, nions, Rc, g, cart);
-    const double Rd = g.Rd;
-    const long long total = nshift * nions;
-    const int chunks = (int)std::min<long long>(256, (total + kRedThreads * 8 - 1) / (kRedThreads * 8));
-    double *d_cart, *d_z, *d_part;
-    const size_t np = (size_t)nions * chunks * kIonIonScalars;
-    if (int rc = get_ws(c, "ii:cart", sizeof(double) * cart.size(), (void**)&d_cart)) return rc;
-    if (int rc = get_ws(c, "ii:z", sizeof(double) * nions, (void**)&d_z)) return rc;
-    if (int rc = get_ws(c, "ii:part", sizeof(double) * np, (void**)&d_part)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(d_cart, cart.data(), sizeof(double) * cart.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(d_z, charges_host, sizeof(double) * nions, hipMemcpyHostToDevice, st));
-    OFDFT_LAUNCH(c, st, "ion_ion", ion_ion_kernel, dim3(chunks, nions), dim3(kRedThreads), 0, (const double*)d_cart,
-                 (const double*)d_z, nions, g, d_part);
-    std::vector<double> hp(np);
-    HIP_TRY(c, hipMemcpyAsync(hp.data(), d_part, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipGetLastError());
+    const double Rd = ii.g.Rd;
+    const int chunks = ion_ion_chunks(ii.nshift * nions);
+    if (int rc = ion_ion_upload(c, ii, charges_host, nions, "ii:part", nions, chunks, kIonIonScalars, st)) return rc;
+    OFDFT_LAUNCH(c, st, "ion_ion", ion_ion_kernel, dim3(chunks, nions), dim3(kRedThreads), 0, (const double*)ii.d_cart,
+                 (const double*)ii.d_z, nions, ii.g, ii.d_part);
+    if (int rc = ion_ion_fetch(c, ii, st)) return rc;
     double ztot = 0.0;
     for (int a = 0; a < nions; ++a) ztot += charges_host[a];
     const double rho = ztot / c->vol, spi = std::sqrt(kPi);
     long double E = 0.0L, sig6[6] = {0, 0, 0, 0, 0, 0}, corr = 0.0L;
     for (int a = 0; a < nions; ++a) {
         long double s[kIonIonScalars];
-        for (int k = 0; k < kIonIonScalars; ++k) {
-            s[k] = 0.0L;
-            for (int b = 0; b < chunks; ++b) s[k] += hp[((size_t)a * chunks + b) * kIonIonScalars + k];
-        }
+        for (int k = 0; k < kIonIonScalars; ++k) s[k] = chunk_sum(ii.part.data(), a, chunks, kIonIonScalars, k);
         const double Z = charges_host[a];
-        const double Q = Z + (double)s[1];
-        const double aux = 0.75 / kPi * Q / rho;
-        const double Ra = std::cbrt(aux);
-        const double ex = std::exp(-Ra * Ra / (Rd * Rd)), er = std::erf(Ra / Rd);
+        const IonBackground bg = ion_background(Z, Z + (double)s[1], rho, Rd);
+        const double Ra = bg.Ra, ex = bg.ex, er = bg.er;
+        // (the energy and dE_dRa multiply rho inside each term: rho h(R_a) and rho h'(R_a) round differently, so they stay)
         E += 0.5L * s[0] - kPi * Z * rho * Ra * Ra + kPi * Z * rho * (Ra * Ra - 0.5 * Rd * Rd) * er + spi * Z * rho * Ra * Rd * ex -
              Z * Z / spi / Rd;
         if (forces_host)
             for (int d = 0; d < 3; ++d) forces_host[3 * a + d] = (double)s[2 + d];
         for (int k = 0; k < 6; ++k) sig6[k] += 0.5L * s[5 + k];
-        const double e_rho = -kPi * Z * Ra * Ra + kPi * Z * (Ra * Ra - 0.5 * Rd * Rd) * er + spi * Z * Ra * Rd * ex;
+        const double e_rho = bg.h;
         const double dE_dRa = -2.0 * kPi * Z * rho * Ra + 2.0 * kPi * Z * rho * Ra * er +
                               kPi * Z * rho * (Ra * Ra - 0.5 * Rd * Rd) * 2.0 / (spi * Rd) * ex +
                               spi * Z * rho * Rd * ex * (1.0 - 2.0 * Ra * Ra / (Rd * Rd));

@@ -1,7 +1,10 @@
 // C ABI of the second strain derivative at fixed chi (strain2_kernels.h): the reciprocal-space terms of the
 // functional, the ion-electron term and the ion-ion sum.  Included once by engine.hip inside its extern "C" block (fp64 library),
-// after engine_force_constants.inc.h (fc_checks) and engine_hvp.inc.h (hvp_refusal).  Single GPU, exact structure factor; each
-// entry clears hvp_valid.  Tensors are [3][3][3][3] row-major in (m, n, p, q) = d2 E / d eps_mn d eps_pq, Ha.
+// after engine_ions_stress.inc.h (the frames of the ion entries, moment_sums, density_power_spectrum) and engine_hvp.inc.h
+// (hvp_checks).  Single GPU, exact structure factor.  Each entry clears hvp_valid, the fields ofdft_hessian_vector retains for
+// reuse_density = 1: the two functional entries through begin_call, the three ion entries by the second-order convention (they
+// write no "hv:*" workspace; DESIGN.md §9f has the table).  Tensors are [3][3][3][3] row-major in (m, n, p, q) =
+// d2 E / d eps_mn d eps_pq, Ha.
 namespace {
 
 const int kK2Index[3][3] = {{0, 3, 4}, {3, 1, 5}, {4, 5, 2}};
@@ -70,13 +73,13 @@ int ofdft_potential_strain_gradient(ofdft_ctx* c, const void* den_dev, void* out
         double nsum;
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
         const TermScalars ts = term_scalars(c, nsum * c->dV);
-        const double nbar = nsum * invN;
+        const WtMoment wt = wt_moment(ts, nsum * invN);
         ca.al = ts.nlp.al;
         ca.be = ts.nlp.be;
         if (ca.al != ca.be) flags |= SG_WT2;
-        sa.pref = 5.0 / (9.0 * ca.al * ca.be * std::pow(nbar, ca.al + ca.be - 5.0 / 3.0));
-        sa.inv2kf = 1.0 / (2.0 * std::cbrt(3.0 * kPi * kPi * nbar));
-        sa.q = ca.al + ca.be - 5.0 / 3.0;
+        sa.pref = wt.pref;
+        sa.inv2kf = wt.inv2kf;
+        sa.q = wt.q;
     }
     sa.flags = ca.flags = flags;
     static const char* const in_names[kStrainGradFamilies] = {"sg:i0", "sg:i1", "sg:i2", "sg:i3"};
@@ -124,11 +127,9 @@ int ofdft_ionic_potential_strain_gradient(ofdft_ctx* c, const double* frac_host,
                                           int ntab, double z_ion, int pme_order, void* out6_dev, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !tab_k || !tab_v || !out6_dev) return OFDFT_EINVAL;
-    c->hvp_valid = false;
-    if (int rc = fc_checks(c, pme_order, "ofdft_ionic_potential_strain_gradient")) return rc;
-    OFDFT_ON_DEVICE(c, c->device);
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, 0, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ionic_potential_strain_gradient", true, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st))
+        return rc;
     IonStrainGradOut so{};
     cplx* spec[6];
     real* out[6];
@@ -143,10 +144,7 @@ int ofdft_ionic_potential_strain_gradient(ofdft_ctx* c, const double* frac_host,
                  (const double*)p.d_cart, nions, p.tab, 1.0 / c->vol);
     for (int b0 = 0; b0 < 6; b0 += kBsBatch)
         if (int rc = irfftn_internal_multi(c, spec + b0, out + b0, std::min(kBsBatch, 6 - b0), 1.0, st)) return rc;      // norm='forward'
-    HIP_TRY(c, hipStreamSynchronize(st));      // `p` (host staging) must outlive the async copies
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
 // W2^0 of the reciprocal-space terms of the active set at the density den (n ~ 1/J under the strain): hartree, vw, wt_nl; every
@@ -163,47 +161,41 @@ int ofdft_strain_hessian(ofdft_ctx* c, const void* den_dev, double* w2, void* st
     const unsigned mask = c->mask;
     const double invN = 1.0 / (double)c->npts, invN2 = invN * invN;
     for (int i = 0; i < OFDFT_NTERMS * 81; ++i) w2[i] = 0.0;
-    const int sp_blocks = grid_for(c->g.total, kRedThreads, kRedBlocks), pw_grid = grid_for(c->npts / 2 + 1);
+    const int sp_blocks = grid_for(c->g.total, kRedThreads, kRedBlocks);
     double s23[kStrain2Scalars];
     cplx *s0 = nullptr, *s1 = nullptr;
-    double* tmp = nullptr;
     if (int rc = spec_ws(c, "s0", &s0)) return rc;
     if (int rc = spec_ws(c, "s1", &s1)) return rc;
-    if (int rc = real_ws(c, "t0", &tmp)) return rc;
     if (mask & OFDFT_HARTREE) {         // E = (vol / 2) sum_k w 4 pi |n~ / N|^2 / (J s)
         if (int rc = rfftn_internal(c, den, s0, st)) return rc;
         OFDFT_LAUNCH(c, st, "strain2_spec", (strain2_spec_kernel<STRAIN2_HARTREE>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0,
                      (const cplx*)nullptr, c->kg, invN2, 0.0, c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
+        if (int rc = moment_sums(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
         strain2_assemble(s23, kC2bSame, 0.5 * c->vol, w2 + 81 * 1);
     }
     if (mask & OFDFT_VW) {              // E = (vol / 2) sum_k w s |F[sqrt n] / N|^2: no J left
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_SQRT>), dim3(pw_grid), dim3(256), 0, den, tmp, c->npts, 0.0);
-        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        if (int rc = density_power_spectrum(c, den, MAP_SQRT, 0.0, s0, st)) return rc;
         OFDFT_LAUNCH(c, st, "strain2_spec", (strain2_spec_kernel<STRAIN2_VW>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)s0,
                      (const cplx*)nullptr, c->kg, invN2, 0.0, c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
+        if (int rc = moment_sums(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
         strain2_assemble(s23, kC2bNone, 0.5 * c->vol, w2 + 81 * 3);
     }
     if (mask & OFDFT_WT_NL) {           // E = vol c_TF pref sum_k w Re(a~ b~*) / N^2 J^(-2/3) F(eta); n0 = N_e / vol as ofdft_stress forms it
         double nsum;
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
         const TermScalars ts = term_scalars(c, nsum * c->dV);
-        const double al = ts.nlp.al, be = ts.nlp.be, nbar = nsum * invN;
-        const double kf = std::cbrt(3.0 * kPi * kPi * nbar), ctf = 0.3 * std::pow(3.0 * kPi * kPi, 2.0 / 3.0);
-        const double pref = ctf * 5.0 / (9.0 * al * be * std::pow(nbar, al + be - 5.0 / 3.0));
-        OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, c->npts, be);
-        if (int rc = rfftn_internal(c, tmp, s0, st)) return rc;
+        const double al = ts.nlp.al, be = ts.nlp.be;
+        const WtMoment wt = wt_moment(ts, nsum * invN);
+        if (int rc = density_power_spectrum(c, den, MAP_POW, be, s0, st)) return rc;      // n^beta first, n^alpha second
         cplx* sa = s0;
         if (al != be) {
-            OFDFT_LAUNCH(c, st, "map", (map_kernel<MAP_POW>), dim3(pw_grid), dim3(256), 0, den, tmp, c->npts, al);
-            if (int rc = rfftn_internal(c, tmp, s1, st)) return rc;
+            if (int rc = density_power_spectrum(c, den, MAP_POW, al, s1, st)) return rc;
             sa = s1;
         }
         OFDFT_LAUNCH(c, st, "strain2_spec", (strain2_spec_kernel<STRAIN2_WT>), dim3(sp_blocks), dim3(kRedThreads), 0, (const cplx*)sa,
-                     (const cplx*)s0, c->kg, invN2, 1.0 / (2.0 * kf), c->d_partial);
-        if (int rc = fetch_partials(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
-        strain2_assemble(s23, kC2bTrace, c->vol * pref, w2 + 81 * 4);
+                     (const cplx*)s0, c->kg, invN2, wt.inv2kf, c->d_partial);
+        if (int rc = moment_sums(c, sp_blocks, kStrain2Scalars, s23, st)) return rc;
+        strain2_assemble(s23, kC2bTrace, c->vol * wt.pref_ctf, w2 + 81 * 4);
     }
     return end_call(c, st);
 }
@@ -214,11 +206,9 @@ int ofdft_ion_electron_strain_hessian(ofdft_ctx* c, const void* den_dev, const d
                                       const double* tab_v, int ntab, double z_ion, int pme_order, double* w2_host, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!c || !den_dev || !frac_host || !tab_k || !tab_v || !w2_host) return OFDFT_EINVAL;
-    c->hvp_valid = false;
-    if (int rc = fc_checks(c, pme_order, "ofdft_ion_electron_strain_hessian")) return rc;
-    OFDFT_ON_DEVICE(c, c->device);
-    IonPrep p;
-    if (int rc = ion_prepare(c, p, frac_host, nions, tab_k, tab_v, ntab, z_ion, 0, st)) return rc;
+    IonPrep p(c);
+    if (int rc = ion_begin(c, p, "ofdft_ion_electron_strain_hessian", true, frac_host, nions, tab_k, tab_v, ntab, z_ion, pme_order, st))
+        return rc;
     cplx* sN;
     if (int rc = spec_ws(c, "i:F", &sN)) return rc;
     if (int rc = rfftn_internal(c, (const double*)den_dev, sN, st)) return rc;
@@ -226,12 +216,10 @@ int ofdft_ion_electron_strain_hessian(ofdft_ctx* c, const void* den_dev, const d
     OFDFT_LAUNCH(c, st, "strain2_ion", strain2_ion_kernel, dim3(blocks), dim3(kRedThreads), 0, (const cplx*)sN, c->kg,
                  (const double*)p.d_cart, nions, p.tab, c->d_partial);
     double s23[kStrain2Scalars];
-    if (int rc = fetch_partials(c, blocks, kStrain2Scalars, s23, st)) return rc;      // (synchronises: `p` outlives its copies)
+    if (int rc = moment_sums(c, blocks, kStrain2Scalars, s23, st)) return rc;
     for (int i = 0; i < 81; ++i) w2_host[i] = 0.0;
     strain2_assemble(s23, kC2bSame, 1.0 / (double)c->npts, w2_host);
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
+    return ion_finish(c, st);
 }
 
 // W2^0 of the ion-ion energy (ion_utils.py:293-333 with the heuristics of system.py:733-754) at fixed fractional coordinates:
@@ -245,29 +233,17 @@ int ofdft_ion_ion_strain_hessian(ofdft_ctx* c, const double* frac_host, const do
     hipStream_t st = (hipStream_t)stream;
     if (!c || !frac_host || !charges_host || !w2_host || nions < 1) return OFDFT_EINVAL;
     c->hvp_valid = false;
-    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    IonIonCall ii;
+    if (int rc = ion_ion_begin(c, ii, frac_host, nions, Rc)) return rc;
     if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "ofdft_ion_ion_strain_hessian is served by single-GPU contexts");
     if (nions > 65535) return fail(c, OFDFT_EINVAL, "ofdft_ion_ion_strain_hessian: at most 65535 ions (the direct pair scan)");
     OFDFT_ON_DEVICE(c, c->device);
-    IonIonGeom g{};
-    std::vector<double> cart;
-    const long long nshift = ion_ion_setup(c, frac_host, nions, Rc, g, cart);
-    const double Rd = g.Rd;
-    const long long total = nshift * nions;
-    const int chunks = (int)std::min<long long>(256, (total + kRedThreads * 8 - 1) / (kRedThreads * 8));
-    double *d_cart, *d_z, *d_part;
-    const size_t np = (size_t)nions * chunks * kIonStrain2Scalars;
-    if (int rc = get_ws(c, "ii:cart", sizeof(double) * cart.size(), (void**)&d_cart)) return rc;
-    if (int rc = get_ws(c, "ii:z", sizeof(double) * nions, (void**)&d_z)) return rc;
-    if (int rc = get_ws(c, "ii:s2part", sizeof(double) * np, (void**)&d_part)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(d_cart, cart.data(), sizeof(double) * cart.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(d_z, charges_host, sizeof(double) * nions, hipMemcpyHostToDevice, st));
-    OFDFT_LAUNCH(c, st, "ion_ion_strain2", ion_ion_strain2_kernel, dim3(chunks, nions), dim3(kRedThreads), 0, (const double*)d_cart,
-                 (const double*)d_z, nions, g, d_part);
-    std::vector<double> hp(np);
-    HIP_TRY(c, hipMemcpyAsync(hp.data(), d_part, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipGetLastError());
+    const double Rd = ii.g.Rd;
+    const int chunks = ion_ion_chunks(ii.nshift * nions);
+    if (int rc = ion_ion_upload(c, ii, charges_host, nions, "ii:s2part", nions, chunks, kIonStrain2Scalars, st)) return rc;
+    OFDFT_LAUNCH(c, st, "ion_ion_strain2", ion_ion_strain2_kernel, dim3(chunks, nions), dim3(kRedThreads), 0, (const double*)ii.d_cart,
+                 (const double*)ii.d_z, nions, ii.g, ii.d_part);
+    if (int rc = ion_ion_fetch(c, ii, st)) return rc;
     double ztot = 0.0;
     for (int a = 0; a < nions; ++a) ztot += charges_host[a];
     const double rho = ztot / c->vol, spi = std::sqrt(kPi);
@@ -275,15 +251,11 @@ int ofdft_ion_ion_strain_hessian(ofdft_ctx* c, const double* frac_host, const do
     for (int k = 0; k < 21; ++k) m[k] = 0.0L;
     for (int a = 0; a < nions; ++a) {
         long double s[kIonStrain2Scalars];
-        for (int k = 0; k < kIonStrain2Scalars; ++k) {
-            s[k] = 0.0L;
-            for (int b = 0; b < chunks; ++b) s[k] += hp[((size_t)a * chunks + b) * kIonStrain2Scalars + k];
-        }
+        for (int k = 0; k < kIonStrain2Scalars; ++k) s[k] = chunk_sum(ii.part.data(), a, chunks, kIonStrain2Scalars, k);
         for (int k = 0; k < 21; ++k) m[k] += 0.5L * s[k];
-        const double Z = charges_host[a], Q = Z + (double)s[21];
-        const double Ra = std::cbrt(0.75 / kPi * Q / rho);
-        const double ex = std::exp(-Ra * Ra / (Rd * Rd)), er = std::erf(Ra / Rd), erc = std::erfc(Ra / Rd);
-        const double h = -kPi * Z * Ra * Ra + kPi * Z * (Ra * Ra - 0.5 * Rd * Rd) * er + spi * Z * Ra * Rd * ex;
+        const double Z = charges_host[a];
+        const IonBackground bg = ion_background(Z, Z + (double)s[21], rho, Rd);
+        const double Ra = bg.Ra, ex = bg.ex, h = bg.h, erc = std::erfc(Ra / Rd);
         const double h1 = -2.0 * kPi * Z * Ra * erc, h2 = -2.0 * kPi * Z * erc + 4.0 * spi * Z * Ra * ex / Rd;
         EJ += rho * (h1 * Ra / 3.0 - h);
         EJJ += rho * (2.0 * h - 8.0 / 9.0 * h1 * Ra + h2 * Ra * Ra / 9.0);

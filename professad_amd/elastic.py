@@ -15,15 +15,11 @@ where dn_pq is `optimize.density_response` to dv = V_pq (six solves: V is symmet
 the 6 x 6 matrix in its order 11, 22, 33, 23, 13, 12, and K = vol d2E/dvol2 = (sum_ik W2[i, i, k, k] + 6 vol P) / (9 vol) with
 P = -tr(W1) / (3 vol).  Single GPU, fp64, exact structure factor.
 """
-import warnings
-
 import numpy as np
-import torch
 
-from . import _native as N
 from . import ions, optimize
+from .optimize import A_PER_BOHR
 
-A_PER_BOHR = 5.29177210903e-11 * 1e10                       # system.py:27-33 (CODATA 2018)
 GPA_PER_ATOMIC = 4.3597447222071e-18 / 5.29177210903e-11 ** 3 * 1e-9
 VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))    # the reference's order (system.py:1330-1336) and that of the six fields
 
@@ -38,22 +34,9 @@ def unit_factor(units):
     raise ValueError("units must be one of 'Ha/b3', 'eV/a3', 'GPa', not %r" % (units,))
 
 
-class HipElasticBackend:
-    """What `elastic_constants` needs, on the device: the strain entries of professad_amd.ions and Engine, and the conjugate
-    gradients of optimize.HipCgBackend.  Grids are torch tensors of the engine; tensors in the strain are numpy arrays."""
-
-    def __init__(self, engine, box_vecs, species):
-        self.eng, self.box, self.species = engine, box_vecs, species
-        engine.set_cell(box_vecs)
-        self.volume = engine.volume
-        self.dV = engine.volume / engine.npts
-        self.cg = optimize.HipCgBackend(engine)
-
-    def ground_state_gradient(self, chi, n_elec):
-        """max|g| / dV of the closure at chi with v_ext rebuilt from the ions"""
-        vext = ions.ionic_potential(self.eng, self.box, self.species)
-        _E, _mu, g = self.eng.energy_grad_chi(chi, n_elec, vext)
-        return float(g.abs().max()) / self.dV
+class HipElasticBackend(optimize.HipResponseBackend):
+    """What `elastic_constants` needs, on the device: the strain entries of professad_amd.ions and Engine on top of
+    optimize.HipResponseBackend (the conjugate gradients, the ground-state check).  Tensors in the strain are numpy arrays."""
 
     def strain_hessian(self, den):
         """{term: W2^0_t}, the ion_electron entry filled from the ions"""
@@ -75,21 +58,10 @@ class HipElasticBackend:
         V[:3] -= self.eng.hessian_vector(den, den)
         return V
 
-    def close(self):
-        self.cg.close()
-
 
 def refusal(engine, pme_order=None):
     """None, or why `elastic_constants` cannot run on this engine (raised before any device work)"""
-    if pme_order:
-        return ('particle-mesh Ewald (PME, pme_order=%r) is not served: the derivative of the B-spline spread is not built; '
-                'use the exact structure factor' % (pme_order,))
-    why = optimize.second_order_refusal(engine)
-    if why:
-        return why
-    if not engine._mask() & N.TERM_BITS['ion_electron']:
-        return 'the term set has no ion_electron term: nothing couples the density to the ions'
-    return None
+    return optimize.response_refusal(engine, pme_order)
 
 
 def tensor_from_w2(W2, W1, volume):
@@ -131,9 +103,7 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
     NotImplementedError, before any device work and naming the cause: PME, a slab-decomposed engine, an fp32 engine, a term
     without a second derivative.  (`backend`: an object with HipElasticBackend's methods -- the tests' numpy double.)"""
     f = unit_factor(units)
-    species = [(np.asarray(torch.as_tensor(fr).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3), tab) for fr, tab in species]
-    frac = np.concatenate([fr for fr, _t in species], axis=0)
-    charges = np.concatenate([np.full(fr.shape[0], float(tab[2])) for fr, tab in species])
+    species, frac, charges = optimize.normalise_species(species)
     if backend is None:
         why = refusal(engine, pme_order)
         if why:
@@ -149,22 +119,17 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
         ion_ion = b.ion_ion_strain_hessian(frac, charges, Rc)
         sigma = np.asarray(b.stress(n, frac, charges, Rc), dtype=np.float64)
         V = b.potential_strain_gradient(n)
-        log = dict(iterations=[], rel_residual=[], reason=[])
-        hvp_count = 0
+        log = optimize.new_solve_log()
         R6 = np.zeros((6, 6))
         for c in range(6):
             r = optimize.density_response(engine, chi, n_elec, V[c], rtol=rtol, maxiter=maxiter, backend=b.cg)
             for a in range(6):
                 R6[a, c] = float((V[a] * r['dn']).sum()) * b.dV
-            for k in log:
-                log[k].append(r[k])
-            hvp_count += r['hvp_count']
+            optimize.log_solve(log, r)
     finally:
         if backend is None:
             b.close()
-    if any(x != optimize.CG_CONVERGED for x in log['reason']):          # (unpreconditioned: the count grows with the grid)
-        warnings.warn('elastic_constants: %d of 6 response solves did not converge within maxiter=%d (see `reason`, `rel_residual`); '
-                      'the constants are not accurate' % (sum(x != optimize.CG_CONVERGED for x in log['reason']), maxiter))
+    optimize.warn_unconverged('elastic_constants', log, maxiter, 'the constants are not accurate')
     response = np.zeros((3, 3, 3, 3))
     for a, (i, j) in enumerate(VOIGT):
         for c, (k, l) in enumerate(VOIGT):
@@ -175,7 +140,7 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
     C, sym = voigt_matrix(C4)
     K, P = bulk_from_w2(W2, W1, vol)
     return dict(C=C * f, C4=C4 * f, W2=W2, parts=dict(fixed_chi=fixed, ion_ion=ion_ion, response=response), stress=sigma * f,
-                pressure=P * f, bulk_modulus=K * f, symmetry_residual=sym, hvp_count=hvp_count, ground_state_gradient=gsg, **log)
+                pressure=P * f, bulk_modulus=K * f, symmetry_residual=sym, ground_state_gradient=gsg, **log)
 
 
 def bulk_modulus(engine, box_vecs, species, chi, units='Ha/b3', **kwargs):

@@ -11,31 +11,15 @@ ion-electron force entry (linear in the density: it takes dn as it is), D the io
 (`ofdft_ion_electron_curvature`) and Phi_ii the ion-ion Hessian (`ofdft_ion_ion_hessian`).  Phi is symmetric, so the 3 P solves
 for the displaced primitive ions give every requested row.  Single GPU, fp64, exact structure factor.
 """
-import warnings
-
 import numpy as np
-import torch
 
 from . import ions, optimize
+from .optimize import A_PER_BOHR
 
-A_PER_BOHR = 5.29177210903e-11 * 1e10      # system.py:27-28 (CODATA 2018)
 
-
-class HipFcBackend:
-    """What `force_constants` needs, on the device: the pieces from professad_amd.ions and the conjugate gradients of
-    optimize.HipCgBackend.  Grids are torch tensors of the engine; the small per-ion results are numpy arrays."""
-
-    def __init__(self, engine, box_vecs, species):
-        self.eng, self.box, self.species = engine, box_vecs, species
-        engine.set_cell(box_vecs)
-        self.dV = engine.volume / engine.npts
-        self.cg = optimize.HipCgBackend(engine)
-
-    def ground_state_gradient(self, chi, n_elec):
-        """max|g| / dV of the closure at chi with v_ext rebuilt from the ions"""
-        vext = ions.ionic_potential(self.eng, self.box, self.species)
-        _E, _mu, g = self.eng.energy_grad_chi(chi, n_elec, vext)
-        return float(g.abs().max()) / self.dV
+class HipFcBackend(optimize.HipResponseBackend):
+    """What `force_constants` needs, on the device: the pieces from professad_amd.ions on top of optimize.HipResponseBackend
+    (the conjugate gradients, the ground-state check).  The small per-ion results are numpy arrays."""
 
     def potential_gradient(self, ion):
         return ions.ionic_potential_gradient(self.eng, self.box, self.species, ion)
@@ -49,21 +33,10 @@ class HipFcBackend:
     def ion_ion_hessian(self, frac, charges, rows, Rc):
         return ions.ion_ion_hessian(self.eng, self.box, frac, charges, rows, Rc)
 
-    def close(self):
-        self.cg.close()
-
 
 def refusal(engine, pme_order=None):
     """None, or why `force_constants` cannot run on this engine (raised before any device work)"""
-    if pme_order:
-        return ('particle-mesh Ewald (PME, pme_order=%r) is not served: the derivative of the B-spline spread is not built; '
-                'use the exact structure factor' % (pme_order,))
-    why = optimize.second_order_refusal(engine)
-    if why:
-        return why
-    if not engine._mask() & 1:
-        return 'the term set has no ion_electron term: nothing couples the density to the ions'
-    return None
+    return optimize.response_refusal(engine, pme_order)
 
 
 def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b2',
@@ -88,9 +61,7 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
     without a second derivative.  (`backend`: an object with HipFcBackend's methods -- the tests' numpy double.)"""
     if units not in ('Ha/b2', 'eV/a2'):
         raise ValueError("Parameter 'units' can only be 'Ha/b2' or 'eV/a2'")                       # system.py:717
-    species = [(np.asarray(torch.as_tensor(f).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3), tab) for f, tab in species]
-    frac = np.concatenate([f for f, _t in species], axis=0)
-    charges = np.concatenate([np.full(f.shape[0], float(tab[2])) for f, tab in species])
+    species, frac, charges = optimize.normalise_species(species)
     nions = frac.shape[0]
     rows = list(range(nions)) if primitive_ion_indices is None else [int(p) for p in primitive_ion_indices]
     if not rows or min(rows) < 0 or max(rows) >= nions:
@@ -100,30 +71,27 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
         if why:
             raise NotImplementedError('force_constants: ' + why)
     b = backend if backend is not None else HipFcBackend(engine, box_vecs, species)
-    n_elec = float(charges.sum())
-    S = float((chi * chi).sum())
-    n = (n_elec / (S * b.dV)) * chi * chi
-    gsg = b.ground_state_gradient(chi, n_elec)
-    ion_ion = b.ion_ion_hessian(frac, charges, rows, Rc)
-    D = b.ion_electron_curvature(n)
-    direct = np.zeros_like(ion_ion)
-    response = np.zeros_like(ion_ion)
-    log = dict(iterations=[], rel_residual=[], reason=[])
-    hvp_count = 0
-    for q, p in enumerate(rows):
-        direct[q, p] = D[p]
-        dv = b.potential_gradient(p)
-        for i in range(3):
-            r = optimize.density_response(engine, chi, n_elec, dv[i], rtol=rtol, maxiter=maxiter, backend=b.cg)
-            response[q, :, i, :] = -b.ion_electron_forces(r['dn'])
-            for k in log:
-                log[k].append(r[k])
-            hvp_count += r['hvp_count']
-    if backend is None:
-        b.close()
-    if any(x != optimize.CG_CONVERGED for x in log['reason']):          # (unpreconditioned: the count grows with the grid)
-        warnings.warn('force_constants: %d of %d response solves did not converge within maxiter=%d (see `reason`, `rel_residual`); '
-                      'the matrix is not accurate' % (sum(x != optimize.CG_CONVERGED for x in log['reason']), len(log['reason']), maxiter))
+    try:
+        n_elec = float(charges.sum())
+        S = float((chi * chi).sum())
+        n = (n_elec / (S * b.dV)) * chi * chi
+        gsg = b.ground_state_gradient(chi, n_elec)
+        ion_ion = b.ion_ion_hessian(frac, charges, rows, Rc)
+        D = b.ion_electron_curvature(n)
+        direct = np.zeros_like(ion_ion)
+        response = np.zeros_like(ion_ion)
+        log = optimize.new_solve_log()
+        for q, p in enumerate(rows):
+            direct[q, p] = D[p]
+            dv = b.potential_gradient(p)
+            for i in range(3):
+                r = optimize.density_response(engine, chi, n_elec, dv[i], rtol=rtol, maxiter=maxiter, backend=b.cg)
+                response[q, :, i, :] = -b.ion_electron_forces(r['dn'])
+                optimize.log_solve(log, r)
+    finally:
+        if backend is None:
+            b.close()
+    optimize.warn_unconverged('force_constants', log, maxiter, 'the matrix is not accurate')
     parts = dict(ion_ion=ion_ion, direct=direct, response=response)
     phi = ion_ion + direct + response
     row_sum = phi.sum(axis=1)
@@ -135,4 +103,4 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
         f = optimize.EV_PER_HA / A_PER_BOHR ** 2
         phi = phi * f
         parts = {k: v * f for k, v in parts.items()}
-    return dict(phi=phi, parts=parts, hvp_count=hvp_count, asr_residual=asr, ground_state_gradient=gsg, **log)
+    return dict(phi=phi, parts=parts, asr_residual=asr, ground_state_gradient=gsg, **log)

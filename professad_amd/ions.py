@@ -60,67 +60,100 @@ def _f64(engine):
     return engine_for(engine.global_shape, engine.device)
 
 
+# ---------------------------------------------------------------------------------------------------- marshalling
+_DP = C.POINTER(C.c_double)
+
+
+def _arg(x):
+    """an argument of a C entry: tensors and arrays as pointers, everything else as it is"""
+    if torch.is_tensor(x):
+        return C.c_void_p(x.data_ptr())
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data_as(C.POINTER(C.c_int) if x.dtype == np.int32 else _DP)
+    return x
+
+
+def _ion_arrays(frac, charges=None):
+    """frac as a contiguous fp64 [n, 3] array; with `charges`: (frac, z [n]), one charge per ion"""
+    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
+    if charges is None:
+        return frac
+    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
+    if z.size != frac.shape[0]:
+        raise ValueError('one charge per ion')
+    return frac, z
+
+
+def _species_arrays(frac, tab):
+    """(frac [n, 3], ks, v, z) of one species as the C entries take them; the table's shape is checked here, because C reads
+    `ks.size` entries of both `ks` and `v`"""
+    ks, v, z = tab
+    ks = np.ascontiguousarray(ks, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if ks.shape != v.shape or ks.ndim != 1:
+        raise ValueError('table k and v must be 1-D arrays of equal length')
+    return _ion_arrays(frac), ks, v, float(z)
+
+
+def _marshal(species):
+    """every species through `_species_arrays`, before any engine work"""
+    return [_species_arrays(frac, tab) for frac, tab in species]
+
+
+def _pme_refusal(who, pme_order):
+    if pme_order:
+        raise NotImplementedError('%s: particle-mesh Ewald (PME, pme_order=%r) is not served; use the exact structure factor '
+                                  '(pme_order=None)' % (who, pme_order))
+
+
+def _species_call(engine, entry, lead, sp, pme_order, tail):
+    """one call of a per-species entry: (ctx, *lead, frac, n, ks, v, ntab, z, pme_order, *tail, stream), sp from `_species_arrays`"""
+    frac, ks, v, z = sp
+    rc = getattr(engine.lib, entry)(engine._ctx, *map(_arg, lead), _arg(frac), frac.shape[0], _arg(ks), _arg(v), ks.size, z,
+                                    0 if pme_order is None else int(pme_order), *map(_arg, tail), engine._stream())
+    engine._check(rc, entry)
+
+
+def _species_loop(engine, entry, lead, marshalled, new_out, pme_order=None):
+    """`entry` once per species, its output in the buffer new_out(frac) (array or tensor); yields (frac, buffer) after each call"""
+    for sp in marshalled:
+        out = new_out(sp[0])
+        _species_call(engine, entry, lead, sp, pme_order, (out,))
+        yield sp[0], out
+
+
 def ionic_potential(engine, box_vecs, species, pme_order=None):
     """v_ext on the engine's grid.  species: iterable of (frac_coords [n,3], (ks, v, z)) per ion type.
     pme_order None -> exact O(N_ion N_k) structure factor; even int >= 2 -> particle-mesh Ewald."""
+    species = _marshal(species)
     want = engine.dtype
     engine = _f64(engine)
     engine.set_cell(box_vecs)
     out = torch.zeros(engine.shape, dtype=torch.double, device=engine.device)
-    dp = C.POINTER(C.c_double)
-    for i, (frac, (ks, v, z)) in enumerate(species):
-        frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-        ks = np.ascontiguousarray(ks, dtype=np.float64)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if ks.shape != v.shape or ks.ndim != 1:
-            raise ValueError('table k and v must be 1-D arrays of equal length')
-        rc = engine.lib.ofdft_ionic_potential(engine._ctx, frac.ctypes.data_as(dp), frac.shape[0], ks.ctypes.data_as(dp),
-                                              v.ctypes.data_as(dp), ks.size, float(z), 0 if pme_order is None else int(pme_order),
-                                              C.c_void_p(out.data_ptr()), 1 if i else 0, engine._stream())
-        engine._check(rc, 'ofdft_ionic_potential')
+    for i, sp in enumerate(species):
+        _species_call(engine, 'ofdft_ionic_potential', (), sp, pme_order, (out, 1 if i else 0))      # (accumulate after the first)
     return out.to(want)
 
 
 def ion_electron_forces(engine, box_vecs, den, species, pme_order=None):
     """Forces F = -dU/dR of U = int n v_ext on every ion (Ha/bohr), species by species -> list of [n,3] arrays
     (the IonElectron part of System.forces(), system.py:913-923)."""
+    species = _marshal(species)
     den = engine._grid_tensor(den, 'den').double()
     engine = _f64(engine)
     engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
-    out = []
-    for frac, (ks, v, z) in species:
-        frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-        ks = np.ascontiguousarray(ks, dtype=np.float64)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        f = np.zeros_like(frac)
-        rc = engine.lib.ofdft_ion_electron_forces(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
-                                                  ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, float(z),
-                                                  0 if pme_order is None else int(pme_order), f.ctypes.data_as(dp),
-                                                  engine._stream())
-        engine._check(rc, 'ofdft_ion_electron_forces')
-        out.append(f)
-    return out
+    return [f for _frac, f in _species_loop(engine, 'ofdft_ion_electron_forces', (den,), species, np.zeros_like, pme_order)]
 
 
 def ion_electron_stress(engine, box_vecs, den, species, pme_order=None):
     """Ion-electron stress (3x3, Ha/bohr^3) with the potential rebuilt from the ions at fixed fractional coordinates
     (the IonElectron part of System.stress(), system.py:925-935), summed over species."""
+    species = _marshal(species)
     den = engine._grid_tensor(den, 'den').double()
     engine = _f64(engine)
     engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
     total = np.zeros((3, 3))
-    for frac, (ks, v, z) in species:
-        frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-        ks = np.ascontiguousarray(ks, dtype=np.float64)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        s = np.zeros(9)
-        rc = engine.lib.ofdft_ion_electron_stress(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
-                                                  ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, float(z),
-                                                  0 if pme_order is None else int(pme_order), s.ctypes.data_as(dp),
-                                                  engine._stream())
-        engine._check(rc, 'ofdft_ion_electron_stress')
+    for _frac, s in _species_loop(engine, 'ofdft_ion_electron_stress', (den,), species, lambda frac: np.zeros(9), pme_order):
         total += s.reshape(3, 3)
     return total
 
@@ -183,10 +216,7 @@ def ion_ion(engine, box_vecs, frac, charges, Rc=None, Rd=None, method='direct', 
         raise ValueError("method must be 'direct', 'cells' or 'auto'")
     if Rd is not None and not Rc:
         raise ValueError('Rd needs an explicit Rc')
-    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
-    if z.size != frac.shape[0]:
-        raise ValueError('one charge per ion')
+    frac, z = _ion_arrays(frac, charges)
     if method == 'direct':
         if Rd is not None or part != 0 or nparts != 1:
             raise ValueError("method='direct' derives Rd from Rc and computes the whole sum: Rd, part and nparts need method='cells'")
@@ -199,36 +229,26 @@ def ion_ion(engine, box_vecs, frac, charges, Rc=None, Rd=None, method='direct', 
             raise ValueError('ion_ion: about %.3g pairs within Rc = %.6g bohr (pairs_estimate) exceed max_pairs = %.3g; the direct '
                              'kernel would scan %.3g candidates (direct_candidates).  Pass a smaller Rc or raise max_pairs.'
                              % (cost['pairs_estimate'], cost['Rc'], limit, cost['direct_candidates']))
-    engine = _f64(engine)
-    engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
     E = C.c_double(0.0)
     F = np.zeros_like(frac)
     S = np.zeros(9)
     if method == 'cells':
-        rc = engine.lib.ofdft_ion_ion_cells(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
-                                            float(Rc) if Rc else 0.0, float(Rd) if Rd else 0.0, int(part), int(nparts),
-                                            C.byref(E), F.ctypes.data_as(dp), S.ctypes.data_as(dp), engine._stream())
-        engine._check(rc, 'ofdft_ion_ion_cells')
-        return E.value, F, S.reshape(3, 3)
-    rc = engine.lib.ofdft_ion_ion(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
-                                  float(Rc) if Rc else 0.0, C.byref(E), F.ctypes.data_as(dp), S.ctypes.data_as(dp),
-                                  engine._stream())
-    engine._check(rc, 'ofdft_ion_ion')
+        _ion_ion_call(engine, box_vecs, 'ofdft_ion_ion_cells', frac, z, Rc, float(Rd) if Rd else 0.0, int(part), int(nparts), C.byref(E), F, S)
+    else:
+        _ion_ion_call(engine, box_vecs, 'ofdft_ion_ion', frac, z, Rc, C.byref(E), F, S)
     return E.value, F, S.reshape(3, 3)
 
 
+def _ion_ion_call(engine, box_vecs, entry, frac, z, Rc, *tail):
+    """one call of an ion-ion entry on the fp64 engine: (ctx, frac, z, n, Rc, *tail, stream); frac, z from `_ion_arrays`"""
+    engine = _f64(engine)
+    engine.set_cell(box_vecs)
+    rc = getattr(engine.lib, entry)(engine._ctx, _arg(frac), _arg(z), frac.shape[0], float(Rc) if Rc else 0.0, *map(_arg, tail),
+                                    engine._stream())
+    engine._check(rc, entry)
+
+
 # ---------------------------------------------------------------------------------------------------- second derivatives
-def _species_arrays(frac, tab):
-    ks, v, z = tab
-    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-    ks = np.ascontiguousarray(ks, dtype=np.float64)
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    if ks.shape != v.shape or ks.ndim != 1:
-        raise ValueError('table k and v must be 1-D arrays of equal length')
-    return frac, ks, v, float(z)
-
-
 def locate_ion(species, ion):
     """(species index, index within it) of the global ion index `ion` = position in the concatenation of the species"""
     ion = int(ion)
@@ -246,19 +266,14 @@ def ionic_potential_gradient(engine, box_vecs, species, ion, pme_order=None):
     through lattice_sum yields, ion_utils.py:88-137).  `ion` counts over the concatenated species.  Exact structure factor only:
     a `pme_order` raises NotImplementedError (the derivative of the particle-mesh-Ewald spread is not built).  Plain fp64 work:
     an fp32 engine hands it to its fp64 sibling and gets the grids narrowed."""
-    if pme_order:
-        raise NotImplementedError('ionic_potential_gradient: particle-mesh Ewald (PME, pme_order=%r) is not served; '
-                                  'use the exact structure factor (pme_order=None)' % (pme_order,))
+    _pme_refusal('ionic_potential_gradient', pme_order)
     s, a = locate_ion(species, ion)
+    sp = _species_arrays(*species[s])
     want = engine.dtype
     engine = _f64(engine)
     engine.set_cell(box_vecs)
-    frac, ks, v, z = _species_arrays(*species[s])
     out = torch.empty((3,) + tuple(engine.shape), dtype=torch.double, device=engine._dev_exact)
-    dp = C.POINTER(C.c_double)
-    rc = engine.lib.ofdft_ionic_potential_gradient(engine._ctx, frac.ctypes.data_as(dp), frac.shape[0], ks.ctypes.data_as(dp),
-                                                   v.ctypes.data_as(dp), ks.size, z, 0, a, C.c_void_p(out.data_ptr()), engine._stream())
-    engine._check(rc, 'ofdft_ionic_potential_gradient')
+    _species_call(engine, 'ofdft_ionic_potential_gradient', (), sp, None, (a, out))
     return out.to(want)
 
 
@@ -266,22 +281,14 @@ def ion_electron_curvature(engine, box_vecs, den, species, pme_order=None):
     """D[a] = d^2 (int n v_ext) / dR_a dR_a at fixed density for every ion, species by species -> list of [n, 3, 3] arrays
     (Ha/bohr^2; `ofdft_ion_electron_curvature`: the diagonal blocks of the Hessian of IonElectron over lattice_sum, whose
     off-diagonal blocks vanish).  fp64 engines only: the density is the engine's own, as for `Engine.stress`."""
-    if pme_order:
-        raise NotImplementedError('ion_electron_curvature: particle-mesh Ewald (PME, pme_order=%r) is not served; '
-                                  'use the exact structure factor (pme_order=None)' % (pme_order,))
+    _pme_refusal('ion_electron_curvature', pme_order)
+    species = _marshal(species)
     if engine.dtype != torch.double:
         raise NotImplementedError('ion_electron_curvature is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
     den = engine._grid_tensor(den, 'den')
     engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
     out = []
-    for frac, tab in species:
-        frac, ks, v, z = _species_arrays(frac, tab)
-        c6 = np.zeros((frac.shape[0], 6))
-        rc = engine.lib.ofdft_ion_electron_curvature(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
-                                                     ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, z, 0, c6.ctypes.data_as(dp),
-                                                     engine._stream())
-        engine._check(rc, 'ofdft_ion_electron_curvature')
+    for frac, c6 in _species_loop(engine, 'ofdft_ion_electron_curvature', (den,), species, lambda frac: np.zeros((frac.shape[0], 6))):
         D = np.empty((frac.shape[0], 3, 3))
         for k, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
             D[:, i, j] = D[:, j, i] = c6[:, k]
@@ -293,48 +300,28 @@ def ion_ion_hessian(engine, box_vecs, frac, charges, rows, Rc=None):
     """d^2 E_ion-ion / dR_p dR_b for p in `rows` -> [len(rows), n, 3, 3] (Ha/bohr^2): a second autograd pass over
     ion_interaction_sum (ion_utils.py:293-333) at a fixed pair list, with the Rd / Rc rules and the pair set of
     `ion_ion(method='direct')` (`ofdft_ion_ion_hessian`).  Plain fp64 work: an fp32 engine hands it to its fp64 sibling."""
-    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
-    if z.size != frac.shape[0]:
-        raise ValueError('one charge per ion')
+    frac, z = _ion_arrays(frac, charges)
     rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
     if rows.size == 0 or rows.min() < 0 or rows.max() >= frac.shape[0]:
         raise ValueError('rows must name at least one ion, each in [0, %d)' % frac.shape[0])
-    engine = _f64(engine)
-    engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
     H = np.zeros((rows.size, frac.shape[0], 3, 3))
-    rc = engine.lib.ofdft_ion_ion_hessian(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
-                                          float(Rc) if Rc else 0.0, rows.ctypes.data_as(C.POINTER(C.c_int)), rows.size,
-                                          H.ctypes.data_as(dp), engine._stream())
-    engine._check(rc, 'ofdft_ion_ion_hessian')
+    _ion_ion_call(engine, box_vecs, 'ofdft_ion_ion_hessian', frac, z, Rc, rows, rows.size, H)
     return H
 
 
 # ---------------------------------------------------------------------------------------------------- strain derivatives
-def _pme_refusal(who, pme_order):
-    if pme_order:
-        raise NotImplementedError('%s: particle-mesh Ewald (PME, pme_order=%r) is not served; use the exact structure factor '
-                                  '(pme_order=None)' % (who, pme_order))
-
-
 def ionic_potential_strain_gradient(engine, box_vecs, species, pme_order=None):
     """d v_ext / d eps_kl, kl = xx, yy, zz, yz, xz, xy, under h -> h (I + eps) at fixed fractional coordinates -> [6, n0, n1, n2]:
     -delta_kl v_ext + F^-1[S v~'(|k|) (-k_k k_l / |k|)] / vol summed over the species (`ofdft_ionic_potential_strain_gradient`;
     DESIGN.md §9e).  Exact structure factor only.  Plain fp64 work: an fp32 engine hands it to its fp64 sibling."""
     _pme_refusal('ionic_potential_strain_gradient', pme_order)
+    species = _marshal(species)
     want = engine.dtype
     engine = _f64(engine)
     engine.set_cell(box_vecs)
     total = None
-    dp = C.POINTER(C.c_double)
-    for frac, tab in species:
-        frac, ks, v, z = _species_arrays(frac, tab)
-        out = torch.empty((6,) + tuple(engine.shape), dtype=torch.double, device=engine._dev_exact)
-        rc = engine.lib.ofdft_ionic_potential_strain_gradient(engine._ctx, frac.ctypes.data_as(dp), frac.shape[0], ks.ctypes.data_as(dp),
-                                                              v.ctypes.data_as(dp), ks.size, z, 0, C.c_void_p(out.data_ptr()),
-                                                              engine._stream())
-        engine._check(rc, 'ofdft_ionic_potential_strain_gradient')
+    new_out = lambda frac: torch.empty((6,) + tuple(engine.shape), dtype=torch.double, device=engine._dev_exact)  # noqa: E731
+    for _frac, out in _species_loop(engine, 'ofdft_ionic_potential_strain_gradient', (), species, new_out):
         total = out if total is None else total + out
     return total.to(want)
 
@@ -344,19 +331,13 @@ def ion_electron_strain_hessian(engine, box_vecs, den, species, pme_order=None):
     fractional coordinates, the potential rebuilt from the ions in the strained cell, summed over the species
     (`ofdft_ion_electron_strain_hessian`).  fp64 engines only: the density is the engine's own, as for `Engine.stress`."""
     _pme_refusal('ion_electron_strain_hessian', pme_order)
+    species = _marshal(species)
     if engine.dtype != torch.double:
         raise NotImplementedError('ion_electron_strain_hessian is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
     den = engine._grid_tensor(den, 'den')
     engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
     total = np.zeros(81)
-    for frac, tab in species:
-        frac, ks, v, z = _species_arrays(frac, tab)
-        w = np.zeros(81)
-        rc = engine.lib.ofdft_ion_electron_strain_hessian(engine._ctx, C.c_void_p(den.data_ptr()), frac.ctypes.data_as(dp), frac.shape[0],
-                                                          ks.ctypes.data_as(dp), v.ctypes.data_as(dp), ks.size, z, 0, w.ctypes.data_as(dp),
-                                                          engine._stream())
-        engine._check(rc, 'ofdft_ion_electron_strain_hessian')
+    for _frac, w in _species_loop(engine, 'ofdft_ion_electron_strain_hessian', (den,), species, lambda frac: np.zeros(81)):
         total += w
     return total.reshape(3, 3, 3, 3)
 
@@ -365,15 +346,7 @@ def ion_ion_strain_hessian(engine, box_vecs, frac, charges, Rc=None):
     """d^2 E_ion-ion / d eps_mn d eps_pq -> [3, 3, 3, 3] (Ha) at fixed fractional coordinates: the pair sum over the fixed pair list
     of `ion_ion(method='direct')` with Rd and Rc held (the reference takes h_max from box_vecs.detach()), plus the background
     term through rho ~ 1/J and R_a ~ J^(1/3) (`ofdft_ion_ion_strain_hessian`).  Plain fp64 work."""
-    frac = np.ascontiguousarray(np.asarray(torch.as_tensor(frac).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3))
-    z = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
-    if z.size != frac.shape[0]:
-        raise ValueError('one charge per ion')
-    engine = _f64(engine)
-    engine.set_cell(box_vecs)
-    dp = C.POINTER(C.c_double)
+    frac, z = _ion_arrays(frac, charges)
     w = np.zeros(81)
-    rc = engine.lib.ofdft_ion_ion_strain_hessian(engine._ctx, frac.ctypes.data_as(dp), z.ctypes.data_as(dp), frac.shape[0],
-                                                 float(Rc) if Rc else 0.0, w.ctypes.data_as(dp), engine._stream())
-    engine._check(rc, 'ofdft_ion_ion_strain_hessian')
+    _ion_ion_call(engine, box_vecs, 'ofdft_ion_ion_strain_hessian', frac, z, Rc, w)
     return w.reshape(3, 3, 3, 3)

@@ -603,6 +603,77 @@ def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=N
     return dict(dn=dn, dmu=dmu, iterations=iters, rel_residual=rel, reason=reason, hvp_count=nprod)
 
 
+# ---- what the drivers over `density_response` share (force_constants.py, elastic.py)
+A_PER_BOHR = 5.29177210903e-11 * 1e10      # system.py:27-33 (CODATA 2018)
+
+
+def normalise_species(species):
+    """-> (species with fp64 [n, 3] coordinates, frac [N, 3] and charges [N] of all ions).  The global ion index is the position
+    in the concatenation of the species, and n_elec = charges.sum()."""
+    species = [(np.asarray(torch.as_tensor(f).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3), tab) for f, tab in species]
+    frac = np.concatenate([f for f, _t in species], axis=0)
+    charges = np.concatenate([np.full(f.shape[0], float(tab[2])) for f, tab in species])
+    return species, frac, charges
+
+
+def response_refusal(engine, pme_order=None):
+    """None, or why a driver over `density_response` with ions cannot run on this engine (raised before any device work)"""
+    from . import _native as N
+    if pme_order:
+        return ('particle-mesh Ewald (PME, pme_order=%r) is not served: the derivative of the B-spline spread is not built; '
+                'use the exact structure factor' % (pme_order,))
+    why = second_order_refusal(engine)
+    if why:
+        return why
+    if not engine._mask() & N.TERM_BITS['ion_electron']:
+        return 'the term set has no ion_electron term: nothing couples the density to the ions'
+    return None
+
+
+class HipResponseBackend:
+    """Base of the drivers' device backends: the engine on its cell, dV, the conjugate gradients (`cg`, closed by `close`) and the
+    check of the ground state.  Grids are torch tensors of the engine; the small results are numpy arrays."""
+
+    def __init__(self, engine, box_vecs, species):
+        self.eng, self.box, self.species = engine, box_vecs, species
+        engine.set_cell(box_vecs)
+        self.volume = engine.volume
+        self.dV = engine.volume / engine.npts
+        self.cg = HipCgBackend(engine)
+
+    def ground_state_gradient(self, chi, n_elec):
+        """max|g| / dV of the closure at chi with v_ext rebuilt from the ions"""
+        from . import ions
+        vext = ions.ionic_potential(self.eng, self.box, self.species)
+        _E, _mu, g = self.eng.energy_grad_chi(chi, n_elec, vext)
+        return float(g.abs().max()) / self.dV
+
+    def close(self):
+        self.cg.close()
+
+
+def new_solve_log():
+    """what a driver reports of its response solves, in solve order"""
+    return dict(iterations=[], rel_residual=[], reason=[], hvp_count=0)
+
+
+def log_solve(log, r):
+    """append the result `r` of one `density_response` call"""
+    for k in ('iterations', 'rel_residual', 'reason'):
+        log[k].append(r[k])
+    log['hvp_count'] += r['hvp_count']
+
+
+def warn_unconverged(who, log, maxiter, what):
+    """The conjugate gradients are unpreconditioned: their iteration count grows with the grid, so a solve may end
+    at maxiter.  `what`: what is then not accurate."""
+    import warnings
+    bad = sum(x != CG_CONVERGED for x in log['reason'])
+    if bad:
+        warnings.warn('%s: %d of %d response solves did not converge within maxiter=%d (see `reason`, `rel_residual`); %s'
+                      % (who, bad, len(log['reason']), maxiter, what))
+
+
 def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_cond_count=3, n_step_size=0.1,
                      n_maxiter=1000, conv_target='dE', verbose=False, volume=None, optimizer='fused', n_method='LBFGS',
                      tn_cg_maxiter=50, tn_gtol=1e-10):

@@ -237,3 +237,94 @@ def test_entry_points_are_exported_and_refuse_null_arguments(dtype):
     assert lib.ofdft_ionic_potential_gradient(None, x, 1, x, x, 2, 3.0, 0, 0, None, None) == N.EINVAL
     assert lib.ofdft_ion_electron_curvature(None, None, x, 1, x, x, 2, 3.0, 0, x, None) == N.EINVAL
     assert lib.ofdft_ion_ion_hessian(None, x, x, 1, 0.0, rows, 1, x, None) == N.EINVAL
+
+
+# ------------------------------------------------------------------------------- 5: the driver code shared with elastic.py
+def test_the_device_backend_is_closed_when_a_piece_raises(monkeypatch):
+    """force_constants owns the backend it makes: a piece that raises leaves no conjugate-gradient handle behind"""
+    from professad_amd import force_constants as fc_mod
+
+    class Fake:
+        dV = 1.0
+        closed = 0
+
+        def __init__(self, engine, box_vecs, species):
+            Fake.made = self
+
+        def ground_state_gradient(self, chi, n_elec):
+            return 0.0
+
+        def ion_ion_hessian(self, frac, charges, rows, Rc):
+            return np.zeros((len(rows), frac.shape[0], 3, 3))
+
+        def ion_electron_curvature(self, den):
+            raise RuntimeError('curvature failed')
+
+        def close(self):
+            self.closed += 1
+
+    monkeypatch.setattr(fc_mod, 'HipFcBackend', Fake)
+    monkeypatch.setattr(fc_mod, 'refusal', lambda engine, pme_order=None: None)
+    tab = (np.linspace(0.0, 4.0, 9), np.ones(9), 3.0)
+    with pytest.raises(RuntimeError, match='curvature failed'):
+        force_constants(None, np.eye(3), [(np.zeros((2, 3)), tab)], np.ones((2, 2, 2)))
+    assert Fake.made.closed == 1
+
+
+def test_both_drivers_normalise_a_species_list_the_same_way(monkeypatch):
+    """one normalisation (optimize.normalise_species) behind force_constants and elastic_constants: the backends of both see the
+    same (frac, charges, n_elec) for a two-species list"""
+    from professad_amd import elastic as el_mod
+    from professad_amd import force_constants as fc_mod
+    tab_a, tab_b = (np.linspace(0.0, 4.0, 9), np.ones(9), 3.0), (np.linspace(0.0, 4.0, 5), np.ones(5), 1.0)
+    species = [([[0.0, 0.0, 0.0], [0.5, 0.5, 0.5]], tab_a), (np.array([0.25, 0.25, 0.75]), tab_b)]
+    want_frac = np.array([[0.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.25, 0.25, 0.75]])
+    want_z = np.array([3.0, 3.0, 1.0])
+    norm, frac, z = optimize.normalise_species(species)
+    assert np.array_equal(frac, want_frac) and np.array_equal(z, want_z) and frac.dtype == np.float64
+    assert [f.shape for f, _t in norm] == [(2, 3), (1, 3)] and norm[1][1] is tab_b
+    seen = {}
+
+    class Stop(Exception):
+        pass
+
+    class Spy:
+        dV, volume = 1.0, 1.0
+
+        def __init__(self, who):
+            self.who = who
+
+        def ground_state_gradient(self, chi, n_elec):
+            seen[self.who] = [n_elec]
+            return 0.0
+
+        def ion_ion_hessian(self, frac, charges, rows, Rc):
+            seen[self.who] += [frac, charges]
+            raise Stop
+
+        def strain_hessian(self, den):
+            return {}
+
+        def ion_ion_strain_hessian(self, frac, charges, Rc):
+            seen[self.who] += [frac, charges]
+            raise Stop
+
+    chi = np.ones((2, 2, 2))
+    with pytest.raises(Stop):
+        fc_mod.force_constants(None, np.eye(3), species, chi, backend=Spy('fc'))
+    with pytest.raises(Stop):
+        el_mod.elastic_constants(None, np.eye(3), species, chi, backend=Spy('el'))
+    for who in ('fc', 'el'):
+        n_elec, frac, z = seen[who]
+        assert n_elec == 7.0 and np.array_equal(frac, want_frac) and np.array_equal(z, want_z)
+
+
+def test_species_arrays_rejects_unequal_and_two_dimensional_tables():
+    from professad_amd.ions import _species_arrays
+    ks = np.linspace(0.0, 4.0, 9)
+    frac, k, v, z = _species_arrays([0.1, 0.2, 0.3], (ks, np.ones(9), 3))
+    assert frac.shape == (1, 3) and frac.flags.c_contiguous and k.dtype == v.dtype == np.float64 and z == 3.0 and isinstance(z, float)
+    with pytest.raises(ValueError, match='equal length'):
+        _species_arrays(np.zeros((1, 3)), (ks, np.ones(8), 3.0))
+    with pytest.raises(ValueError, match='1-D'):
+        _species_arrays(np.zeros((1, 3)), (ks.reshape(3, 3), np.ones((3, 3)), 3.0))
