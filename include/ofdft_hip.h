@@ -98,11 +98,16 @@ typedef struct ofdft_ctx ofdft_ctx;
                                    set with OFDFT_TF and OFDFT_WT_NL (or OFDFT_NLK: KGAP's f argument): T = T_TF f(X), X = T_NL / (f'(0) T_TF).  0 (default): f(x) = 1 + x,
                                    i.e. the plain sum T_TF + T_NL; 1: f(x) = exp(x).  Then E_terms[TF] reports T_TF f(X), E_terms[WT_NL]
                                    zero, the potential and the stress carry the weights f - f' X and f'(X) / f'(0).  Single-GPU contexts. */
-#define OFDFT_P_NLK_KIND    13  /* kernel of OFDFT_NLK: 1 = KGAP, 2 = Mi-Genova-Pavanello, 3 = Xu-Wang-Ma (0, the default, is refused with the bit set) */
-#define OFDFT_P_NLK_P0      14  /* KGAP: E_gap [eV] (0 -> alpha = beta = 1/2 and the Lindhard kernel: Smargiassi-Madden); MGP: a; XWM: kappa */
-#define OFDFT_P_NLK_P1      15  /* MGP: b */
-#define OFDFT_P_NLK_P2      16  /* reserved (0) */
-#define OFDFT_NPARAMS       17
+#define OFDFT_P_NLK_KIND    13  /* kernel of OFDFT_NLK: 1 = KGAP, 2 = Mi-Genova-Pavanello, 3 = Xu-Wang-Ma, 4 = Huang-Carter, 5 = revised
+                                   Huang-Carter (0, the default, is refused with the bit set).  Kinds 4 and 5 (functionals.py:1176-1365) have a
+                                   density-DEPENDENT kernel w(|r - r'|, xi(r)): they do not ride the Wang-Teter stages but run a chain of their own
+                                   after the rest of the term set (csrc/engine_hc.inc.h), need the table of ofdft_set_nlk_table,
+                                   0 < beta < 5/3, kappa > 1, lambda, a, b >= 0 and OFDFT_P_WTS_KIND = 0; fp64 library, no stress */
+#define OFDFT_P_NLK_P0      14  /* KGAP: E_gap [eV] (0 -> alpha = beta = 1/2 and the Lindhard kernel: Smargiassi-Madden); MGP: a; XWM: kappa; HC: lambda; revHC: a */
+#define OFDFT_P_NLK_P1      15  /* MGP: b; HC: beta; revHC: b */
+#define OFDFT_P_NLK_P2      16  /* HC: kappa, the ratio of the geometric xi nodes; revHC: beta */
+#define OFDFT_P_NLK_P3      17  /* revHC: kappa */
+#define OFDFT_NPARAMS       18
 
 /* The scalar block of an evaluation (ofdft_dist_finish / ofdft_dist_scalars / ofdft_dist_energies; csrc/eval_layout.h names every
  * slot): OFDFT_NSCALARS doubles owned by the context, of which the first OFDFT_NSUMS are the local sums of an evaluation (ten of the
@@ -140,6 +145,12 @@ const char* ofdft_last_error(const ofdft_ctx* ctx);   /* ctx may be NULL: last c
 
 int  ofdft_set_cell(ofdft_ctx* ctx, const double box_vecs[9]);
 int  ofdft_set_terms(ofdft_ctx* ctx, uint32_t term_mask, const double* params, int nparams);
+/* The 1-D kernel table w(eta) of the Huang-Carter kinds of OFDFT_NLK (OFDFT_P_NLK_KIND = 4, 5): n >= 4 values on a uniform eta
+ * grid that starts at 0 (host arrays; the reference's HuangCarter.kernel, functionals.py:1227-1230).  The call forms the node
+ * slopes of functional_tools.interpolate (functional_tools.py:309-310) on the host and uploads both arrays; eta beyond the last
+ * node reads the last node (functionals.py:1257).  It replaces an earlier table and clears the validity of the OFDFT_NLK tables.
+ * An evaluation of kind 4 / 5 without a table returns OFDFT_ESTATE.  fp64 library only (the fp32 one returns OFDFT_EINVAL). */
+int  ofdft_set_nlk_table(ofdft_ctx* ctx, const double* eta_host, const double* w_host, int n);
 
 /* E_terms_host[OFDFT_NTERMS] (entries of unset terms are 0); dEdn_dev may be NULL (energy only).
  * vext_dev is required iff OFDFT_ION_ELECTRON is set. */

@@ -23,10 +23,12 @@ TERM_BITS = {
 TERM_ORDER = ['ion_electron', 'hartree', 'tf', 'vw', 'wt_nl', 'wgc99_nl', 'lda_x', 'pz_c', 'pw_c', 'chachiyo_c',
               'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk']
 NTERMS = 15
-NPARAMS = 17
+NPARAMS = 18
 # local sums of an evaluation; doubles of the context's device-resident scalar block (ofdft_dist_scalars); its slot of sum chi^2
 NSUMS, NSCALARS, SCALAR_SUMSQ = 13, 16, 15
 NLK_KGAP, NLK_MGP, NLK_XWM = 1, 2, 3      # OFDFT_P_NLK_KIND
+NLK_HC, NLK_REVHC = 4, 5                  # ... with a density-dependent kernel (HuangCarter, RevisedHuangCarter)
+P_NLK_KIND, P_NLK_P0, P_NLK_P1, P_NLK_P2, P_NLK_P3 = 13, 14, 15, 16, 17      # OFDFT_P_NLK_*
 NTERMS_ALWAYS = 14      # per-term results always carry these terms (zero when not in the set); a later one only while it is set
 
 
@@ -67,7 +69,7 @@ CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_CURVATURE = 0, 1, 2, 3
 CG_REASONS = {CG_RUNNING: 'running', CG_CONVERGED: 'converged', CG_MAXITER: 'maxiter', CG_CURVATURE: 'curvature'}
 
 EXPORTS = ['ofdft_create', 'ofdft_destroy', 'ofdft_last_error', 'ofdft_set_cell', 'ofdft_set_terms',
-           'ofdft_energy_potential', 'ofdft_energy_grad_chi', 'ofdft_rfftn', 'ofdft_irfftn', 'ofdft_debug_math', 'ofdft_query',
+           'ofdft_set_nlk_table', 'ofdft_energy_potential', 'ofdft_energy_grad_chi', 'ofdft_rfftn', 'ofdft_irfftn', 'ofdft_debug_math', 'ofdft_query',
            'ofdft_create_dist', 'ofdft_dist_sumsq', 'ofdft_dist_begin', 'ofdft_dist_stage', 'ofdft_dist_step', 'ofdft_dist_finish', 'ofdft_dist_scalars',
            'ofdft_dist_energies', 'ofdft_dist_chi_grad', 'ofdft_ipc_export', 'ofdft_ipc_attach', 'ofdft_ipc_detach', 'ofdft_dist_closure', 'ofdft_ionic_potential', 'ofdft_ion_electron_forces', 'ofdft_stress', 'ofdft_ion_electron_stress', 'ofdft_ion_ion', 'ofdft_ion_ion_cells', 'ofdft_ionic_potential_gradient', 'ofdft_ion_electron_curvature', 'ofdft_ion_ion_hessian',
            'ofdft_potential_strain_gradient', 'ofdft_ionic_potential_strain_gradient', 'ofdft_strain_hessian','ofdft_ion_electron_strain_hessian', 'ofdft_ion_ion_strain_hessian',
@@ -118,6 +120,7 @@ def load(dtype=F64):
     lib.ofdft_last_error.restype = C.c_char_p
     lib.ofdft_set_cell.argtypes = [vp, dp]
     lib.ofdft_set_terms.argtypes = [vp, C.c_uint32, dp, ip]
+    lib.ofdft_set_nlk_table.argtypes = [vp, dp, dp, ip]
     lib.ofdft_energy_potential.argtypes = [vp, vp, vp, dp, vp, vp]
     lib.ofdft_energy_grad_chi.argtypes = [vp, vp, vp, C.c_double, dp, dp, vp, vp]
     lib.ofdft_rfftn.argtypes = [vp, vp, vp, vp]

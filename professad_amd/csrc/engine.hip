@@ -10,6 +10,7 @@
 #include "hvp_kernels.h"
 #include "fc_kernels.h"
 #include "strain2_kernels.h"
+#include "hc_kernels.h"
 #endif
 
 namespace {
@@ -181,6 +182,19 @@ struct ProfRec { const char* name; hipEvent_t a, b; };
 void graph_drop(ofdft_ctx* c);
 void ipc_release(ofdft_ctx* c);
 void resident_give_up(ofdft_ctx* c);
+// OFDFT_NLK of kind 4 / 5 (HuangCarter / RevisedHuangCarter): a chain of its own around the rest of the term set (engine_hc.inc.h)
+inline bool hc_kind_active(const ofdft_ctx* c) { return (c->mask & OFDFT_NLK) && c->params[OFDFT_P_NLK_KIND] >= 4.0; }
+int hc_evaluate(ofdft_ctx* c, const void* src, bool closure, const void* vext, double n_electrons, double* E_terms, double* mu_host, void* out,
+                void* stream);
+// The staged entries (ofdft_dist_begin .. ofdft_dist_finish, ofdft_dist_closure) have no such chain: they refuse the two kinds.
+// Called before anything of the last evaluation is reset, so its counters stay as they were.
+int hc_refuse_staged(ofdft_ctx* c) {
+    if (!hc_kind_active(c)) return 0;
+    return fail(c, OFDFT_EINVAL,
+                "OFDFT_NLK of kind %d (HuangCarter / RevisedHuangCarter) is served by ofdft_energy_potential and ofdft_energy_grad_chi only: "
+                "the staged ofdft_dist_* entries carry the Wang-Teter stages, which serve kinds 1 .. 3",
+                (int)c->params[OFDFT_P_NLK_KIND]);
+}
 
 // ---------------------------------------------------------------------------------- reductions
 // copy `rows` x `ns` partials to the host and sum them in a fixed order
@@ -992,7 +1006,7 @@ int ofdft_create_dist(ofdft_ctx** out, int n0g, int n1g, int n2, int dtype, int 
     xchg_chunks_set(c, 0);
     const double s5 = std::sqrt(5.0);
     const double defaults[OFDFT_NPARAMS] = {kFiveSixths, kFiveSixths, (5.0 + s5) / 6.0, (5.0 - s5) / 6.0, (double)27 / 10, 1.0, 0.0, (double)40 / 27,
-                                            0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                                            0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     std::memcpy(c->params, defaults, sizeof(defaults));
     DeviceScope device_scope_(device_id);
     hipError_t e = device_scope_.err;
@@ -1047,6 +1061,8 @@ void ofdft_destroy(ofdft_ctx* c) {
     if (c->d_wgc_coef) (void)hipFree(c->d_wgc_coef);
     if (c->d_nlk_w) (void)hipFree(c->d_nlk_w);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
+    for (auto e : c->hc_ev)
+        if (e) (void)hipEventDestroy(e);
     delete c->zr;
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1110,14 +1126,30 @@ int ofdft_set_terms(ofdft_ctx* c, uint32_t mask, const double* params, int npara
             return fail(c, OFDFT_EINVAL, "OFDFT_NLK (KGAP / MGP / XWM) is served by single-GPU contexts: the slab-decomposed path has no tabulated-kernel term yet");
         if (mask & (OFDFT_WT_NL | OFDFT_WGC99_NL))
             return fail(c, OFDFT_EINVAL, "OFDFT_NLK cannot be combined with OFDFT_WT_NL / OFDFT_WGC99_NL: they share the nonlocal chain's buffers");
-        if (kind != 1.0 && kind != 2.0 && kind != 3.0)
-            return fail(c, OFDFT_EINVAL, "OFDFT_NLK needs OFDFT_P_NLK_KIND = 1 (KGAP), 2 (MGP) or 3 (XWM), got %g", kind);
+        if (kind != 1.0 && kind != 2.0 && kind != 3.0 && kind != 4.0 && kind != 5.0)
+            return fail(c, OFDFT_EINVAL, "OFDFT_NLK needs OFDFT_P_NLK_KIND = 1 (KGAP), 2 (MGP), 3 (XWM), 4 (HC) or 5 (revHC), got %g", kind);
+        if (kind >= 4.0) {         // HuangCarter (lambda, beta, kappa) / RevisedHuangCarter (a, b, beta, kappa)
+#ifdef OFDFT_REAL_F32
+            return fail(c, OFDFT_EINVAL, "OFDFT_NLK of kind 4 / 5 (Huang-Carter) is served by the fp64 library (libofdft_hip.so) only");
+#else
+            auto slot = [&](int i) { return nparams > i ? params[i] : c->params[i]; };
+            const bool hc = kind == 4.0;
+            const char* who = hc ? "HuangCarter" : "RevisedHuangCarter";
+            const double p1 = slot(OFDFT_P_NLK_P1), beta = hc ? p1 : slot(OFDFT_P_NLK_P2), kappa = slot(hc ? OFDFT_P_NLK_P2 : OFDFT_P_NLK_P3);
+            if (!(kappa > 1.0)) return fail(c, OFDFT_EINVAL, "%s: kappa must exceed 1 (the ratio of the geometric xi nodes), got %g", who, kappa);
+            if (!(beta > 0.0 && beta < 5.0 / 3.0)) return fail(c, OFDFT_EINVAL, "%s: beta must lie in (0, 5/3), got %g", who, beta);
+            if (!(p0 >= 0.0)) return fail(c, OFDFT_EINVAL, "%s: %s must be >= 0, got %g", who, hc ? "lambda" : "a", p0);
+            if (!hc && !(p1 >= 0.0)) return fail(c, OFDFT_EINVAL, "%s: b must be >= 0, got %g", who, p1);
+            if (slot(OFDFT_P_WTS_KIND) != 0.0)
+                return fail(c, OFDFT_EINVAL, "%s has no stabilised form: OFDFT_P_WTS_KIND (wts_kind) must be 0 with OFDFT_P_NLK_KIND = 4 / 5", who);
+#endif
+        }
         if (kind == 1.0 && !(p0 >= 0.0)) return fail(c, OFDFT_EINVAL, "KGAP: E_gap must be >= 0 eV, got %g", p0);
         if (kind == 3.0 && !(p0 > -5.0 / 6.0)) return fail(c, OFDFT_EINVAL, "XWM: kappa must exceed -5/6, got %g", p0);
     }
     for (int i = 0; i < nparams; ++i) {
         if (i >= OFDFT_P_WGC_ALPHA && i <= OFDFT_P_WGC_KAPPA && c->params[i] != params[i]) c->wgc_valid = false;
-        if (i >= OFDFT_P_NLK_KIND && i <= OFDFT_P_NLK_P2 && c->params[i] != params[i]) c->nlk_valid = false;
+        if (i >= OFDFT_P_NLK_KIND && i <= OFDFT_P_NLK_P3 && c->params[i] != params[i]) c->nlk_valid = false;
         c->params[i] = params[i];
     }
     c->mask = mask;
@@ -1130,6 +1162,7 @@ int ofdft_energy_potential(ofdft_ctx* c, const void* den, const void* vext, doub
     hipStream_t st = (hipStream_t)stream;
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
+    if (hc_kind_active(c)) return hc_evaluate(c, den, false, vext, 0.0, E_terms, nullptr, dEdn, stream);
     if (int rc = begin_call(c, st)) return rc;
     if (!den || !E_terms) return fail(c, OFDFT_EINVAL, "null argument");
     if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
@@ -1328,6 +1361,7 @@ int ofdft_energy_grad_chi(ofdft_ctx* c, const void* chi, const void* vext, doubl
     hipStream_t st = (hipStream_t)stream;
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
+    if (hc_kind_active(c)) return hc_evaluate(c, chi, true, vext, n_electrons, E_terms, mu_host, grad, stream);
     const bool timed = !(c->resident == 2 && resident_serves(c) && !c->profiling);
     if (int rc = begin_call(c, st, timed)) return rc;
     if (!chi || !E_terms) return fail(c, OFDFT_EINVAL, "null argument");
@@ -1494,6 +1528,7 @@ int ofdft_dist_begin(ofdft_ctx* c, const void* src_local, int from_chi, double c
     hipStream_t st = (hipStream_t)stream;
     if (!c) return OFDFT_EINVAL;
     OFDFT_ON_DEVICE(c, c->device);
+    if (int rc = hc_refuse_staged(c)) return rc;
     if (int rc = begin_call(c, st)) return rc;
     // from_chi == 2: the closure scale is formed from the (all-reduced) sum of chi^2 in scalars[OFDFT_SCALAR_SUMSQ]; it never visits the host
     const DenSrc ds = from_chi == 2 ? DenSrc{(const real*)src_local, 0.0, 1, c->d_scal + kScalClosure}
@@ -1609,6 +1644,7 @@ int ofdft_dist_chi_grad(ofdft_ctx* c, const void* chi_local, const void* v_local
 #include "engine_hvp.inc.h"
 #include "engine_force_constants.inc.h"
 #include "engine_strain.inc.h"
+#include "engine_hc.inc.h"
 #else
 // The fp32 build serves the density-optimisation hot path only.  The once-per-geometry-step quantities (ionic potential,
 // forces, stress, ion-ion sum) are fp64 work: callers run them on the fp64 library (professad_amd.ions does).
@@ -1654,6 +1690,11 @@ int ofdft_ion_electron_strain_hessian(ofdft_ctx* c, const void*, const double*, 
     return OFDFT_F64_ONLY(c);
 }
 int ofdft_ion_ion_strain_hessian(ofdft_ctx* c, const double*, const double*, int, double, double*, void*) { return OFDFT_F64_ONLY(c); }
+int ofdft_set_nlk_table(ofdft_ctx* c, const double*, const double*, int) { return OFDFT_F64_ONLY(c); }
+}
+namespace {
+// (never reached: ofdft_set_terms of this build refuses the kinds)
+int hc_evaluate(ofdft_ctx* c, const void*, bool, const void*, double, double*, double*, void*, void*) { return OFDFT_F64_ONLY(c); }
 }
 #endif
 

@@ -82,6 +82,11 @@ struct ofdft_ctx {
     long long nlk_key_nel = -1;    // round(N_e)
     double nlk_key_nel_exact = 0.0;  // XWM: eta comes from the un-rounded count (functionals.py:631-639)
     double* d_nlk_w = nullptr;     // MGP: the 1-D table (kMgpNodes doubles) + one word for max |k|^2
+    // OFDFT_NLK of kind 4 / 5 (Huang-Carter; engine_hc.inc.h): the 1-D table w(eta) and its slopes in "t:hc" (ofdft_set_nlk_table)
+    int hc_tab_n = 0;              // nodes of the table (0: none set)
+    double hc_tab_h = 0.0;         // its spacing
+    bool hc_inner = false;         // the rest of such a term set is being evaluated: the persistent kernel and the graph replay decline
+    hipEvent_t hc_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // head and tail of the chain, timed around the rest (OFDFT_Q_KERNEL_MS)
     bool wgc_fold = true;          // orthogonal cells: the cross-wave x pass reads the table entry of x > n0 / 2 at n0 - x (OFDFT_OPT_WGC_FOLD)
     // stats
     int fft_count = 0, launch_count = 0;
@@ -215,10 +220,12 @@ inline NlPow nl_pow(const ofdft_ctx* c) {
             p.e_a = p.al;
         } else if (p.kind == NLK_MGP) {
             p.al = p.be = p.e_b = p.e_a = kFiveSixths;
-        } else {                                 // XWM functionals.py:1480,1492
+        } else if (p.kind == NLK_XWM) {          // functionals.py:1480,1492
             p.al = p.e_b = x + kFiveSixths;
             p.be = p.e_a = x + (double)11 / 6;
             p.sym = 1;
+        } else {                                 // kinds 4 / 5 (Huang-Carter) are no two-power term: they have their own chain
+            p.on = p.nlk = false;                // (engine_hc.inc.h), and the staged entries refuse them (hc_refuse_staged)
         }
     }
     p.two = p.on && p.al != p.be;
@@ -323,7 +330,8 @@ int fail(ofdft_ctx* c, int code, const char* fmt, ...);
 // hipGraph replay serves the launch-bound regime only (single-GPU contexts up to 2^19 points, e.g. 64 x 64 x 128; above
 // that launches are hidden behind the kernels and the measured gain is nil).  There the WGC99 part of the combine stays inside the combine kernel: the forked + split stream topology
 // crashes this ROCm's stream capture, and fewer launches is the better trade on small grids anyway.
-inline bool graph_eligible(const ofdft_ctx* c) { return c->use_graph && c->nranks == 1 && c->npts <= (1LL << 19); }
+// (the rest of a Huang-Carter term set, c->hc_inner, launches kernel by kernel: its chain has a host round trip in the middle)
+inline bool graph_eligible(const ofdft_ctx* c) { return c->use_graph && c->nranks == 1 && c->npts <= (1LL << 19) && !c->hc_inner; }
 void prof_begin(ofdft_ctx* c, hipStream_t st, const char* name);
 void prof_end(ofdft_ctx* c, hipStream_t st);
 void prof_collect(ofdft_ctx* c);

@@ -274,6 +274,8 @@ int ofdft_stress(ofdft_ctx* c, const void* den_dev, double* sig, void* stream) {
         return fail(c, OFDFT_EINVAL, "the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND) is served by single-GPU contexts");
     if ((c->mask & OFDFT_NLK) && c->params[OFDFT_P_NLK_KIND] == 2.0)
         return fail(c, OFDFT_EINVAL, "MiGenovaPavanello has no stress: the reference's own get_stress raises on it (torch.unique has no derivative)");
+    if ((c->mask & OFDFT_NLK) && c->params[OFDFT_P_NLK_KIND] >= 4.0)
+        return fail(c, OFDFT_EINVAL, "HuangCarter / RevisedHuangCarter (OFDFT_P_NLK_KIND = 4 / 5): no stress (the strain derivative of the density-dependent kernel is not built)");
     const double* den = (const double*)den_dev;
     const unsigned mask = c->mask;
     const long long npts = c->npts;

@@ -87,6 +87,7 @@ enum { kStepYFwd = 1, kStepX, kStepYInv, kStepMid, kStepDivX, kStepDivYInv, kSte
 int zrun_begin(ofdft_ctx* c, const DenSrc& ds, double nel, const real* vext, real* v_out) {
     if (!ds.src) return fail(c, OFDFT_EINVAL, "null argument");
     if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
+    if (int rc = hc_refuse_staged(c)) return rc;       // (the single-GPU entries hand those kinds to hc_evaluate before they get here)
     if ((c->mask & OFDFT_ION_ELECTRON) && !vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
     if (!(c->fast && c->n2 / 2 <= 512)) return fail(c, OFDFT_EINVAL, "staged path needs the power-of-two fast path");
     if (gga_needs_laplacian(c) && !c->gga_split)

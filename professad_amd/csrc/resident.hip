@@ -663,7 +663,8 @@ bool resident_serves(const ofdft_ctx* c) {
     if ((c->mask & kGgaAny) && (gga_needs_laplacian(c) || (c->n0 > 32 && sizeof(real) == 8))) return false;      // (64^3 fp64 with a GGA term: five phases of
                                                                                           //  4096-point planes per workgroup measured slower than the graph replay, 0.160 vs 0.153 ms; fp32: 0.118 vs 0.150)
     if (wts_active(c)) return false;
-    if (c->mask & OFDFT_NLK) return false;        // (the tabulated kernels live in device memory: the staged path serves them)
+    if ((c->mask & OFDFT_NLK) || c->hc_inner) return false;        // (the tabulated kernels live in device memory: the staged path serves them;
+                                                                   //  hc_inner: the rest of a Huang-Carter term set, engine_hc.inc.h)
     return c->mask != 0;
 }
 

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import hc_kernel
 
 
 def _ptr(t):
@@ -47,6 +48,7 @@ class Engine:
         self._box_key = None
         self._terms_key = None
         self._terms_memo = {}
+        self._nlk_table_key = None
         self.npts = int(np.prod(self.shape))
         self._dev_index = idx
         self._dev_exact = torch.device('cuda', idx)
@@ -110,7 +112,9 @@ class Engine:
     def set_terms(self, names, params=None):
         """names: iterable of keys of _native.TERM_BITS; params: dict slot->value
         (wt_alpha, wt_beta, wgc_alpha, wgc_beta, wgc_gamma, wgc_kappa, ggak_kind, ggak_mu, ggak_beta, ggak_lambda, ggak_sigma, vwgtf_kind,
-        wts_kind, nlk_kind, nlk_p0, nlk_p1, nlk_p2)."""
+        wts_kind, nlk_kind, nlk_p0, nlk_p1, nlk_p2, nlk_p3).  For nlk_kind 4 / 5 (HuangCarter: nlk_p0..2 = lambda, beta, kappa;
+        RevisedHuangCarter: nlk_p0..3 = a, b, beta, kappa) the kernel table of hc_kernel.solve_kernel(beta, nlk_eta_max, nlk_n_eta)
+        goes to the library with the call; the two table arguments are keys of ``params`` too (defaults 50, 10000)."""
         memo = None
         if isinstance(names, tuple) and (params is None or isinstance(params, tuple)):      # hashable call (the drop-in terms): memoised
             memo = (names, params)
@@ -121,17 +125,20 @@ class Engine:
                     self._check(self.lib.ofdft_set_terms(self._ctx, key[0], vals.ctypes.data_as(C.POINTER(C.c_double)), len(vals)),
                                 'ofdft_set_terms')
                     self._terms_key = key
+                self._hc_table(key[1], self._terms_memo[(memo, 'table')])
                 return self
             params = dict(params) if params else None
         mask = 0
         for nm in names:
             mask |= N.TERM_BITS[nm]
         slots = ['wt_alpha', 'wt_beta', 'wgc_alpha', 'wgc_beta', 'wgc_gamma', 'wgc_kappa', 'ggak_kind', 'ggak_mu', 'ggak_beta',
-                 'ggak_lambda', 'ggak_sigma', 'vwgtf_kind', 'wts_kind', 'nlk_kind', 'nlk_p0', 'nlk_p1', 'nlk_p2']
+                 'ggak_lambda', 'ggak_sigma', 'vwgtf_kind', 'wts_kind', 'nlk_kind', 'nlk_p0', 'nlk_p1', 'nlk_p2', 'nlk_p3']
         s5 = np.sqrt(5.0)
-        vals = np.array([5 / 6, 5 / 6, (5 + s5) / 6, (5 - s5) / 6, 2.7, 1.0, 0.0, 40 / 27, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+        vals = np.array([5 / 6, 5 / 6, (5 + s5) / 6, (5 - s5) / 6, 2.7, 1.0, 0.0, 40 / 27, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0],
                         dtype=np.float64)
-        for k, v in (params or {}).items():
+        params = dict(params or {})
+        table = (float(params.pop('nlk_eta_max', 50.0)), int(params.pop('nlk_n_eta', 10000)))
+        for k, v in params.items():
             vals[slots.index(k)] = float(v)
         key = (mask, vals.tobytes())
         if key != self._terms_key:
@@ -140,6 +147,43 @@ class Engine:
             self._terms_key = key
         if memo is not None:
             self._terms_memo[memo] = key
+            self._terms_memo[(memo, 'table')] = table
+        self._hc_table(key[1], table)
+        return self
+
+    def _hc_table(self, vals_bytes, table):
+        """the Huang-Carter kernel table of the term set just selected goes to the library, once per (beta, eta_max, n_eta)"""
+        vals = np.frombuffer(vals_bytes, dtype=np.float64)
+        kind = int(vals[N.P_NLK_KIND])
+        if kind not in (N.NLK_HC, N.NLK_REVHC) or not (self._terms_key[0] & N.TERM_BITS['nlk']):
+            return
+        beta = float(vals[N.P_NLK_P1 if kind == N.NLK_HC else N.P_NLK_P2])
+        if self._nlk_table_key == ('custom', beta):       # the caller's own table for this beta (set_nlk_table) stays
+            return
+        tkey = (beta,) + tuple(table)
+        if tkey != self._nlk_table_key:
+            eta, w = hc_kernel.solve_kernel(*tkey)
+            self.set_nlk_table(eta, w)
+            self._nlk_table_key = tkey
+
+    def set_nlk_table(self, eta, w):
+        """The 1-D kernel table w(eta) of the Huang-Carter kinds (ofdft_set_nlk_table): uniform eta grid from 0, >= 4 nodes.
+        ``set_terms`` calls it by itself with the table of hc_kernel.solve_kernel.  A caller with a table of its own calls it after
+        the ``set_terms`` that selects kind 4 / 5: the table then belongs to that term set's beta and stays through later
+        ``set_terms`` calls (those of the drop-in classes included) until one selects another beta, which brings solve_kernel's
+        table for the new beta back.  Called before such a ``set_terms``, it is replaced by that call."""
+        eta = np.ascontiguousarray(eta, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if eta.ndim != 1 or eta.shape != w.shape:
+            raise ValueError('eta and w must be one-dimensional arrays of one length')
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.ofdft_set_nlk_table(self._ctx, eta.ctypes.data_as(dp), w.ctypes.data_as(dp), len(eta)), 'ofdft_set_nlk_table')
+        self._nlk_table_key = None
+        if self._terms_key is not None and (self._terms_key[0] & N.TERM_BITS['nlk']):
+            vals = np.frombuffer(self._terms_key[1], dtype=np.float64)
+            kind = int(vals[N.P_NLK_KIND])
+            if kind in (N.NLK_HC, N.NLK_REVHC):
+                self._nlk_table_key = ('custom', float(vals[N.P_NLK_P1 if kind == N.NLK_HC else N.P_NLK_P2]))
         return self
 
     def _mask(self):

@@ -493,3 +493,55 @@ def XuWangMa(box_vecs, den, kappa=0):
     """functionals.py:1456-1498: vW + TF + the Taylor-expanded line-integral kernel (two powers of the density, a 2 x 2 kernel
     matrix mixed inside one x pass); ``get_stress`` works on it."""
     return _evaluate(box_vecs, den, ('tf', 'vw', 'nlk'), _nlk_params(N.NLK_XWM, kappa))
+
+
+# ------------------------------------------- nonlocal functionals with a density-dependent kernel (OFDFT_NLK kinds 4 and 5)
+class _HuangCarterBase:
+    """What HuangCarter and RevisedHuangCarter share: the kernel table w(eta) (``.kernel``, [2, N_eta]: eta; w) and the call.
+    The table is the project's own classical Runge-Kutta solution of the reference's initial-value problem
+    (professad_amd.hc_kernel), not xitorch's ``solve_ivp`` -- the two differ by the truncation error of the integrators."""
+
+    def generate_kernel(self, eta_max=50, N_eta=10000):
+        from . import hc_kernel
+        self._table = (float(eta_max), int(N_eta))
+        eta, w = hc_kernel.solve_kernel(self.beta, *self._table)
+        self.kernel = torch.from_numpy(np.stack([eta, w]))
+
+    def _params(self):
+        raise NotImplementedError
+
+    def forward(self, box_vecs, den):
+        if box_vecs.requires_grad:
+            raise NotImplementedError('%s has no stress: the strain derivative of its density-dependent kernel is not built '
+                                      '(differentiate in the density only)' % self.__name__)
+        p = self._params() + (('nlk_eta_max', self._table[0]), ('nlk_n_eta', float(self._table[1])))
+        return _evaluate(box_vecs, den, ('tf', 'vw', 'nlk'), p)
+
+    __call__ = forward
+
+
+class HuangCarter(_HuangCarterBase):
+    """functionals.py:1176-1269: vW + TF + the Huang-Carter term with the single-point density-dependent kernel
+    w(|r - r'|, xi(r)), xi = 2 k_F (1 + lambda |grad n|^2 / n^(8/3)).  ``init_args=(lamb, beta, kappa)``; kappa > 1 is the ratio
+    of the geometric spline nodes in xi.  Differentiable once in ``den``; single GPU, fp64."""
+
+    def __init__(self, init_args):
+        self.lamb, self.beta, self.kappa = (float(x) for x in init_args)
+        self.__name__ = self.__qualname__ = 'HuangCarter'
+        self.generate_kernel()
+
+    def _params(self):
+        return (('nlk_kind', float(N.NLK_HC)), ('nlk_p0', self.lamb), ('nlk_p1', self.beta), ('nlk_p2', self.kappa))
+
+
+class RevisedHuangCarter(_HuangCarterBase):
+    """functionals.py:1272-1365: as HuangCarter with xi = 2 k_F (1 + a s^2 / (1 + b s^2)), s the reduced gradient.
+    ``init_args=(a, b, beta, kappa)``."""
+
+    def __init__(self, init_args):
+        self.a, self.b, self.beta, self.kappa = (float(x) for x in init_args)
+        self.__name__ = self.__qualname__ = 'RevisedHuangCarter'
+        self.generate_kernel()
+
+    def _params(self):
+        return (('nlk_kind', float(N.NLK_REVHC)), ('nlk_p0', self.a), ('nlk_p1', self.b), ('nlk_p2', self.beta), ('nlk_p3', self.kappa))
