@@ -11,19 +11,15 @@ namespace ofdft {
 // Phase and table value are formed once per k-point (k = 0: all three vanish with k_j).
 __global__ void ion_potential_grad_spec_kernel(cplx* __restrict__ out0, cplx* __restrict__ out1, cplx* __restrict__ out2, KGeom kg,
                                                double rx, double ry, double rz, RecpotTable tab, double inv_vol) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
+    for_each_kpoint(kg, [&](const KPoint& p) {
         double sn, cs;
-        sincos(kx * rx + ky * ry + kz * rz, &sn, &cs);
-        const double f = recpot_value(tab, (k2 != 0.0) ? sqrt(k2) : 0.0) * inv_vol;
+        sincos(p.kx * rx + p.ky * ry + p.kz * rz, &sn, &cs);
+        const double f = recpot<0>(tab, (p.k2 != 0.0) ? sqrt(p.k2) : 0.0).v * inv_vol;
         const double re = -f * sn, im = -f * cs;               // -i (cs - i sn) f
-        out0[i] = make_double2(kx * re, kx * im);
-        out1[i] = make_double2(ky * re, ky * im);
-        out2[i] = make_double2(kz * re, kz * im);
-    }
+        out0[p.i] = make_double2(p.kx * re, p.kx * im);
+        out1[p.i] = make_double2(p.ky * re, p.ky * im);
+        out2[p.i] = make_double2(p.kz * re, p.kz * im);
+    });
 }
 
 // sum_k w_k v~(|k|) k_i k_j Re(exp(-i k.R_a) conj(n^_k)) for every ion a: xx, yy, zz, xy, xz, yz.  grid = (k chunks, ions);
@@ -34,24 +30,14 @@ __global__ __launch_bounds__(kRedThreads) void ion_curvature_kernel(const cplx* 
     const int a = blockIdx.y;
     const double rx = cart[3 * a], ry = cart[3 * a + 1], rz = cart[3 * a + 2];
     double acc[kIonCurvScalars] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = (z == 0 || ((kg.g.n2 & 1) == 0 && z == kg.g.n2 / 2)) ? 1.0 : 2.0;
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z);
         double sn, cs;
-        sincos(kx * rx + ky * ry + kz * rz, &sn, &cs);
-        const cplx n = nk[i];
-        const double f = w * recpot_value(tab, sqrt(k2)) * (cs * n.x - sn * n.y);
-        acc[0] += f * kx * kx;
-        acc[1] += f * ky * ky;
-        acc[2] += f * kz * kz;
-        acc[3] += f * kx * ky;
-        acc[4] += f * kx * kz;
-        acc[5] += f * ky * kz;
-    }
+        sincos(p.kx * rx + p.ky * ry + p.kz * rz, &sn, &cs);
+        const cplx n = nk[p.i];
+        add_k2(acc, w * recpot<0>(tab, sqrt(p.k2)).v * (cs * n.x - sn * n.y), p.kx, p.ky, p.kz);
+    });
     block_reduce_store<kIonCurvScalars>(acc, partial + (long long)a * gridDim.x * kIonCurvScalars);
 }
 
@@ -72,20 +58,15 @@ __global__ __launch_bounds__(kRedThreads) void ion_ion_hessian_kernel(const doub
     const double inv_rd = 1.0 / g.Rd, two_over = 2.0 / (sqrt(kPi) * g.Rd);
     double acc[kIonHessScalars] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int s2 = (int)(t % w2) - g.nmax[2];
-        const long long u = t / w2;
-        const int s1 = (int)(u % w1) - g.nmax[1];
-        const int s0 = (int)(u / w1) - g.nmax[0];
+        int s0, s1, s2;
+        lattice_shift(g, t, s0, s1, s2);
         const double dx = xb + s0 * g.box[0] + s1 * g.box[3] + s2 * g.box[6];
         const double dy = yb + s0 * g.box[1] + s1 * g.box[4] + s2 * g.box[7];
         const double dz = zb + s0 * g.box[2] + s1 * g.box[5] + s2 * g.box[8];
         const double r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 > 1e-24 && r2 <= g.Rc * g.Rc) {
-            const double r = sqrt(r2), ir = 1.0 / r, ir2 = ir * ir;
-            const double ec = erfc(r * inv_rd) * ir, ge = two_over * exp(-r2 * inv_rd * inv_rd);      // erfc(r/Rd)/r, 2 e^{-r^2/Rd^2}/(sqrt(pi) Rd)
-            const double fpr = -zz * (ge + ec) * ir2;                                                  // f'(r) / r
-            const double fpp = zz * (2.0 * ge * inv_rd * inv_rd + 2.0 * ge * ir2 + 2.0 * ec * ir2);    // f''(r)
-            const double q = (fpp - fpr) * ir2;
+        if (in_cutoff(r2, g)) {
+            double fpr, q;
+            damped_pair_d2(r2, zz, inv_rd, two_over, fpr, q);
             acc[0] += q * dx * dx + fpr;
             acc[1] += q * dy * dy + fpr;
             acc[2] += q * dz * dz + fpr;

@@ -3,6 +3,7 @@
 // src/professad/system.py:183-194).  fp64, gfx950.
 #pragma once
 #include "pointwise_kernels.h"
+#include "kpoint.h"
 
 namespace ofdft {
 
@@ -49,57 +50,16 @@ __global__ __launch_bounds__(256) void pme_spread_kernel(const double* __restric
     }
 }
 
-struct RecpotTable {
-    const double* ks;    // [n] uniform grid from 0
-    const double* y;     // [n] table with the Coulomb tail 4 pi z/k^2 added for k > 0 (ion_utils.py:67-68)
-    const double* m;     // [n] Hermite slopes (functional_tools.py:309-310)
-    int n;
-    double z;
-    double inv_dk;
-};
-
-// interpolate_recpot at |k| (ion_utils.py:74-81; functional_tools.py:311-334)
-__device__ __forceinline__ double recpot_value(const RecpotTable& t, double kabs) {
-    const double xs = fmin(kabs, t.ks[t.n - 1]);
-    int idx = (int)ceil(xs * t.inv_dk) - 1;
-    idx = max(0, min(idx, t.n - 2));
-    while (idx > 0 && t.ks[idx] >= xs) --idx;            // searchsorted(x[1:], xs): #entries of x[1:] below xs
-    while (idx < t.n - 2 && t.ks[idx + 1] < xs) ++idx;
-    const double dx = t.ks[idx + 1] - t.ks[idx];
-    const double u = (xs - t.ks[idx]) / dx, u2 = u * u, u3 = u2 * u;
-    const double v = (1.0 - 3.0 * u2 + 2.0 * u3) * t.y[idx] + (u - 2.0 * u2 + u3) * t.m[idx] * dx +
-                     (3.0 * u2 - 2.0 * u3) * t.y[idx + 1] + (-u2 + u3) * t.m[idx + 1] * dx;
-    return (kabs != 0.0) ? v - 4.0 * kPi * t.z / (kabs * kabs) : v;
-}
-
-// F^ = conj(b0 b1 b2 Q^) v~(|k|) / vol  (PME, ion_utils.py:275-286,118) -- or, with cart != nullptr, the exact
-// structure factor sum_i exp(-i k.r_i) (ion_utils.py:121-137)
+// F^ = S v~(|k|) / vol with the PME structure factor (ion_utils.py:118) or, with cart != nullptr, the exact one
 __global__ void ion_potential_spec_kernel(const cplx* __restrict__ Qk, cplx* __restrict__ out, KGeom kg,
                                           const cplx* __restrict__ b0, const cplx* __restrict__ b1,
                                           const cplx* __restrict__ b2, const double* __restrict__ cart, int nion,
                                           RecpotTable tab, double inv_vol) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        cplx S;
-        if (cart) {
-            double sr = 0.0, si = 0.0;
-            for (int a = 0; a < nion; ++a) {
-                double sn, cs;
-                sincos(kx * cart[3 * a] + ky * cart[3 * a + 1] + kz * cart[3 * a + 2], &sn, &cs);
-                sr += cs;
-                si -= sn;
-            }
-            S = make_double2(sr, si);
-        } else {
-            const cplx b = cmul(cmul(b0[x], b1[y]), b2[z]);
-            S = cconj(cmul(b, Qk[i]));
-        }
-        const double f = recpot_value(tab, (k2 != 0.0) ? sqrt(k2) : 0.0) * inv_vol;
-        out[i] = make_double2(S.x * f, S.y * f);
-    }
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        const cplx S = cart ? structure_factor(cart, nion, p.kx, p.ky, p.kz) : pme_structure_factor(b0, b1, b2, Qk, p);
+        const double f = recpot<0>(tab, (p.k2 != 0.0) ? sqrt(p.k2) : 0.0).v * inv_vol;
+        out[p.i] = make_double2(S.x * f, S.y * f);
+    });
 }
 
 }  // namespace ofdft
@@ -107,62 +67,37 @@ __global__ void ion_potential_spec_kernel(const cplx* __restrict__ Qk, cplx* __r
 namespace ofdft {
 
 // Exact-structure-factor ion-electron forces: F_a = (dV/vol) sum_k w_k v~(k) k (cos(k.R) Im n^ + sin(k.R) Re n^)
-// (= -d/dR_a of dV sum_r n v_ext; reference system.py:913-923 by autograd).  grid = (k chunks, ions).
+// (= -d/dR_a of dV sum_r n v_ext; reference system.py:913-923 by autograd).  grid = (k chunks, ions);
+// partial[(a * gridDim.x + blockIdx.x) * 3 + c].
 __global__ __launch_bounds__(kRedThreads) void ion_force_exact_kernel(const cplx* __restrict__ nk, KGeom kg,
                                                                       const double* __restrict__ cart, RecpotTable tab,
                                                                       double* __restrict__ partial) {
     const int a = blockIdx.y;
     const double rx = cart[3 * a], ry = cart[3 * a + 1], rz = cart[3 * a + 2];
     double acc[3] = {0.0, 0.0, 0.0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = (z == 0 || ((kg.g.n2 & 1) == 0 && z == kg.g.n2 / 2)) ? 1.0 : 2.0;
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z);
         double sn, cs;
-        sincos(kx * rx + ky * ry + kz * rz, &sn, &cs);
-        const cplx n = nk[i];
-        const double f = w * recpot_value(tab, sqrt(k2)) * (cs * n.y + sn * n.x);
-        acc[0] += kx * f;
-        acc[1] += ky * f;
-        acc[2] += kz * f;
-    }
-    // partial[(a * gridDim.x + blockIdx.x) * 3 + c]
-    __shared__ double red[kRedThreads / 64][3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        double v = acc[s];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        acc[s] = v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int s = 0; s < 3; ++s) red[threadIdx.x >> 6][s] = acc[s];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int s = 0; s < 3; ++s) {
-            double t = 0.0;
-            for (int w = 0; w < kRedThreads / 64; ++w) t += red[w][s];
-            partial[((long long)a * gridDim.x + blockIdx.x) * 3 + s] = t;
-        }
+        sincos(p.kx * rx + p.ky * ry + p.kz * rz, &sn, &cs);
+        const cplx n = nk[p.i];
+        const double f = w * recpot<0>(tab, sqrt(p.k2)).v * (cs * n.y + sn * n.x);
+        acc[0] += p.kx * f;
+        acc[1] += p.ky * f;
+        acc[2] += p.kz * f;
+    });
+    block_reduce_store<3>(acc, partial + (long long)a * gridDim.x * 3);
 }
 
 // theta^ = v~(k) conj(b(k) n^(k)) / vol  (the adjoint of the PME potential build applied to the density)
 __global__ void pme_theta_spec_kernel(const cplx* __restrict__ nk, cplx* __restrict__ out, KGeom kg,
                                       const cplx* __restrict__ b0, const cplx* __restrict__ b1,
                                       const cplx* __restrict__ b2, RecpotTable tab, double inv_vol) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        const cplx b = cmul(cmul(b0[x], b1[y]), b2[z]);
-        const cplx s = cconj(cmul(b, nk[i]));
-        const double f = recpot_value(tab, (k2 != 0.0) ? sqrt(k2) : 0.0) * inv_vol;
-        out[i] = make_double2(s.x * f, s.y * f);
-    }
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        const cplx s = pme_structure_factor(b0, b1, b2, nk, p);
+        const double f = recpot<0>(tab, (p.k2 != 0.0) ? sqrt(p.k2) : 0.0).v * inv_vol;
+        out[p.i] = make_double2(s.x * f, s.y * f);
+    });
 }
 
 // G[a][d] = sum over the ion's B-spline stencil of theta(l) * d/du_d (M0 M1 M2); one workgroup per ion
@@ -235,6 +170,24 @@ struct IonIonGeom {
     int nmax[3];         // shifts -nmax..nmax per axis
     double Rc, Rd;
 };
+// lattice shift number u (s2 fastest) -> its three components, each in -nmax..nmax
+__device__ __forceinline__ void lattice_shift(const IonIonGeom& g, long long u, int& s0, int& s1, int& s2) {
+    const int w1 = 2 * g.nmax[1] + 1, w2 = 2 * g.nmax[2] + 1;
+    s2 = (int)(u % w2) - g.nmax[2];
+    u /= w2;
+    s1 = (int)(u % w1) - g.nmax[1];
+    s0 = (int)(u / w1) - g.nmax[0];
+}
+// a pair counts at 0 < r <= Rc (r = 0: an ion and itself in the home cell)
+__device__ __forceinline__ bool in_cutoff(double r2, const IonIonGeom& g) { return r2 > 1e-24 && r2 <= g.Rc * g.Rc; }
+// f(r) = zz erfc(r/Rd)/r at r^2 = r2:  fpr = f'/r,  q = (f'' - f'/r) / r^2;  inv_rd = 1/Rd, two_over = 2 / (sqrt(pi) Rd)
+__device__ __forceinline__ void damped_pair_d2(double r2, double zz, double inv_rd, double two_over, double& fpr, double& q) {
+    const double r = sqrt(r2), ir = 1.0 / r, ir2 = ir * ir;
+    const double ec = erfc(r * inv_rd) * ir, ge = two_over * exp(-r2 * inv_rd * inv_rd);      // erfc(r/Rd)/r, 2 e^{-r^2/Rd^2}/(sqrt(pi) Rd)
+    fpr = -zz * (ge + ec) * ir2;                                                               // f'(r) / r
+    const double fpp = zz * (2.0 * ge * inv_rd * inv_rd + 2.0 * ge * ir2 + 2.0 * ec * ir2);    // f''(r)
+    q = (fpp - fpr) * ir2;
+}
 __global__ __launch_bounds__(kRedThreads) void ion_ion_kernel(const double* __restrict__ cart, const double* __restrict__ Z,
                                                               int nion, IonIonGeom g, double* __restrict__ partial) {
     const int i = blockIdx.y;
@@ -247,16 +200,13 @@ __global__ __launch_bounds__(kRedThreads) void ion_ion_kernel(const double* __re
     for (int s = 0; s < kIonIonScalars; ++s) acc[s] = 0.0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(t % nion);
-        long long u = t / nion;
-        const int s2 = (int)(u % w2) - g.nmax[2];
-        u /= w2;
-        const int s1 = (int)(u % w1) - g.nmax[1];
-        const int s0 = (int)(u / w1) - g.nmax[0];
+        int s0, s1, s2;
+        lattice_shift(g, t / nion, s0, s1, s2);
         const double dx = cart[3 * j] + s0 * g.box[0] + s1 * g.box[3] + s2 * g.box[6] - xi;
         const double dy = cart[3 * j + 1] + s0 * g.box[1] + s1 * g.box[4] + s2 * g.box[7] - yi;
         const double dz = cart[3 * j + 2] + s0 * g.box[2] + s1 * g.box[5] + s2 * g.box[8] - zi;
         const double r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 > 1e-24 && r2 <= g.Rc * g.Rc) {
+        if (in_cutoff(r2, g)) {
             const double r = sqrt(r2), ir = 1.0 / r, zz = Zi * Z[j];
             const double ec = erfc(r * inv_rd) * ir;
             acc[0] += zz * ec;

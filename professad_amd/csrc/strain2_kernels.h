@@ -31,35 +31,6 @@ namespace ofdft {
 constexpr int kStrain2Scalars = 23;      // 15 quartic + 6 quadratic + c0a + c0b
 static_assert(kStrain2Scalars <= kMaxScalars, "a row of c->d_partial holds kMaxScalars doubles");
 
-// acc[0..14] += f k_a k_b k_c k_d over the sorted quadruples xxxx xxxy xxxz xxyy xxyz xxzz xyyy xyyz xyzz xzzz yyyy yyyz yyzz yzzz zzzz
-__device__ __forceinline__ void add_k4(double* acc, double f, double x, double y, double z) {
-    const double xx = f * x * x, xy = f * x * y, xz = f * x * z, yy = f * y * y, yz = f * y * z, zz = f * z * z;
-    acc[0] += xx * x * x;
-    acc[1] += xx * x * y;
-    acc[2] += xx * x * z;
-    acc[3] += xx * y * y;
-    acc[4] += xx * y * z;
-    acc[5] += xx * z * z;
-    acc[6] += xy * y * y;
-    acc[7] += xy * y * z;
-    acc[8] += xy * z * z;
-    acc[9] += xz * z * z;
-    acc[10] += yy * y * y;
-    acc[11] += yy * y * z;
-    acc[12] += yy * z * z;
-    acc[13] += yz * z * z;
-    acc[14] += zz * z * z;
-}
-// acc[0..5] += f k_a k_b: xx, yy, zz, xy, xz, yz
-__device__ __forceinline__ void add_k2(double* acc, double f, double x, double y, double z) {
-    acc[0] += f * x * x;
-    acc[1] += f * y * y;
-    acc[2] += f * z * z;
-    acc[3] += f * x * y;
-    acc[4] += f * x * z;
-    acc[5] += f * y * z;
-}
-
 // F = 1/G - 3 eta^2 - 1 of the Lindhard response G (functionals.py:617-628,648) with P = eta F' and Q = eta^2 F''.
 // eta >= 3: with z = eta^-2 and c_j = 1 / (4 j^2 - 1), G = z R, R = sum_{j>=0} c_(j+1) z^j, V = sum_{j>=0} c_(j+2) z^j, F = -3 u - 1,
 // u = V / R (lindhard_shape's series); eta d/d eta = -2 z d/dz gives P = 6 z u', Q = -18 z u' - 12 z^2 u'': 18 terms (tail 9^-18),
@@ -115,63 +86,30 @@ __global__ __launch_bounds__(kRedThreads) void strain2_spec_kernel(const cplx* _
     double acc[kStrain2Scalars];
 #pragma unroll
     for (int s = 0; s < kStrain2Scalars; ++s) acc[s] = 0.0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = half_weight(kg.g, z) * scale;
-        const cplx av = a[i];
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z) * scale;
+        const cplx av = a[p.i];
         if (OP == STRAIN2_HARTREE) {
-            const double is = 1.0 / k2, X = w * 4.0 * kPi * (av.x * av.x + av.y * av.y) * is;
-            add_k4(acc, 8.0 * X * is * is, kx, ky, kz);
-            add_k2(acc + 15, -2.0 * X * is, kx, ky, kz);
+            const double is = 1.0 / p.k2, X = w * 4.0 * kPi * (av.x * av.x + av.y * av.y) * is;
+            add_k4(acc, 8.0 * X * is * is, p.kx, p.ky, p.kz);
+            add_k2(acc + 15, -2.0 * X * is, p.kx, p.ky, p.kz);
             acc[21] += 2.0 * X;
             acc[22] -= X;
         } else if (OP == STRAIN2_VW) {
-            add_k2(acc + 15, 2.0 * w * (av.x * av.x + av.y * av.y), kx, ky, kz);
+            add_k2(acc + 15, 2.0 * w * (av.x * av.x + av.y * av.y), p.kx, p.ky, p.kz);
         } else {
-            const cplx bv = b[i];
-            const double X = w * (av.x * bv.x + av.y * bv.y), is = 1.0 / k2;
+            const cplx bv = b[p.i];
+            const double X = w * (av.x * bv.x + av.y * bv.y), is = 1.0 / p.k2;
             double F, P, Q;
-            lindhard_shape_d2(sqrt(k2) * inv2kf, F, P, Q);
-            add_k4(acc, X * (Q - P) * is * is, kx, ky, kz);
-            add_k2(acc + 15, X * P * is, kx, ky, kz);
+            lindhard_shape_d2(sqrt(p.k2) * inv2kf, F, P, Q);
+            add_k4(acc, X * (Q - P) * is * is, p.kx, p.ky, p.kz);
+            add_k2(acc + 15, X * P * is, p.kx, p.ky, p.kz);
             acc[21] += X * (10.0 / 9.0 * F - 2.0 / 3.0 * P + Q / 9.0);
             acc[22] += X * (-2.0 / 3.0 * F + P / 3.0);
         }
-    }
+    });
     block_reduce_store<kStrain2Scalars>(acc, partial);
-}
-
-// interpolate_recpot with its first and second derivative in |k|: the cubic Hermite interpolant inside an interval, zero slope
-// and curvature beyond the table end (torch.minimum clamp), the Coulomb tail -4 pi z / k^2 taken off (the interval search and
-// the first two results are those of recpot_value_d, stress_kernels.h, restated so that the stress kernels stay as they are)
-__device__ __forceinline__ double recpot_value_d2(const RecpotTable& t, double kabs, double& dv, double& d2v) {
-    const double xs = fmin(kabs, t.ks[t.n - 1]);
-    int idx = (int)ceil(xs * t.inv_dk) - 1;
-    idx = max(0, min(idx, t.n - 2));
-    while (idx > 0 && t.ks[idx] >= xs) --idx;
-    while (idx < t.n - 2 && t.ks[idx + 1] < xs) ++idx;
-    const double dx = t.ks[idx + 1] - t.ks[idx];
-    const double u = (xs - t.ks[idx]) / dx, u2 = u * u, u3 = u2 * u;
-    const double y0 = t.y[idx], y1 = t.y[idx + 1], m0 = t.m[idx] * dx, m1 = t.m[idx + 1] * dx;
-    const double v = (1.0 - 3.0 * u2 + 2.0 * u3) * y0 + (u - 2.0 * u2 + u3) * m0 + (3.0 * u2 - 2.0 * u3) * y1 + (-u2 + u3) * m1;
-    const double d = ((6.0 * u2 - 6.0 * u) * y0 + (3.0 * u2 - 4.0 * u + 1.0) * m0 + (-6.0 * u2 + 6.0 * u) * y1 + (3.0 * u2 - 2.0 * u) * m1) / dx;
-    const double d2 = ((12.0 * u - 6.0) * y0 + (6.0 * u - 4.0) * m0 + (-12.0 * u + 6.0) * y1 + (6.0 * u - 2.0) * m1) / (dx * dx);
-    const bool inside = kabs < t.ks[t.n - 1];
-    dv = inside ? d : 0.0;
-    d2v = inside ? d2 : 0.0;
-    if (kabs != 0.0) {
-        const double ik2 = 1.0 / (kabs * kabs);
-        dv += 8.0 * kPi * t.z * ik2 / kabs;
-        d2v -= 24.0 * kPi * t.z * ik2 * ik2;
-        return v - 4.0 * kPi * t.z * ik2;
-    }
-    dv = 0.0;
-    d2v = 0.0;
-    return v;
 }
 
 // ion-electron, exact structure factor: X = w Re(S_k conj(n^_k)), nk unnormalised; k = 0 contributes to c0a, c0b only
@@ -180,31 +118,19 @@ __global__ __launch_bounds__(kRedThreads) void strain2_ion_kernel(const cplx* __
     double acc[kStrain2Scalars];
 #pragma unroll
     for (int s = 0; s < kStrain2Scalars; ++s) acc[s] = 0.0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        double sr = 0.0, si = 0.0;
-        for (int a = 0; a < nion; ++a) {
-            double sn, cs;
-            sincos(kx * cart[3 * a] + ky * cart[3 * a + 1] + kz * cart[3 * a + 2], &sn, &cs);
-            sr += cs;
-            si -= sn;
-        }
-        const cplx n = nk[i];
-        const double X = half_weight(kg.g, z) * (sr * n.x + si * n.y);
-        const double kabs = (k2 != 0.0) ? sqrt(k2) : 0.0;
-        double dv, d2v;
-        const double v = recpot_value_d2(tab, kabs, dv, d2v);
-        acc[21] += 2.0 * X * v;
-        acc[22] -= X * v;
-        if (k2 != 0.0) {
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        const cplx S = structure_factor(cart, nion, p.kx, p.ky, p.kz), n = nk[p.i];
+        const double X = half_weight(kg.g, p.z) * (S.x * n.x + S.y * n.y);
+        const double kabs = (p.k2 != 0.0) ? sqrt(p.k2) : 0.0;
+        const RecpotValue t = recpot<2>(tab, kabs);
+        acc[21] += 2.0 * X * t.v;
+        acc[22] -= X * t.v;
+        if (p.k2 != 0.0) {
             const double ik = 1.0 / kabs;
-            add_k4(acc, X * (d2v - dv * ik) / k2, kx, ky, kz);
-            add_k2(acc + 15, X * dv * ik, kx, ky, kz);
+            add_k4(acc, X * (t.d2v - t.dv * ik) / p.k2, p.kx, p.ky, p.kz);
+            add_k2(acc + 15, X * t.dv * ik, p.kx, p.ky, p.kz);
         }
-    }
+    });
     block_reduce_store<kStrain2Scalars>(acc, partial);
 }
 
@@ -239,13 +165,10 @@ struct StrainGradSpecArgs {
 };
 // spectral: k, eta, F and P once per k-point; six spectra per active family
 static __global__ void strain_grad_spec_kernel(StrainGradSpecArgs a) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(a.kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(a.kg, x, y, z, kx, ky, kz, k2);
-        const double is = (k2 != 0.0) ? 1.0 / k2 : 0.0;
-        const double kk[6] = {kx * kx, ky * ky, kz * kz, ky * kz, kx * kz, kx * ky};
+    for_each_kpoint(a.kg, [&](const KPoint& p) {
+        const long long i = p.i;
+        const double is = (p.k2 != 0.0) ? 1.0 / p.k2 : 0.0;
+        const double kk[6] = {p.kx * p.kx, p.ky * p.ky, p.kz * p.kz, p.ky * p.kz, p.kx * p.kz, p.kx * p.ky};
         if (a.flags & SG_HARTREE) {
             const cplx v = a.in[0][i];
             const double f = 8.0 * kPi * is * is;
@@ -259,24 +182,20 @@ static __global__ void strain_grad_spec_kernel(StrainGradSpecArgs a) {
         }
         if (a.flags & SG_WT) {
             double F = 0.0, P = 0.0, Q = 0.0;
-            if (k2 != 0.0) lindhard_shape_d2(sqrt(k2) * a.inv2kf, F, P, Q);      // (Q is unused here: inlined, its arithmetic is dead code)
-            const double iso = (k2 != 0.0) ? a.pref * (a.q * F + P / 3.0) : 0.0, an = -a.pref * P * is;
+            if (p.k2 != 0.0) lindhard_shape_d2(sqrt(p.k2) * a.inv2kf, F, P, Q);      // (Q is unused here: inlined, its arithmetic is dead code)
+            const double iso = (p.k2 != 0.0) ? a.pref * (a.q * F + P / 3.0) : 0.0, an = -a.pref * P * is;
+            double f[6];
+            voigt6(an, iso, p, f);
             const cplx v = a.in[2][i];
 #pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                const double f = an * kk[c] + (c < 3 ? iso : 0.0);
-                a.out[12 + c][i] = make_double2(v.x * f, v.y * f);
-            }
+            for (int c = 0; c < 6; ++c) a.out[12 + c][i] = make_double2(v.x * f[c], v.y * f[c]);
             if (a.flags & SG_WT2) {
                 const cplx u = a.in[3][i];
 #pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    const double f = an * kk[c] + (c < 3 ? iso : 0.0);
-                    a.out[18 + c][i] = make_double2(u.x * f, u.y * f);
-                }
+                for (int c = 0; c < 6; ++c) a.out[18 + c][i] = make_double2(u.x * f[c], u.y * f[c]);
             }
         }
-    }
+    });
 }
 
 struct StrainGradCombineArgs {
@@ -294,7 +213,8 @@ static __global__ void strain_grad_combine_kernel(StrainGradCombineArgs a) {
         double cvw = 0.0, cb = 0.0, ca = 0.0;
         if (a.flags & SG_VW) cvw = -1.0 / sqrt(d);
         if (a.flags & SG_WT) {
-            const double ctf = 0.3 * 9.570780000627306053141655531512398907;      // 0.3 (3 pi^2)^(2/3)
+            // 0.3 (3 pi^2)^(2/3) as a product of doubles: one ulp below kCtf (the rounded long-double product), so it stays
+            const double ctf = 0.3 * 9.570780000627306053141655531512398907;
             cb = ctf * a.al * pow(d, a.al - 1.0);
             ca = ctf * a.be * pow(d, a.be - 1.0);
             if (!(a.flags & SG_WT2)) cb += ca;                                    // alpha = beta: one convolution counts twice
@@ -316,29 +236,16 @@ static __global__ void strain_grad_combine_kernel(StrainGradCombineArgs a) {
 struct IonStrainGradOut { cplx* s[6]; };
 static __global__ void ion_strain_grad_spec_kernel(IonStrainGradOut out, KGeom kg, const double* __restrict__ cart, int nion, RecpotTable tab,
                                                    double inv_vol) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        double sr = 0.0, si = 0.0;
-        for (int a = 0; a < nion; ++a) {
-            double sn, cs;
-            sincos(kx * cart[3 * a] + ky * cart[3 * a + 1] + kz * cart[3 * a + 2], &sn, &cs);
-            sr += cs;
-            si -= sn;
-        }
-        const double kabs = (k2 != 0.0) ? sqrt(k2) : 0.0;
-        double dv;
-        const double v = recpot_value_d(tab, kabs, dv);
-        const double an = (k2 != 0.0) ? -dv / kabs * inv_vol : 0.0, iso = -v * inv_vol;
-        const double kk[6] = {kx * kx, ky * ky, kz * kz, ky * kz, kx * kz, kx * ky};
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        const cplx S = structure_factor(cart, nion, p.kx, p.ky, p.kz);
+        const double kabs = (p.k2 != 0.0) ? sqrt(p.k2) : 0.0;
+        const RecpotValue t = recpot<1>(tab, kabs);
+        const double an = (p.k2 != 0.0) ? -t.dv / kabs * inv_vol : 0.0, iso = -t.v * inv_vol;
+        double f[6];
+        voigt6(an, iso, p, f);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            const double f = an * kk[c] + (c < 3 ? iso : 0.0);
-            out.s[c][i] = make_double2(sr * f, si * f);
-        }
-    }
+        for (int c = 0; c < 6; ++c) out.s[c][p.i] = make_double2(S.x * f[c], S.y * f[c]);
+    });
 }
 
 // Pair sum of the ion-ion energy, the geometry and pair set of ion_ion_kernel (0 < r <= Rc at the unstrained cell, Rd and Rc
@@ -357,21 +264,16 @@ __global__ __launch_bounds__(kRedThreads) void ion_ion_strain2_kernel(const doub
     for (int s = 0; s < kIonStrain2Scalars; ++s) acc[s] = 0.0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(t % nion);
-        long long u = t / nion;
-        const int s2 = (int)(u % w2) - g.nmax[2];
-        u /= w2;
-        const int s1 = (int)(u % w1) - g.nmax[1];
-        const int s0 = (int)(u / w1) - g.nmax[0];
+        int s0, s1, s2;
+        lattice_shift(g, t / nion, s0, s1, s2);
         const double dx = cart[3 * j] + s0 * g.box[0] + s1 * g.box[3] + s2 * g.box[6] - xi;
         const double dy = cart[3 * j + 1] + s0 * g.box[1] + s1 * g.box[4] + s2 * g.box[7] - yi;
         const double dz = cart[3 * j + 2] + s0 * g.box[2] + s1 * g.box[5] + s2 * g.box[8] - zi;
         const double r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 > 1e-24 && r2 <= g.Rc * g.Rc) {
-            const double r = sqrt(r2), ir = 1.0 / r, ir2 = ir * ir, zz = Zi * Z[j];
-            const double ec = erfc(r * inv_rd) * ir, ge = two_over * exp(-r2 * inv_rd * inv_rd);      // erfc(r/Rd)/r, 2 e^{-r^2/Rd^2}/(sqrt(pi) Rd)
-            const double fpr = -zz * (ge + ec) * ir2;                                                  // f'(r) / r
-            const double fpp = zz * (2.0 * ge * inv_rd * inv_rd + 2.0 * ge * ir2 + 2.0 * ec * ir2);    // f''(r)
-            add_k4(acc, (fpp - fpr) * ir2, dx, dy, dz);
+        if (in_cutoff(r2, g)) {
+            double fpr, q;
+            damped_pair_d2(r2, Zi * Z[j], inv_rd, two_over, fpr, q);
+            add_k4(acc, q, dx, dy, dz);
             add_k2(acc + 15, fpr, dx, dy, dz);
             acc[21] += Z[j];
         }

@@ -11,19 +11,6 @@ namespace ofdft {
 constexpr int kStressSpecScalars = 7;
 constexpr int kStressRealScalars = 28;
 
-__device__ __forceinline__ double half_weight(const SpecGeom& g, int z) {
-    return (z == 0 || ((g.n2 & 1) == 0 && z == g.n2 / 2)) ? 1.0 : 2.0;
-}
-
-__device__ __forceinline__ void add_kk(double (&acc)[kStressSpecScalars], double f, double kx, double ky, double kz) {
-    acc[0] += f * kx * kx;
-    acc[1] += f * ky * ky;
-    acc[2] += f * kz * kz;
-    acc[3] += f * kx * ky;
-    acc[4] += f * kx * kz;
-    acc[5] += f * ky * kz;
-}
-
 enum { STRESS_HARTREE = 0, STRESS_VW = 1, STRESS_WT = 2, STRESS_HESS = 3 };
 
 // a, b: UNNORMALISED spectra (b only for WT); scale = 1/N^2.
@@ -36,39 +23,35 @@ __global__ __launch_bounds__(kRedThreads) void stress_spec_kernel(const cplx* __
                                                                   KGeom kg, double scale, double inv2kf,
                                                                   double* __restrict__ partial) {
     double acc[kStressSpecScalars] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = half_weight(kg.g, z) * scale;
-        const cplx av = a[i];
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z) * scale;
+        const cplx av = a[p.i];
         if (OP == STRESS_HARTREE) {
-            const double f = w * 4.0 * kPi * (av.x * av.x + av.y * av.y) / (k2 * k2);
-            add_kk(acc, f, kx, ky, kz);
-            acc[6] += f * k2;
+            const double f = w * 4.0 * kPi * (av.x * av.x + av.y * av.y) / (p.k2 * p.k2);
+            add_k2(acc, f, p.kx, p.ky, p.kz);
+            acc[6] += f * p.k2;
         } else if (OP == STRESS_VW) {
-            add_kk(acc, -w * (av.x * av.x + av.y * av.y), kx, ky, kz);
+            add_k2(acc, -w * (av.x * av.x + av.y * av.y), p.kx, p.ky, p.kz);
         } else if (OP == STRESS_HESS) {
-            const cplx bv = b[i];
-            add_kk(acc, w * (av.x * bv.x + av.y * bv.y), kx, ky, kz);
+            const cplx bv = b[p.i];
+            add_k2(acc, w * (av.x * bv.x + av.y * bv.y), p.kx, p.ky, p.kz);
         } else {
-            const cplx bv = b[i];
+            const cplx bv = b[p.i];
             const double re = w * (av.x * bv.x + av.y * bv.y);
-            const double eta = sqrt(k2) * inv2kf;
+            const double eta = sqrt(p.k2) * inv2kf;
             const double lg = log(fabs((1.0 + eta) / (1.0 - eta)));
             const double lind = 0.5 + (1.0 - eta * eta) / (4.0 * eta) * lg;
             const double aux3 = eta / (lind * lind) * (0.5 / eta - 0.25 * (1.0 + 1.0 / (eta * eta)) * lg) + 6.0 * eta * eta;
-            const double f = re * aux3 / k2;
-            add_kk(acc, f, kx, ky, kz);
+            const double f = re * aux3 / p.k2;
+            add_k2(acc, f, p.kx, p.ky, p.kz);
             const double third = re * aux3 / 3.0;
             acc[0] -= third;
             acc[1] -= third;
             acc[2] -= third;
             acc[6] += re * lindhard_shape(eta);
         }
-    }
+    });
     block_reduce_store<kStressSpecScalars>(acc, partial);
 }
 
@@ -112,15 +95,11 @@ __device__ __forceinline__ void nlk_gap_derivs(double e, double d, double& G, do
 __global__ __launch_bounds__(kRedThreads) void stress_nlk_kernel(const cplx* __restrict__ a, const cplx* __restrict__ b, KGeom kg,
                                                                  double scale, NlkStress t, double* __restrict__ partial) {
     double acc[kStressSpecScalars] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = half_weight(kg.g, z) * scale;
-        const cplx av = a[i], bv = b[i];
-        const double eta = sqrt(k2) * t.inv2kf;
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z) * scale;
+        const cplx av = a[p.i], bv = b[p.i];
+        const double eta = sqrt(p.k2) * t.inv2kf;
         double G, Ge, Gd;
         nlk_gap_derivs(eta, t.kind == NLK_KGAP ? t.delta : 0.0, G, Ge, Gd);
         const double F = 1.0 / G - 3.0 * eta * eta - 1.0, Fe = -Ge / (G * G) - 6.0 * eta;
@@ -138,12 +117,12 @@ __global__ __launch_bounds__(kRedThreads) void stress_nlk_kernel(const cplx* __r
             g = eta * (Xaa * (t.c0 * Fe + t.c1 * He) + Xab * t.c2 * He);
             en = Xaa * (t.c0 * F + t.c1 * H) + Xab * t.c2 * H;
         }
-        add_kk(acc, -g / k2, kx, ky, kz);
+        add_k2(acc, -g / p.k2, p.kx, p.ky, p.kz);
         acc[0] += g / 3.0 + diag;
         acc[1] += g / 3.0 + diag;
         acc[2] += g / 3.0 + diag;
         acc[6] += en;
-    }
+    });
     block_reduce_store<kStressSpecScalars>(acc, partial);
 }
 
@@ -153,14 +132,10 @@ struct WgcSpectra { const cplx* s[6]; };
 __global__ __launch_bounds__(kRedThreads) void stress_wgc_kernel(WgcSpectra sp, KGeom kg, WgcSeries s, double scale,
                                                                  double* __restrict__ partial) {
     double acc[kStressSpecScalars] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        if (k2 == 0.0) continue;
-        const double w = half_weight(kg.g, z) * scale;
-        const double eta = sqrt(k2) * s.inv2kf;
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        if (p.k2 == 0.0) return;
+        const double w = half_weight(kg.g, p.z) * scale;
+        const double eta = sqrt(p.k2) * s.inv2kf;
         double w0, w1, w2, w3;
         wgc_series<true>(eta, s, w0, w1, w2, w3);
         w0 *= s.pref;
@@ -175,41 +150,19 @@ __global__ __launch_bounds__(kRedThreads) void stress_wgc_kernel(WgcSpectra sp, 
         const double common = 2.0 * eta * w2 + eta * eta * w3;
         const double dK2 = (common + (7.0 - s.gamma) * (w1 + eta * w2)) * i36;
         const double dK3 = (common + (1.0 + s.gamma) * (w1 + eta * w2)) * i36;
-        const cplx A = sp.s[0][i], B = sp.s[1][i], C = sp.s[2][i], P = sp.s[3][i], Q = sp.s[4][i], S = sp.s[5][i];
+        const cplx A = sp.s[0][p.i], B = sp.s[1][p.i], C = sp.s[2][p.i], P = sp.s[3][p.i], Q = sp.s[4][p.i], S = sp.s[5][p.i];
         const double X0 = w * (P.x * A.x + P.y * A.y);
         const double X1 = w * (P.x * B.x + P.y * B.y + Q.x * A.x + Q.y * A.y);
         const double X2 = w * (P.x * C.x + P.y * C.y + S.x * A.x + S.y * A.y);
         const double X3 = w * (Q.x * B.x + Q.y * B.y);
         const double G = (w1 * X0 + dK1 * X1 + dK2 * X2 + dK3 * X3) * eta;
-        add_kk(acc, -G / k2, kx, ky, kz);
+        add_k2(acc, -G / p.k2, p.kx, p.ky, p.kz);
         acc[0] += G / 3.0;
         acc[1] += G / 3.0;
         acc[2] += G / 3.0;
         acc[6] += w0 * X0 + K1 * X1 + K2 * X2 + K3 * X3;
-    }
+    });
     block_reduce_store<kStressSpecScalars>(acc, partial);
-}
-
-// interpolate_recpot and its derivative with respect to |k| (zero slope beyond the table end: torch.minimum clamp)
-__device__ __forceinline__ double recpot_value_d(const RecpotTable& t, double kabs, double& dv) {
-    const double xs = fmin(kabs, t.ks[t.n - 1]);
-    int idx = (int)ceil(xs * t.inv_dk) - 1;
-    idx = max(0, min(idx, t.n - 2));
-    while (idx > 0 && t.ks[idx] >= xs) --idx;
-    while (idx < t.n - 2 && t.ks[idx + 1] < xs) ++idx;
-    const double dx = t.ks[idx + 1] - t.ks[idx];
-    const double u = (xs - t.ks[idx]) / dx, u2 = u * u, u3 = u2 * u;
-    const double v = (1.0 - 3.0 * u2 + 2.0 * u3) * t.y[idx] + (u - 2.0 * u2 + u3) * t.m[idx] * dx +
-                     (3.0 * u2 - 2.0 * u3) * t.y[idx + 1] + (-u2 + u3) * t.m[idx + 1] * dx;
-    const double d = ((6.0 * u2 - 6.0 * u) * t.y[idx] + (3.0 * u2 - 4.0 * u + 1.0) * t.m[idx] * dx +
-                      (-6.0 * u2 + 6.0 * u) * t.y[idx + 1] + (3.0 * u2 - 2.0 * u) * t.m[idx + 1] * dx) / dx;
-    dv = (kabs < t.ks[t.n - 1]) ? d : 0.0;
-    if (kabs != 0.0) {
-        dv += 8.0 * kPi * t.z / (kabs * kabs * kabs);
-        return v - 4.0 * kPi * t.z / (kabs * kabs);
-    }
-    dv = 0.0;
-    return v;
 }
 
 // ion-electron: acc_ij += core v~'(k) k_i k_j / |k|,  acc[6] += core v~(k),  core = w Re(S_k conj(n^_k)) (oracle/stress.py)
@@ -220,32 +173,15 @@ __global__ __launch_bounds__(kRedThreads) void stress_ion_kernel(const cplx* __r
                                                                  const double* __restrict__ cart, int nion, RecpotTable tab,
                                                                  double* __restrict__ partial) {
     double acc[kStressSpecScalars] = {0, 0, 0, 0, 0, 0, 0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        int x, y, z;
-        spec_decode(kg.g, i, x, y, z);
-        double kx, ky, kz, k2;
-        kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
-        cplx S;
-        if (cart) {
-            double sr = 0.0, si = 0.0;
-            for (int a = 0; a < nion; ++a) {
-                double sn, cs;
-                sincos(kx * cart[3 * a] + ky * cart[3 * a + 1] + kz * cart[3 * a + 2], &sn, &cs);
-                sr += cs;
-                si -= sn;
-            }
-            S = make_double2(sr, si);
-        } else {
-            S = cconj(cmul(cmul(cmul(b0[x], b1[y]), b2[z]), Qk[i]));
-        }
-        const cplx n = nk[i];
-        const double core = half_weight(kg.g, z) * (S.x * n.x + S.y * n.y);
-        const double kabs = (k2 != 0.0) ? sqrt(k2) : 0.0;
-        double dv;
-        const double v = recpot_value_d(tab, kabs, dv);
-        acc[6] += core * v;
-        if (k2 != 0.0) add_kk(acc, core * dv / kabs, kx, ky, kz);
-    }
+    for_each_kpoint(kg, [&](const KPoint& p) {
+        const cplx S = cart ? structure_factor(cart, nion, p.kx, p.ky, p.kz) : pme_structure_factor(b0, b1, b2, Qk, p);
+        const cplx n = nk[p.i];
+        const double core = half_weight(kg.g, p.z) * (S.x * n.x + S.y * n.y);
+        const double kabs = (p.k2 != 0.0) ? sqrt(p.k2) : 0.0;
+        const RecpotValue t = recpot<1>(tab, kabs);
+        acc[6] += core * t.v;
+        if (p.k2 != 0.0) add_k2(acc, core * t.dv / kabs, p.kx, p.ky, p.kz);
+    });
     block_reduce_store<kStressSpecScalars>(acc, partial);
 }
 

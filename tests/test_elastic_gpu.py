@@ -22,7 +22,7 @@ import elastic_cases as EC
 import elastic_double as ED
 import tn_cases
 from professad_amd import _native as N
-from professad_amd import elastic, ions, optimize
+from professad_amd import elastic, ions, optimize, synth
 from professad_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
@@ -234,6 +234,37 @@ def test_entries_on_other_grids(name):
         assert v <= bound(GRID_DEV[name][t]), t
     assert dv <= bound(FIELD_DEV) and dvi <= bound(DOUBLE_DEV['b']['ion_electron'])
     assert all(np.array_equal(W[t], again[t]) for t in W) and torch.equal(V, V2)
+
+
+def test_table_derivatives_beyond_the_table_end():
+    """the first and second derivative of the table interpolant (csrc/kpoint.h: recpot<1>, recpot<2>) on both sides of the table
+    end, where they change from the Hermite forms to zero slope and curvature plus the Coulomb tail: the (18, 20, 16) triclinic
+    cell of tools/geometry_entries_digest.py with its thinned table (every other point, half the charge) and one species of 2
+    ions.  That table ends at |k| = 30 and the cell's largest |k| is 13.4, so a prefix of 1251 points (|k| <= 7.5) is used: 47 %
+    of the half spectrum lies beyond it and 53 % inside, asserted here.  Against tests/elastic_double.py with the bounds of
+    test_entries_on_other_grids for these two entries; the W2 bound there is per grid, and the smallest of them (17^3, the grid
+    nearest in size) is taken.  Measured on an MI355X: W2 2.56e-13 of max|W2|, the field 1.79e-14 of its maximum."""
+    g = np.load(os.path.join(GOLDEN, 'ions.npz'))
+    full = ions.recpot_table(g['recpot_raw'], float(g['recpot_kmax']))
+    tab = (full[0][::2][:1251], 0.5 * full[1][::2][:1251], 0.5 * full[2])
+    shape = (18, 20, 16)
+    box = g['a_box'][0, 0] * np.array([[1.0, 0.0, 0.0], [0.1, 1.1, 0.0], [0.05, -0.1, 0.9]])
+    rng = np.random.default_rng(17)
+    rng.random((1, 3))
+    frac = rng.random((2, 3)) * 1.5 - 0.25
+    kabs = np.sqrt(ED._half_spectrum(box, shape)[1])
+    beyond, inside = float((kabs > tab[0][-1]).mean()), float((kabs < tab[0][-1]).mean())
+    den = synth.smooth_density(shape, seed=10, n0=0.03, amp=0.5)
+    eng = Engine(shape, DEV).set_cell(box).set_terms(['ion_electron'])
+    W = ions.ion_electron_strain_hessian(eng, box, dev_t(den), [(frac, tab)])
+    V = ions.ionic_potential_strain_gradient(eng, box, [(frac, tab)])
+    eng.close()
+    dw = rel(W, ED.ion_electron(box, den, frac, tab))
+    dv = rel(V.cpu().numpy(), ED.ionic_potential_strain_gradient(box, shape, frac, tab))
+    print('MEASURE elastic table end: beyond %.3f inside %.3f  W2 - double %.2e  ionic field - double %.2e' % (beyond, inside, dw, dv))
+    assert beyond >= 0.25 and inside >= 0.25
+    assert dw <= bound(min(d['ion_electron'] for d in GRID_DEV.values()))
+    assert dv <= bound(DOUBLE_DEV['b']['ion_electron'])
 
 
 @pytest.mark.parametrize('case', EC.CASES)
