@@ -1,10 +1,16 @@
 """Cases and parameters of the Huang-Carter goldens (make_golden_hc.py writes them, tests/test_hc_cpu.py and
 tests/test_hc_gpu.py read them).  The grid cases are those of cases.py plus `g16w`: g16r's density made wide,
 n_mean exp(2 u) with u = (n - n_mean) / (max n - min n), rescaled to g16r's mean -- its xi spans many spline intervals
-(HC: 1.74 .. 723, 40 nodes, 34 intervals touched) where the plain cases touch three."""
+(HC: 1.74 .. 723, 40 nodes, 34 intervals touched) where the plain cases touch three.
+
+EDGE_CASES are further goldens (hc_<name>.npz; tests/test_hc_cpu.py and tests/test_hc_edges_gpu.py read them): a kernel table short
+enough that a fifth of the (k-point, node) pairs lie past its end, a kappa at which g16w needs exactly the 64 nodes an evaluation
+carries, and a grid of three unequal extents with an odd last one.  They store k_E, k_E_nl, k_v_nl, the node set and the checksum."""
 import numpy as np
 
 import cases
+import elastic_cases
+from professad_amd import synth
 
 CASES = ['g16r', 'g17r', 'g18t', 'g16w']
 # golden key -> (reference class name, init_args, engine parameters of the nonlocal term)
@@ -16,6 +22,18 @@ KINDS = {
               dict(nlk_kind=5, nlk_p0=REVHC_ARGS[0], nlk_p1=REVHC_ARGS[1], nlk_p2=REVHC_ARGS[2], nlk_p3=REVHC_ARGS[3])),
 }
 ETA_MAX, N_ETA = 50.0, 10000
+G20X = 'g20x33'                       # (20, 18, 33) in the triclinic cell of elastic_cases.GRIDS['g20t'], synth.smooth_density of that shape
+# kappa of the M = 64 case: on g16w (HC, xi = 1.7438 .. 722.96) the node set has 64 nodes for kappa = 1.1102 .. 1.1120 (scanned in
+# steps of 1e-4).  KAPPA_M64 is the value of that range whose two ceil arguments lie farthest from an integer (0.292 and 0.336);
+# KAPPA_M65 is the value of the range 1.1090 .. 1.1101, which needs 65 nodes, chosen in the same way (0.351 and 0.370).
+KAPPA_M64, KAPPA_M65 = 1.1108, 1.1095
+# name -> dict(grid: key of make_inputs, keys: kind keys, table: (eta_max, N_eta) or None for the default, kappa: override or None)
+EDGE_CASES = {
+    'g16r_t8': dict(grid='g16r', keys=('hc', 'revhc'), table=(8.0, 1601), kappa=None),
+    'g18t_t8': dict(grid='g18t', keys=('hc', 'revhc'), table=(8.0, 1601), kappa=None),
+    'g16w_m64': dict(grid='g16w', keys=('hc',), table=None, kappa=KAPPA_M64),
+    G20X: dict(grid=G20X, keys=('hc', 'revhc'), table=None, kappa=None),
+}
 
 
 def beta_of(key):
@@ -28,6 +46,9 @@ def kappa_of(key):
 
 def make_inputs(name):
     """-> box, den (numpy fp64)"""
+    if name == G20X:
+        shape, cell = elastic_cases.GRIDS['g20t']
+        return cases.make_cell(cell), synth.smooth_density(shape)
     box, den, _vext, _chi, _n = cases.make_inputs('g16r' if name == 'g16w' else name)
     if name == 'g16w':
         u = (den - den.mean()) / (den.max() - den.min())
@@ -42,3 +63,25 @@ def node_set(xi_min, xi_max, kappa):
     lower = kappa ** (-(np.ceil(a) + 3))
     b = np.log((xi_max + 1) / lower) / np.log(kappa)
     return float(lower), int(np.ceil(b) + 3), float(a), float(b)
+
+
+def edge_args(name, key):
+    """init_args of the reference class for an edge case: those of the kind, with the case's kappa where it names one"""
+    args = KINDS[key][1]
+    kappa = EDGE_CASES[name]['kappa']
+    return args if kappa is None else args[:-1] + (kappa,)
+
+
+def edge_table(name):
+    """(eta_max, N_eta) of an edge case"""
+    return EDGE_CASES[name]['table'] or (ETA_MAX, N_ETA)
+
+
+def edge_params(name, key):
+    """engine parameters of the nonlocal term for an edge case (the table's two keys included where the case names a table)"""
+    p = dict(KINDS[key][2])
+    args = edge_args(name, key)
+    p['nlk_p2' if key == 'hc' else 'nlk_p3'] = args[-1]
+    if EDGE_CASES[name]['table']:
+        p['nlk_eta_max'], p['nlk_n_eta'] = EDGE_CASES[name]['table']
+    return p

@@ -1,6 +1,6 @@
 """Numpy double of the Huang-Carter kinds of OFDFT_NLK (kinds 4 and 5): the closed form the engine evaluates, restated on the CPU.
 
-    hc_energy_potential(kind, args, box, den, eta, w) -> dict(E_nl, v_nl, xi_min, xi_max, lower, M, touched)
+    hc_energy_potential(kind, args, box, den, eta, w) -> dict(E_nl, v_nl, xi_min, xi_max, lower, M, touched, nodes, used, q)
 
 kind 'hc' with args (lambda, beta, kappa) or 'revhc' with (a, b, beta, kappa); (eta, w) the kernel table.  E_nl = T_NL [Ha] and
 v_nl = dT_NL/dn on the grid.  With p = 8/3 - beta, C = 0.3 (3 pi^2)^(2/3) 8 (3 pi^2), gamma = |grad n|^2 (spectral gradient,
@@ -100,7 +100,10 @@ def hc_energy_potential(kind, args, box, den, eta, w):
     for o, c in zip((-1, 0, 1, 2), cw):
         np.put_along_axis(W, (idx + o)[..., None], (A * c)[..., None], 3)
     v = v + beta * n ** (beta - 1) * np.fft.irfftn((wt * np.fft.rfftn(W, axes=(0, 1, 2))).sum(3), s=shape, axes=(0, 1, 2))
-    return dict(E_nl=E, v_nl=v, xi_min=xi_min, xi_max=xi_max, lower=float(lower), M=M, touched=int(idx.max() - idx.min() + 1))      # spline intervals from the lowest to the highest one used
+    # touched: spline intervals from the lowest to the highest one used; nodes, used: the node set and the first and last node
+    # that some point's spline reads; q: |k| on the half spectrum
+    return dict(E_nl=E, v_nl=v, xi_min=xi_min, xi_max=xi_max, lower=float(lower), M=M, touched=int(idx.max() - idx.min() + 1),
+                nodes=xs, used=(int(idx.min()) - 1, int(idx.max()) + 2), q=q)
 
 
 def tf_vw(box, den):

@@ -72,6 +72,77 @@ def test_node_set_margin_of_the_fixtures():
             assert min(abs(a - round(a)), abs(b - round(b))) > 1e-6, (case, key)
 
 
+EDGE = [(case, key) for case, spec in hc_cases.EDGE_CASES.items() for key in spec['keys']]
+_EDGE_DOUBLE = {}
+
+
+def edge_double(case, key):
+    """the numpy double of an edge case (hc_cases.EDGE_CASES) with the case's table and kappa, computed once and shared"""
+    if (case, key) not in _EDGE_DOUBLE:
+        box, den = hc_cases.make_inputs(hc_cases.EDGE_CASES[case]['grid'])
+        eta, w = hc_kernel.solve_kernel(hc_cases.beta_of(key), *hc_cases.edge_table(case))
+        _EDGE_DOUBLE[case, key] = (box, den, eta, hc_double.hc_energy_potential(key, hc_cases.edge_args(case, key), box, den, eta, w))
+    return _EDGE_DOUBLE[case, key]
+
+
+@pytest.mark.parametrize('case,key', EDGE)
+def test_numpy_double_matches_edge_golden(case, key):
+    """The short-table, M = 64 and (20, 18, 33) goldens, at the bounds of the test above.  Measured (dE_nl / |E_total|, dv_nl /
+    max|v_nl|): g16r_t8 hc 2.6e-17 8.0e-15, revhc 6.5e-17 1.0e-14; g18t_t8 hc 5.8e-17 1.1e-14, revhc 4.4e-17 1.2e-14;
+    g16w_m64 hc 3.4e-17 2.9e-14; g20x33 hc 7.3e-18 9.8e-15, revhc 2.8e-17 1.2e-14 -- all below a tenth of the bounds, so the GPU
+    tests of these goldens (tests/test_hc_edges_gpu.py) keep the parity bounds as they are."""
+    gold = np.load(os.path.join(GOLDEN, 'hc_%s.npz' % case))
+    box, den, _eta, r = edge_double(case, key)
+    assert abs(cases.checksum(box, den) - float(gold['checksum'])) < 1e-9
+    assert sorted(gold.files) == sorted(['checksum'] + [k + s for k in hc_cases.EDGE_CASES[case]['keys']
+                                                        for s in ('_E', '_E_nl', '_v_nl', '_xi_min', '_xi_max', '_lower', '_M')])
+    E_tot = float(gold[key + '_E'])
+    v_ref = gold[key + '_v_nl']
+    err_E = abs(r['E_nl'] - float(gold[key + '_E_nl'])) / abs(E_tot)
+    err_v = float(np.abs(r['v_nl'] - v_ref).max() / np.abs(v_ref).max())
+    print('%s %s: dE %.2e dv %.2e M %d intervals %d' % (case, key, err_E, err_v, r['M'], r['touched']))
+    assert err_E <= E_TOL and err_v <= V_TOL
+    assert r['M'] == int(gold[key + '_M'])
+    for k in ('xi_min', 'xi_max', 'lower'):
+        assert r[k] == pytest.approx(float(gold[key + '_' + k]), rel=1e-13)
+    assert abs(hc_double.tf_vw(box, den)[0] + r['E_nl'] - E_tot) <= E_TOL * abs(E_tot)
+    kappa = hc_cases.edge_args(case, key)[-1]
+    _lower, M, a, b = hc_cases.node_set(float(gold[key + '_xi_min']), float(gold[key + '_xi_max']), kappa)
+    assert M == r['M'] and min(abs(a - round(a)), abs(b - round(b))) > 1e-6
+
+
+@pytest.mark.parametrize('case,key', [(c, k) for c, k in EDGE if hc_cases.EDGE_CASES[c]['table']])
+def test_short_table_clamps_a_share_of_the_pairs_and_moves_the_potential(case, key):
+    """The condition that makes the short-table goldens a test of hc_table_interp's clamp, from numpy alone: of the (k-point, node)
+    pairs over the nodes some point's spline reads, at least a tenth lie past the table's end (q / xi_j > eta_max) and at least a
+    tenth inside it.  Measured: g16r_t8 20.7 % (hc), 20.7 % (revhc); g18t_t8 20.7 %, 20.9 %.  With the default table the same
+    pairs are all inside (largest q / xi_j 17.1), and v_nl differs by 5.8e-4 .. 6.9e-4 of its maximum: eight orders above the
+    parity bound."""
+    box, den, eta, r = edge_double(case, key)
+    eta_max = float(eta[-1])
+    assert eta_max == hc_cases.edge_table(case)[0] and len(eta) == hc_cases.edge_table(case)[1]
+    first, last = r['used']
+    assert 0 <= first < last < r['M']
+    ratio = r['q'][..., None] / r['nodes'][first:last + 1]
+    above, below = float(np.mean(ratio > eta_max)), float(np.mean(ratio < eta_max))
+    default = hc_double.hc_energy_potential(key, hc_cases.edge_args(case, key), box, den, *table(key))
+    moved = float(np.abs(default['v_nl'] - r['v_nl']).max() / np.abs(r['v_nl']).max())
+    print('%s %s: %.1f %% of %d pairs clamped, %.1f %% inside, largest q / xi_j %.1f, v_nl moves by %.2e' % (
+        case, key, 100 * above, ratio.size, 100 * below, ratio.max(), moved))
+    assert above >= 0.10 and below >= 0.10
+    assert ratio.max() < hc_cases.ETA_MAX and moved > 1e-5
+
+
+def test_m64_case_fills_the_node_cap_and_its_neighbour_exceeds_it():
+    """g16w at hc_cases.KAPPA_M64 needs exactly the 64 nodes an evaluation carries (M + 3 = 67 transforms forward: no multiple of the
+    batch of 4), at KAPPA_M65 one more; both with ceil margins far above rounding"""
+    _box, _den, _eta, r = edge_double('g16w_m64', 'hc')
+    assert r['M'] == 64 and (r['M'] + 3) % 4 != 0
+    for kappa, want in ((hc_cases.KAPPA_M64, 64), (hc_cases.KAPPA_M65, 65)):
+        _lower, M, a, b = hc_cases.node_set(r['xi_min'], r['xi_max'], kappa)
+        assert M == want and min(abs(a - round(a)), abs(b - round(b))) > 0.1
+
+
 # ------------------------------------------------------------------------------- 2: the kernel table
 @pytest.mark.parametrize('key', list(hc_cases.KINDS))
 def test_table_matches_fixture_and_boundary_values(key):
