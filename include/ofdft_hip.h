@@ -549,7 +549,12 @@ int  ofdft_cg_solution(ofdft_cg* h, void* x_out_dev, void* stream);
                                      three or more spectra and the group-parallel kernel (spectra traded through LDS) for the rest.
                                      0 = always the group-parallel kernel, 2 = the wave-local kernel for every pass, 5 = the cross-wave
                                      kernel wherever it exists (128..1024 points), 6 = ... for passes over >= 3 spectra only, 7 = the
-                                     round-3 choice (no cross-wave kernel) */
+                                     round-3 choice (no cross-wave kernel), 4 = that choice with the group-parallel kernel from 512-point
+                                     lines on.  fp32 build under 1: 1024-point lines take the cross-wave kernel for every pass, 256-point
+                                     lines the group-parallel one for 1 -> 1 passes; its cross-wave kernel owns two memory-adjacent lines
+                                     per lane and hands a pass whose lines do not come in whole pairs on to the wave-local kernel (up to
+                                     512 points) or the group-parallel one (1024).  A pass that also integrates an energy has no
+                                     group-parallel kernel: where neither other family serves it the evaluation takes its plain form */
 int  ofdft_set_option(ofdft_ctx* ctx, int option, double value);
 
 /* Measurement support (bench.py): when on, every kernel launch of the energy calls is bracketed by HIP

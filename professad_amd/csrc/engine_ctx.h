@@ -24,6 +24,7 @@
 #include "bluestein.h"
 #include "zpass.h"
 #include "xwave.h"
+#include "line_lengths.h"
 
 using namespace ofdft;
 
@@ -110,7 +111,8 @@ struct ofdft_ctx {
                             // 8 256 waves -- exactly what the chip holds at once -- so alone every workgroup loads, transforms and stores in lock
                             // step; three spectra per launch stagger: the batched passes 50 -> 46.5 us (fp64), 34 -> 27 us (fp32) per spectrum,
                             // evaluation neutral in fp64 (three alternations within 0.3 %), +0.9 % in fp32
-    int use_xwave = 1;   // fused x pass: 1 = wave-local kernel (xwave.h) where it measured faster (passes over >= 3 spectra, x extents <= 512), 2 = wherever it exists, 0 = group-parallel kernel only
+    int use_xwave = 1;   // OFDFT_OPT_XWAVE (include/ofdft_hip.h): which kernel family a fused x pass takes -- the kXw* values below, read by
+                         // xpass_choice (xpass_impl.h) and nowhere else
     // optional per-kernel-class profiling (HIP events around every launch)
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;
@@ -306,7 +308,7 @@ inline WtMoment wt_moment(const TermScalars& ts, double nbar) {
     return w;
 }
 inline bool zfused_serves(const ofdft_ctx* c) {
-    return c->fast && c->pipeline == 0 && c->n2 / 2 <= 512 && (!gga_needs_laplacian(c) || c->gga_split);
+    return c->fast && c->pipeline == 0 && has_len(kZFusedLens, c->n2 / 2) && (!gga_needs_laplacian(c) || c->gga_split);
 }
 // where the z-fused pipeline does not serve: the x-fused pipeline (run_terms_fast) takes the evaluation, else the unfused one
 inline bool xfused_serves(const ofdft_ctx* c) { return c->fast && !c->force_unfused && !gga_needs_laplacian(c); }
@@ -346,25 +348,6 @@ void prof_collect(ofdft_ctx* c);
 
 inline bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 
-// Extents served by the register / LDS line transforms (fft_radix.h plans) -- and with them by the fused pipelines:
-// powers of two, and the 2^a 3^b 5^c extents listed here (any other extent: chirp-z line transforms + the unfused pipeline).
-// OFDFT_MIXED_LINES: x / y extents; OFDFT_MIXED_ROWS: the half lengths n2 / 2 of the z rows for the same extents.
-// (both precisions since round 3; OFDFT_NO_MIXED_F32 restores the round-2 fp32 build, whose other extents took the chirp-z path)
-#if !defined(OFDFT_REAL_F32) || !defined(OFDFT_NO_MIXED_F32)
-#define OFDFT_MIXED_LINES(X) X(48) X(96) X(120) X(144) X(160) X(192) X(240) X(250) X(270) X(288) X(320) X(384) X(480)
-#define OFDFT_MIXED_ROWS(X) X(24) X(48) X(60) X(72) X(80) X(96) X(120) X(125) X(135) X(144) X(160) X(192) X(240)
-#else
-#define OFDFT_MIXED_LINES(X)
-#define OFDFT_MIXED_ROWS(X)
-#endif
-inline bool mixed_line(int n) {
-#define X(L) if (n == L) return true;
-    OFDFT_MIXED_LINES(X)
-#undef X
-    return false;
-}
-inline bool line_extent_ok(int n) { return (is_pow2(n) && n >= 8 && n <= 1024) || mixed_line(n); }
-inline bool row_extent_ok(int n2) { return (is_pow2(n2) && n2 >= 16 && n2 <= 2048) || mixed_line(n2); }
 inline bool all_pow2(const ofdft_ctx* c) { return is_pow2(c->n0g) && is_pow2(c->n1g) && is_pow2(c->n2); }
 
 inline int grid_for(long long n, int tpb = 256, int cap = 2048) {
@@ -490,6 +473,18 @@ struct XfLayout {
     long long se_in = 0, se_out = 0, tse = 0;
     int xnb = -1, xnrem = 0;       // exchange buffers: kz blocks / remainder planes of the chunk the pointers address (xnb < 0: all of c->xg)
     int kz0 = 0;                   // ... and the kz of its first block
+};
+// the three kernel families of a fused x pass, and the values of OFDFT_OPT_XWAVE (c->use_xwave) that choose among them; the
+// choice itself, with the measurements behind it: xpass_choice (xpass_impl.h)
+enum class XKind { None, Group, Wave, Cross };      // none / group-parallel (fft_kernels.h) / wave-local (xwave.h) / cross-wave (xcross.h)
+enum : int {
+    kXwGroupOnly = 0,     // always the group-parallel kernel
+    kXwMeasured = 1,      // (default) each family where it measured fastest
+    kXwWaveAll = 2,       // the wave-local kernel for every pass it exists for
+    kXwGroupAt512 = 4,    // as the round-3 choice, but the group-parallel kernel from 512-point lines on (A/B)
+    kXwCrossAll = 5,      // the cross-wave kernel wherever it exists
+    kXwCross3 = 6,        // ... for passes over >= 3 spectra only
+    kXwRound3 = 7,        // no cross-wave kernel: the wave-local one for passes over >= 3 spectra, else the group-parallel one
 };
 template <int NIN, int NOUT, class Mix>
 int xfused(ofdft_ctx* c, const XfIo& io, const Mix& mix, hipStream_t st, const char* nm, const XfLayout& lay = XfLayout{});

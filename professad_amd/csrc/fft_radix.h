@@ -397,7 +397,7 @@ OFDFT_PLAN(256, 2, 16, 16, 1, 16)
 OFDFT_PLAN(512, 3, 8, 8, 8, 8)
 OFDFT_PLAN(1024, 3, 16, 8, 8, 16)
 #undef OFDFT_PLAN
-// extents with factors 3 and 5 (OFDFT_MIXED_SIZES lists them for the dispatch switches): LEN, P, stages, radices
+// extents with factors 3 and 5 (line_lengths.h: kMixedLens lists them for the predicates and the dispatch): LEN, P, stages, radices
 #define OFDFT_GPLAN(LEN_, P_, NST_, R0_, R1_, R2_) template <> struct Plan<LEN_> : PlanBase<LEN_, P_, NST_, R0_, R1_, R2_, 1> {};
 OFDFT_GPLAN(48, 8, 2, 6, 8, 1)          // 8 + 6 butterflies over 8 threads: E = 8
 OFDFT_GPLAN(96, 8, 2, 8, 12, 1)         // E = 16

@@ -44,17 +44,10 @@ int fast_axis_pass_multi(ofdft_ctx* c, int axis, cplx* const* specs, int narr, h
     if (axis == 1) c->ypass_count += narr;
     const int len = axis == 0 ? c->n0g : c->n1;
     const char* nm = axis == 0 ? "cpass_x" : "cpass_y";
-#define OFDFT_CASE(L)                                                   \
-    case L:                                                             \
-        if (axis == 0) main.lf = rem.lf = PassCfg<L>::LPW;              \
-        return launch_cpass_t<L, INV>(c, arrs, narr, main, rem, st, nm);
-    switch (len) {
-        OFDFT_CASE(8) OFDFT_CASE(16) OFDFT_CASE(32) OFDFT_CASE(64) OFDFT_CASE(128) OFDFT_CASE(256) OFDFT_CASE(512)
-        OFDFT_CASE(1024)
-        OFDFT_MIXED_LINES(OFDFT_CASE)
-    }
-#undef OFDFT_CASE
-    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", len);
+    return for_len(kLineLens, len, [&](auto L) {
+        if (axis == 0) main.lf = rem.lf = PassCfg<L()>::LPW;
+        return launch_cpass_t<L(), INV>(c, arrs, narr, main, rem, st, nm);
+    }, [&] { return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", len); });
 }
 
 template <bool INV>
@@ -101,14 +94,8 @@ int ypass_xchg(ofdft_ctx* c, const std::vector<cplx*>& list, cplx* buf, hipStrea
     if (narr > 16) return fail(c, OFDFT_EINVAL, "too many spectra in one exchange (%d)", narr);
     ArrList arrs{};
     for (int a = 0; a < narr; ++a) arrs.p[a] = list[a];
-#define OFDFT_CASE(L) case L: return launch_ypass_xchg_t<L, INV>(c, arrs, narr, buf, st, xk);
-    switch (c->n1) {
-        OFDFT_CASE(8) OFDFT_CASE(16) OFDFT_CASE(32) OFDFT_CASE(64) OFDFT_CASE(128) OFDFT_CASE(256) OFDFT_CASE(512)
-        OFDFT_CASE(1024)
-        OFDFT_MIXED_LINES(OFDFT_CASE)
-    }
-#undef OFDFT_CASE
-    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
+    return for_len(kLineLens, c->n1, [&](auto L) { return launch_ypass_xchg_t<L(), INV>(c, arrs, narr, buf, st, xk); },
+                   [&] { return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1); });
 }
 
 template <int M>
@@ -150,22 +137,12 @@ int launch_zinv_t(ofdft_ctx* c, const cplx* spec, real* out, double scale, hipSt
 }
 // dispatch on the half length of the z rows
 int zfwd_any(ofdft_ctx* c, const real* in, cplx* spec, hipStream_t st) {
-#define X(M_) case M_: return launch_zfwd_t<M_>(c, in, spec, st);
-    switch (c->n2 / 2) {
-        X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024)
-        OFDFT_MIXED_ROWS(X)
-    }
-#undef X
-    return fail(c, OFDFT_EINVAL, "bad n2");
+    return for_len(kZRowLens, c->n2 / 2, [&](auto M) { return launch_zfwd_t<M()>(c, in, spec, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "bad n2"); });
 }
 int zinv_any(ofdft_ctx* c, const cplx* spec, real* out, double scale, hipStream_t st) {
-#define X(M_) case M_: return launch_zinv_t<M_>(c, spec, out, scale, st);
-    switch (c->n2 / 2) {
-        X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024)
-        OFDFT_MIXED_ROWS(X)
-    }
-#undef X
-    return fail(c, OFDFT_EINVAL, "bad n2");
+    return for_len(kZRowLens, c->n2 / 2, [&](auto M) { return launch_zinv_t<M()>(c, spec, out, scale, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "bad n2"); });
 }
 
 int gen_axis(ofdft_ctx* c, int axis, int inv, cplx*& cur, cplx*& other, hipStream_t st) {
@@ -284,7 +261,9 @@ static int launch_xmix_t(ofdft_ctx* c, const BsMixIo& io, const Mix& mix, const 
                  c->n0, nlines, (const cplx*)t.chirp, (const cplx*)t.filt, (const cplx*)tw, mix);
     return 0;
 }
-bool bluestein_xmix_ok(const ofdft_ctx* c) { return c->bs_fused && bluestein_ok(c) && c->nranks == 1 && !c->fast && c->n0 <= 256; }
+bool bluestein_xmix_ok(const ofdft_ctx* c) {
+    return c->bs_fused && bluestein_ok(c) && c->nranks == 1 && !c->fast && has_len(kChirpXmixLens, bluestein_pad(c->n0));
+}
 template <int NIN, int NOUT, class Mix>
 int bluestein_xmix(ofdft_ctx* c, const cplx* const* in, cplx* const* out, const Mix& mix, hipStream_t st) {
     BsTables t;
@@ -292,16 +271,8 @@ int bluestein_xmix(ofdft_ctx* c, const cplx* const* in, cplx* const* out, const 
     BsMixIo io{};
     for (int i = 0; i < NIN; ++i) io.in[i] = in[i];
     for (int o = 0; o < NOUT; ++o) io.out[o] = out[o];
-    switch (t.M) {
-        case 8: return launch_xmix_t<8, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 16: return launch_xmix_t<16, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 32: return launch_xmix_t<32, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 64: return launch_xmix_t<64, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 128: return launch_xmix_t<128, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 256: return launch_xmix_t<256, NIN, NOUT, Mix>(c, io, mix, t, st);
-        case 512: return launch_xmix_t<512, NIN, NOUT, Mix>(c, io, mix, t, st);
-    }
-    return fail(c, OFDFT_EINVAL, "no fused chirp-z x pass for length %d", c->n0);
+    return for_len(kChirpXmixLens, t.M, [&](auto M) { return launch_xmix_t<M(), NIN, NOUT, Mix>(c, io, mix, t, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "no fused chirp-z x pass for length %d", c->n0); });
 }
 template int bluestein_xmix<1, 1, MixScale<SPEC_HARTREE>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_HARTREE>&, hipStream_t);
 template int bluestein_xmix<1, 1, MixScale<SPEC_LAPLACE>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_LAPLACE>&, hipStream_t);
@@ -318,7 +289,7 @@ template int bluestein_xmix<3, 3, MixWgc>(ofdft_ctx*, const cplx* const*, cplx* 
 static bool bluestein_zy_ok(const ofdft_ctx* c, int* M_out) {
     if (!c->bs_fused) return false;
     const int M1 = bluestein_pad(c->n1), M2 = bluestein_pad(c->n2);
-    if (M1 != M2 || M1 > 128) return false;
+    if (M1 != M2 || !has_len(kChirpZyLens, M1)) return false;
     *M_out = M1;
     return true;
 }
@@ -337,14 +308,8 @@ static int launch_zy_t(ofdft_ctx* c, const BsIo& io, int narr, double scale, hip
 }
 template <bool INV>
 static int bluestein_zy(ofdft_ctx* c, int M, const BsIo& io, int narr, double scale, hipStream_t st) {
-    switch (M) {
-        case 8: return launch_zy_t<8, INV>(c, io, narr, scale, st);
-        case 16: return launch_zy_t<16, INV>(c, io, narr, scale, st);
-        case 32: return launch_zy_t<32, INV>(c, io, narr, scale, st);
-        case 64: return launch_zy_t<64, INV>(c, io, narr, scale, st);
-        case 128: return launch_zy_t<128, INV>(c, io, narr, scale, st);
-    }
-    return fail(c, OFDFT_EINVAL, "no fused z / y chirp-z pass for padded length %d", M);
+    return for_len(kChirpZyLens, M, [&](auto L) { return launch_zy_t<L(), INV>(c, io, narr, scale, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "no fused z / y chirp-z pass for padded length %d", M); });
 }
 
 // the z and y passes of `n` (<= kBsBatch) transforms, one launch per pass (small grids: ONE launch for both): the halves of a 3-D
@@ -391,17 +356,8 @@ int bluestein_pass_multi(ofdft_ctx* c, int mode, int axis, int inv, const BsIo& 
     b.inv = inv;
     b.scale = scale;
     b.nlines = mode == 0 ? (long long)(axis == 0 ? c->n1 : c->n0) * c->g.nzc : (c->g.nrows + 1) / 2;      // (z rows go in pairs)
-    switch (t.M) {
-        case 8: return launch_bluestein_t<8>(c, io, narr, b, t, st);
-        case 16: return launch_bluestein_t<16>(c, io, narr, b, t, st);
-        case 32: return launch_bluestein_t<32>(c, io, narr, b, t, st);
-        case 64: return launch_bluestein_t<64>(c, io, narr, b, t, st);
-        case 128: return launch_bluestein_t<128>(c, io, narr, b, t, st);
-        case 256: return launch_bluestein_t<256>(c, io, narr, b, t, st);
-        case 512: return launch_bluestein_t<512>(c, io, narr, b, t, st);
-        case 1024: return launch_bluestein_t<1024>(c, io, narr, b, t, st);
-    }
-    return fail(c, OFDFT_EINVAL, "no Bluestein plan for length %d", N);
+    return for_len(kChirpLens, t.M, [&](auto M) { return launch_bluestein_t<M()>(c, io, narr, b, t, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "no Bluestein plan for length %d", N); });
 }
 
 int bluestein_pass(ofdft_ctx* c, int mode, int axis, int inv, cplx* spec, const real* rin, real* rout, double scale,
@@ -413,7 +369,11 @@ int bluestein_pass(ofdft_ctx* c, int mode, int axis, int inv, cplx* spec, const 
     return bluestein_pass_multi(c, mode, axis, inv, io, 1, scale, st);
 }
 
-bool bluestein_ok(const ofdft_ctx* c) { return c->use_bluestein && c->n0 <= 512 && c->n1 <= 512 && c->n2 <= 512; }
+// (extents up to 512: a padded length with a plan)
+bool bluestein_ok(const ofdft_ctx* c) {
+    return c->use_bluestein && has_len(kChirpLens, bluestein_pad(c->n0)) && has_len(kChirpLens, bluestein_pad(c->n1)) &&
+           has_len(kChirpLens, bluestein_pad(c->n2));
+}
 static bool bluestein_ok_fwd(const ofdft_ctx* c) { return bluestein_ok(c); }
 
 // ---- slab-decomposed 3-D transforms for the per-geometry-step routines (stress, ionic potential, forces): a real x-slab
@@ -573,93 +533,35 @@ static int dist_irfftn(ofdft_ctx* c, cplx* spec, real* out, double scale, hipStr
 }
 
 
-// index derivative along y of an x-slab spectrum in (kz; y, x) form, in one pass (fft_kernels.h: yderiv_kernel)
-template <int LEN>
-int launch_yderiv_t(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd) {
-    cplx* tw;
-    if (int rc = get_twiddle(c, LEN, &tw)) return rc;
-    using Cfg = PassCfg<LEN>;
-    LineMap main, rem;
-    pass_maps(c, 1, main, rem);
-    const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
-    OFDFT_LAUNCH(c, st, "yderiv", (yderiv_kernel<LEN>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, in, out, main, rem, mb,
-                 c->g.main_count, (const cplx*)tw, (real)scale, fwd);
+// The one-pass y operators on an x-slab spectrum in (kz; y, x) form (fft_kernels.h: yderiv_kernel<LEN, ADD, LAP>); `tail`: the
+// kernel's trailing arguments
+template <bool ADD, bool LAP, class... Tail>
+static int yline_op(ofdft_ctx* c, const char* nm, const cplx* in, cplx* out, double scale, hipStream_t st, Tail... tail) {
+    return for_len(kLineLens, c->n1, [&](auto L) {
+        cplx* tw;
+        if (int rc = get_twiddle(c, L(), &tw)) return rc;
+        using Cfg = PassCfg<L()>;
+        LineMap main, rem;
+        pass_maps(c, 1, main, rem);
+        const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
+        OFDFT_LAUNCH(c, st, nm, (yderiv_kernel<L(), ADD, LAP>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, in, out, main, rem, mb,
+                     c->g.main_count, (const cplx*)tw, (real)scale, tail...);
+        return 0;
+    }, [&] { return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1); });
+}
+// index derivative along y
+int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd) {
+    if (int rc = yline_op<false, false>(c, "yderiv", in, out, scale, st, fwd)) return rc;
     if (fwd) c->fft_passes_fused++, c->yfwd_fused++;
     return 0;
 }
-// ... plus a y-forwarded spectrum added before the inverse (yderiv_kernel<LEN, true>)
-template <int LEN>
-int launch_yderiv_add_t(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
-    cplx* tw;
-    if (int rc = get_twiddle(c, LEN, &tw)) return rc;
-    using Cfg = PassCfg<LEN>;
-    LineMap main, rem;
-    pass_maps(c, 1, main, rem);
-    const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
-    OFDFT_LAUNCH(c, st, "yderiv", (yderiv_kernel<LEN, true>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, in, out, main, rem, mb,
-                 c->g.main_count, (const cplx*)tw, (real)scale, (cplx*)nullptr, add);
-    return 0;
-}
+// ... plus a y-forwarded spectrum added before the inverse
 int yderiv_add(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
-    switch (c->n1) {
-        case 8: return launch_yderiv_add_t<8>(c, in, add, out, scale, st);
-        case 16: return launch_yderiv_add_t<16>(c, in, add, out, scale, st);
-        case 32: return launch_yderiv_add_t<32>(c, in, add, out, scale, st);
-        case 64: return launch_yderiv_add_t<64>(c, in, add, out, scale, st);
-        case 128: return launch_yderiv_add_t<128>(c, in, add, out, scale, st);
-        case 256: return launch_yderiv_add_t<256>(c, in, add, out, scale, st);
-        case 512: return launch_yderiv_add_t<512>(c, in, add, out, scale, st);
-        case 1024: return launch_yderiv_add_t<1024>(c, in, add, out, scale, st);
-#define X(L) case L: return launch_yderiv_add_t<L>(c, in, add, out, scale, st);
-        OFDFT_MIXED_LINES(X)
-#undef X
-    }
-    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
+    return yline_op<true, false>(c, "yderiv", in, out, scale, st, (cplx*)nullptr, add);
 }
-// y part of the Laplacian plus a finished spectrum of the output's layout (yderiv_kernel<LEN, false, true>)
-template <int LEN>
-int launch_ylap_t(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
-    cplx* tw;
-    if (int rc = get_twiddle(c, LEN, &tw)) return rc;
-    using Cfg = PassCfg<LEN>;
-    LineMap main, rem;
-    pass_maps(c, 1, main, rem);
-    const int mb = (main.nlines + Cfg::LPW - 1) / Cfg::LPW, rb = (rem.nlines + Cfg::LPW - 1) / Cfg::LPW;
-    OFDFT_LAUNCH(c, st, "ylap", (yderiv_kernel<LEN, false, true>), dim3(mb + rb), dim3(Cfg::TPB), Cfg::LDS, in, out, main, rem, mb,
-                 c->g.main_count, (const cplx*)tw, (real)scale, (cplx*)nullptr, add);
-    return 0;
-}
+// y part of the Laplacian plus a finished spectrum of the output's layout
 int ylap(ofdft_ctx* c, const cplx* in, const cplx* add, cplx* out, double scale, hipStream_t st) {
-    switch (c->n1) {
-        case 8: return launch_ylap_t<8>(c, in, add, out, scale, st);
-        case 16: return launch_ylap_t<16>(c, in, add, out, scale, st);
-        case 32: return launch_ylap_t<32>(c, in, add, out, scale, st);
-        case 64: return launch_ylap_t<64>(c, in, add, out, scale, st);
-        case 128: return launch_ylap_t<128>(c, in, add, out, scale, st);
-        case 256: return launch_ylap_t<256>(c, in, add, out, scale, st);
-        case 512: return launch_ylap_t<512>(c, in, add, out, scale, st);
-        case 1024: return launch_ylap_t<1024>(c, in, add, out, scale, st);
-#define X(L) case L: return launch_ylap_t<L>(c, in, add, out, scale, st);
-        OFDFT_MIXED_LINES(X)
-#undef X
-    }
-    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
-}
-int yderiv(ofdft_ctx* c, const cplx* in, cplx* out, double scale, hipStream_t st, cplx* fwd) {
-    switch (c->n1) {
-        case 8: return launch_yderiv_t<8>(c, in, out, scale, st, fwd);
-        case 16: return launch_yderiv_t<16>(c, in, out, scale, st, fwd);
-        case 32: return launch_yderiv_t<32>(c, in, out, scale, st, fwd);
-        case 64: return launch_yderiv_t<64>(c, in, out, scale, st, fwd);
-        case 128: return launch_yderiv_t<128>(c, in, out, scale, st, fwd);
-        case 256: return launch_yderiv_t<256>(c, in, out, scale, st, fwd);
-        case 512: return launch_yderiv_t<512>(c, in, out, scale, st, fwd);
-        case 1024: return launch_yderiv_t<1024>(c, in, out, scale, st, fwd);
-#define X(L) case L: return launch_yderiv_t<L>(c, in, out, scale, st, fwd);
-        OFDFT_MIXED_LINES(X)
-#undef X
-    }
-    return fail(c, OFDFT_EINVAL, "unsupported fast FFT length %d", c->n1);
+    return yline_op<false, true>(c, "ylap", in, out, scale, st, (cplx*)nullptr, add);
 }
 
 

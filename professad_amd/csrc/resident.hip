@@ -658,7 +658,7 @@ namespace eng {
 // terms without a Laplacian
 bool resident_serves(const ofdft_ctx* c) {
     if (!c->resident || c->nranks != 1 || !c->fast) return false;
-    if (!(c->n0 == c->n1 && c->n1 == c->n2 && (c->n0 == 16 || c->n0 == 32 || c->n0 == 64))) return false;
+    if (!(c->n0 == c->n1 && c->n1 == c->n2 && has_len(kResidentLens, c->n0))) return false;
     if ((c->mask & OFDFT_WGC99_NL) && c->n0 > 32) return false;      // (six more spectra: beyond 32^3 the graph replay is faster)
     if ((c->mask & kGgaAny) && (gga_needs_laplacian(c) || (c->n0 > 32 && sizeof(real) == 8))) return false;      // (64^3 fp64 with a GGA term: five phases of
                                                                                           //  4096-point planes per workgroup measured slower than the graph replay, 0.160 vs 0.153 ms; fp32: 0.118 vs 0.150)
@@ -703,7 +703,7 @@ int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel
     const int N = c->n0;
     const unsigned mask = c->mask;
     if ((mask & OFDFT_ION_ELECTRON) && !vext) return fail(c, OFDFT_EINVAL, "IonElectron term needs vext");
-    if (c->res_fits < 0) c->res_fits = (N == 16 ? res_fits<16>(c) : N == 32 ? res_fits<32>(c) : res_fits<64>(c)) ? 1 : 0;
+    if (c->res_fits < 0) c->res_fits = for_len(kResidentLens, N, [&](auto L) { return res_fits<L()>(c) ? 1 : 0; }, [] { return 0; });
     if (!c->res_fits) {           // the N workgroups cannot be co-resident on this device / partition: never launch
         c->resident = 0;
         return kResidentDeclined;
@@ -791,12 +791,8 @@ int resident_closure(ofdft_ctx* c, const real* chi, const real* vext, double nel
     a.dV = c->dV;
     a.inv_n = 1.0 / (double)c->npts;
     c->fft_count += a.narr + a.nout + (gga ? 4 : 0);
-    switch (N) {
-        case 16: return launch_res<16>(c, a, st);
-        case 32: return launch_res<32>(c, a, st);
-        case 64: return launch_res<64>(c, a, st);
-    }
-    return fail(c, OFDFT_EINVAL, "resident kernel: unsupported grid");
+    return for_len(kResidentLens, N, [&](auto L) { return launch_res<L()>(c, a, st); },
+                   [&] { return fail(c, OFDFT_EINVAL, "resident kernel: unsupported grid"); });
 }
 
 }  // namespace eng

@@ -15,18 +15,12 @@ template int xfused<1, 2, MixDensityA<true, true, false>>(ofdft_ctx*, const XfIo
 
 extern template int xfused<3, 3, MixWgc>(ofdft_ctx*, const XfIo&, const MixWgc&, hipStream_t, const char*, const XfLayout&);      // xpass_a.hip
 int xfused_wgc(ofdft_ctx* c, const XfIo& io, const MixWgc& mix, hipStream_t st, const char* nm, const XfLayout& lay) {
-    const real* bb = c->kg.b;
-    const bool ortho = bb[1] == 0.0 && bb[2] == 0.0 && bb[3] == 0.0 && bb[5] == 0.0 && bb[6] == 0.0 && bb[7] == 0.0;
-    if (ortho && c->wgc_fold && xc_serves<3, 3>(c)) {
+    if (cell_axes_orthogonal(c) && c->wgc_fold && xcross_wanted(c, 3 + 3)) {
+        // (the folded mix exists in the other two families only where the cross-wave kernel hands the pass on to them)
         MixWgcFold f;
         static_cast<MixWgc&>(f) = mix;
         f.fold_n0 = c->n0g;
-        switch (c->n0g) {
-            case 128: return launch_xc_t<128, 3, 3, MixWgcFold>(c, io, f, lay, st, nm);
-            case 256: return launch_xc_t<256, 3, 3, MixWgcFold>(c, io, f, lay, st, nm);
-            case 512: return launch_xc_t<512, 3, 3, MixWgcFold>(c, io, f, lay, st, nm);
-            case 1024: return launch_xc_t<1024, 3, 3, MixWgcFold>(c, io, f, lay, st, nm);
-        }
+        return xpass_run<3, 3>(c, io, f, lay, st, nm, kXcToWaveLens, kXcToGroupLens);
     }
     return xfused<3, 3, MixWgc>(c, io, mix, st, nm, lay);
 }
