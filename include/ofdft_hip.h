@@ -30,7 +30,7 @@
  *   - precision: the ABI is built once per precision from the same sources -- libofdft_hip.so (OFDFT_F64, the
  *     reference's precision) and libofdft_hip_f32.so (OFDFT_F32, same symbols; grid arrays are float / float2, every
  *     host-visible scalar stays double).  ofdft_create refuses the dtype of the other build.  The fp32 library serves
- *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points, ofdft_hessian_vector and ofdft_hessian_vector_chi are fp64-only and return OFDFT_EINVAL there.
+ *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points, ofdft_hessian_vector, ofdft_hessian_vector_chi and ofdft_precondition are fp64-only and return OFDFT_EINVAL there.
  *   - energies are Hartree; lengths bohr; box_vecs rows are the lattice vectors (reference layout).
  */
 #ifndef OFDFT_HIP_H
@@ -327,6 +327,15 @@ int  ofdft_hessian_vector_chi(ofdft_ctx* ctx, const void* chi_dev, const void* d
                               double n_electrons, void* out_dev, double* scalars_host /* [OFDFT_HVC_NSCALARS] or NULL */,
                               int reuse_density, void* stream);
 
+/* The kinetic preconditioner of the conjugate gradients below:  z = irfftn( rfftn(r) / (k^2 + kappa2) ), k as
+ * everywhere in the engine, kappa2 > 0 [1/bohr^2].  In chi the von Weizsaecker Hessian is c dV (-lap), so 1 / (k^2 + kappa2) with
+ * kappa2 = (4/3) k_F^2 (the Thomas-Fermi shift) follows the stiff end of H up to a constant factor.  Fused x pass where it serves
+ * the grid (five spectrum passes), chirp-z x-mix on chirp-z extents, and forward, multiply, inverse elsewhere and under
+ * OFDFT_OPT_PIPELINE = 1.  It leaves the fields retained for reuse_density = 1 valid and touches no workspace of the products
+ * but a transient spectrum, so it may run between two products.  Single GPU and fp64: the fp32 library and slab-decomposed
+ * contexts return OFDFT_EINVAL, as do kappa2 <= 0 or non-finite and z_dev == r_dev.  Synchronises the stream.  No atomics. */
+int  ofdft_precondition(ofdft_ctx* ctx, const void* r_dev, void* z_dev, double kappa2, void* stream);
+
 /* Ion-ion interaction: the real-space damped pair sum in a neutralising background of
  * ion_interaction_sum (ion_utils.py:293-333) with System.__ion_ion_interaction's parameters (system.py:733-754);
  * Rc <= 0 selects its default Rd = 2 h_max, Rc = 3 Rd^2 / h_max.  The pair list (torch-nl's neighbour list in the
@@ -483,6 +492,22 @@ int  ofdft_cg_vectors(ofdft_cg* h, void** x_dev, void** r_dev, void** p_dev, voi
 int  ofdft_cg_step(ofdft_cg* h, const void* phi_dev, double p_dot_q, double phi_dot_q, int* reason, void* stream);
 int  ofdft_cg_status(const ofdft_cg* h, int* iterations, int* reason, double* rel_residual);
 int  ofdft_cg_solution(ofdft_cg* h, void* x_out_dev, void* stream);
+
+/* Preconditioned mode of the same handle, opt-in: with it off nothing above changes, launch for launch.
+ *   ofdft_cg_set_preconditioned  on != 0: the solves begun by the following ofdft_cg_start calls run preconditioned.  Default 0.
+ *   ofdft_cg_z         the handle's vector z (allocated on first use).  Before every ofdft_cg_direction the caller writes
+ *                      z = M^-1 r there, r being that of ofdft_cg_vectors (ofdft_precondition, or any symmetric positive definite M^-1).
+ *   ofdft_cg_direction one sweep for r . z and phi . z, then rho = r . z - (phi . r)(phi . z) / S, beta = rho / rho_old (0 on the
+ *                      first call after ofdft_cg_start), and one sweep p = (z - phi (phi . z) / S) + beta p.  phi . r is the sum of
+ *                      the last update sweep.  info_host [4] = r . z, phi . z, rho, beta.  rho <= 0 or NaN: reason
+ *                      OFDFT_CG_CURVATURE, x and p stay.  One stream synchronisation.
+ * In this mode ofdft_cg_start stops after r = P b, and ofdft_cg_step takes alpha = rho / (p . q), runs the update sweep and the
+ * stopping rules -- on r . r, as in plain mode, so |r| / |r_0| keeps its meaning -- and no direction sweep.  One iteration is
+ * direction, product, step.  OFDFT_ESTATE: ofdft_cg_direction in plain mode, before ofdft_cg_start, after the solve has ended or
+ * twice for one step; ofdft_cg_step before the direction of the step is formed.  No atomics: bitwise reproducible. */
+int  ofdft_cg_set_preconditioned(ofdft_cg* h, int on);
+int  ofdft_cg_z(ofdft_cg* h, void** z_dev);
+int  ofdft_cg_direction(ofdft_cg* h, const void* phi_dev, double* info_host /* [4] or NULL */, int* reason, void* stream);
 
 /* Tuning / validation switches.  OFDFT_OPT_PIPELINE: 0 = automatic (power-of-two grids: fused x passes and z
  * passes that keep every real-space intermediate on chip), 1 = force the unfused pipeline (separate forward,

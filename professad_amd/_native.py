@@ -73,8 +73,8 @@ EXPORTS = ['ofdft_create', 'ofdft_destroy', 'ofdft_last_error', 'ofdft_set_cell'
            'ofdft_create_dist', 'ofdft_dist_sumsq', 'ofdft_dist_begin', 'ofdft_dist_stage', 'ofdft_dist_step', 'ofdft_dist_finish', 'ofdft_dist_scalars',
            'ofdft_dist_energies', 'ofdft_dist_chi_grad', 'ofdft_ipc_export', 'ofdft_ipc_attach', 'ofdft_ipc_detach', 'ofdft_dist_closure', 'ofdft_ionic_potential', 'ofdft_ion_electron_forces', 'ofdft_stress', 'ofdft_ion_electron_stress', 'ofdft_ion_ion', 'ofdft_ion_ion_cells', 'ofdft_ionic_potential_gradient', 'ofdft_ion_electron_curvature', 'ofdft_ion_ion_hessian',
            'ofdft_potential_strain_gradient', 'ofdft_ionic_potential_strain_gradient', 'ofdft_strain_hessian','ofdft_ion_electron_strain_hessian', 'ofdft_ion_ion_strain_hessian',
-           'ofdft_hessian_vector', 'ofdft_hessian_vector_chi', 'ofdft_cg_create', 'ofdft_cg_destroy', 'ofdft_cg_last_error', 'ofdft_cg_start',
-           'ofdft_cg_vectors', 'ofdft_cg_step', 'ofdft_cg_status', 'ofdft_cg_solution', 'ofdft_lbfgs_create', 'ofdft_lbfgs_destroy', 'ofdft_lbfgs_last_error', 'ofdft_lbfgs_reset', 'ofdft_lbfgs_direction', 'ofdft_lbfgs_abs_step', 'ofdft_lbfgs_dots',
+           'ofdft_hessian_vector', 'ofdft_hessian_vector_chi', 'ofdft_precondition', 'ofdft_cg_create', 'ofdft_cg_destroy', 'ofdft_cg_last_error', 'ofdft_cg_start',
+           'ofdft_cg_vectors', 'ofdft_cg_step', 'ofdft_cg_status', 'ofdft_cg_solution', 'ofdft_cg_set_preconditioned', 'ofdft_cg_z', 'ofdft_cg_direction', 'ofdft_lbfgs_create', 'ofdft_lbfgs_destroy', 'ofdft_lbfgs_last_error', 'ofdft_lbfgs_reset', 'ofdft_lbfgs_direction', 'ofdft_lbfgs_abs_step', 'ofdft_lbfgs_dots',
            'ofdft_lbfgs_commit', 'ofdft_lbfgs_update', 'ofdft_set_option', 'ofdft_set_collectives', 'ofdft_set_profiling', 'ofdft_profile_count', 'ofdft_profile_get']
 
 
@@ -156,6 +156,10 @@ def load(dtype=F64):
     lib.ofdft_cg_step.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(ip), vp]
     lib.ofdft_cg_status.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), dp]
     lib.ofdft_cg_solution.argtypes = [vp, vp, vp]
+    lib.ofdft_cg_set_preconditioned.argtypes = [vp, ip]
+    lib.ofdft_cg_z.argtypes = [vp, C.POINTER(vp)]
+    lib.ofdft_cg_direction.argtypes = [vp, vp, dp, C.POINTER(ip), vp]
+    lib.ofdft_precondition.argtypes = [vp, vp, vp, C.c_double, vp]
     lib.ofdft_ion_ion.argtypes = [vp, dp, dp, ip, C.c_double, dp, dp, dp, vp]
     lib.ofdft_ion_ion_cells.argtypes = [vp, dp, dp, ip, C.c_double, C.c_double, ip, ip, dp, dp, dp, vp]
     lib.ofdft_ionic_potential_gradient.argtypes = [vp, dp, ip, dp, dp, ip, C.c_double, ip, ip, vp, vp]

@@ -4,6 +4,8 @@
 // sweeps over its own vectors:
 //   update     x += alpha p;  r -= alpha (q - phi (phi.q) / S);  sums r.r and phi.r
 //   direction  p = (r - phi (phi.r) / S) + beta p                (the projection is applied here, so p stays in the subspace)
+// Preconditioned mode (opt-in): the direction is formed from z = M^-1 r, which the caller writes, by two sweeps in
+// front of the product (sums r.z, phi.z; p = (z - phi (phi.z) / S) + beta p), and the update sweep is followed by none.
 // Reductions as in lbfgs_kernels.h: fixed order, wavefront shuffles, no atomics -- bitwise reproducible.
 #pragma once
 #include "pointwise_kernels.h"
@@ -79,6 +81,35 @@ static __global__ __launch_bounds__(kRedThreads) void cg_direction_kernel(const 
         cplx pi = cg_ld(p, i, n2, n);
         pi.x = (ri.x - s * f.x) + beta * pi.x;
         pi.y = (ri.y - s * f.y) + beta * pi.y;
+        cg_st(p, i, n2, n, pi);
+    }
+}
+
+// ---- preconditioned mode: the caller writes z = M^-1 r between the update sweep and these two
+// sums r.z and phi.z
+static __global__ __launch_bounds__(kRedThreads) void cg_pre_dots_kernel(const real* __restrict__ phi, const real* __restrict__ r,
+                                                                         const real* __restrict__ z, long long n, acc_t* __restrict__ partial) {
+    acc_t acc[2] = {0.0, 0.0};
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), ri = cg_ld(r, i, n2, n), zi = cg_ld(z, i, n2, n);
+        acc[0] += ri.x * zi.x + ri.y * zi.y;
+        acc[1] += f.x * zi.x + f.y * zi.y;
+    }
+    block_reduce_store<2>(acc, partial);
+}
+
+// direction sweep (s = phi.z / S): p = (z - s phi) + beta p; FIRST: p = z - s phi (beta = 0, whatever p holds)
+template <bool FIRST>
+static __global__ __launch_bounds__(kRedThreads) void cg_pre_direction_kernel(const real* __restrict__ phi, const real* __restrict__ z,
+                                                                              real beta, real s, real* __restrict__ p, long long n) {
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), zi = cg_ld(z, i, n2, n);
+        cplx pi = mkc(zi.x - s * f.x, zi.y - s * f.y);
+        if (!FIRST) {
+            const cplx po = cg_ld(p, i, n2, n);
+            pi.x += beta * po.x;
+            pi.y += beta * po.y;
+        }
         cg_st(p, i, n2, n, pi);
     }
 }

@@ -237,3 +237,48 @@ int ofdft_hessian_vector_chi(ofdft_ctx* c, const void* chi_dev, const void* dir_
     }
     return OFDFT_OK;
 }
+
+// z = irfftn(rfftn(r) / (k^2 + kappa2)): the kinetic preconditioner of the conjugate gradients (include/ofdft_hip.h).
+// The solver calls it between products that run with reuse_density = 1, so it goes round begin_call, like the first-order ion
+// entries (engine_ions_stress.inc.h): hvp_valid and hvp_chi_S stay, which is sound because the one workspace it takes is the
+// spectrum "s0", transient in every product, and no "hv:*" field.
+int ofdft_precondition(ofdft_ctx* c, const void* r_dev, void* z_dev, double kappa2, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "ofdft_precondition is served by single-GPU contexts: slab-decomposed contexts have no preconditioner");
+    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    if (!r_dev || !z_dev) return fail(c, OFDFT_EINVAL, "null argument");
+    if (!(kappa2 > 0.0) || !std::isfinite(kappa2)) return fail(c, OFDFT_EINVAL, "ofdft_precondition: kappa2 must be positive and finite");
+    if (z_dev == r_dev) return fail(c, OFDFT_EINVAL, "ofdft_precondition: z_dev must not be r_dev (the transform is not in place)");
+    const real* r = (const real*)r_dev;
+    real* z = (real*)z_dev;
+    const double inv_n = 1.0 / (double)c->npts;
+    const MixScale<SPEC_SCREENED> mix{c->kg, (real)kappa2, (real)0.0};
+    cplx* s0;
+    if (int rc = spec_ws(c, "s0", &s0)) return rc;
+    if (c->fast && !c->force_unfused) {            // z + y | x with the multiply inside | y + z: five spectrum passes
+        if (int rc = fwd_zy(c, r, s0, st)) return rc;
+        XfIo io{};
+        io.in[0] = s0;
+        io.out[0] = s0;
+        if (int rc = xfused<1, 1>(c, io, mix, st, "xfused_pre")) return rc;
+        if (int rc = inv_yz(c, s0, z, inv_n, st)) return rc;
+    } else if (bluestein_xmix_ok(c) && !c->force_unfused) {      // chirp-z extents: the same shape around the x-mix kernel
+        const real* in[1] = {r};
+        cplx* sp[1] = {s0};
+        real* out[1] = {z};
+        if (int rc = bluestein_fwd_zy_multi(c, in, sp, 1, st)) return rc;
+        if (int rc = bluestein_xmix<1, 1>(c, sp, sp, mix, st)) return rc;
+        if (int rc = bluestein_inv_yz_multi(c, sp, out, 1, inv_n, st)) return rc;
+    } else {                                       // forward, multiply, inverse: seven passes
+        if (int rc = rfftn_internal(c, r, s0, st)) return rc;
+        OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_SCREENED>), dim3(grid_for(c->g.total)), dim3(256), 0, (const cplx*)s0, s0, c->kg,
+                     (real)kappa2, (real)0.0);
+        if (int rc = irfftn_internal(c, s0, z, inv_n, st)) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipGetLastError());
+    if (c->profiling) prof_collect(c);
+    return OFDFT_OK;
+}

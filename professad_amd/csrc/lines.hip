@@ -277,6 +277,9 @@ int bluestein_xmix(ofdft_ctx* c, const cplx* const* in, cplx* const* out, const 
 template int bluestein_xmix<1, 1, MixScale<SPEC_HARTREE>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_HARTREE>&, hipStream_t);
 template int bluestein_xmix<1, 1, MixScale<SPEC_LAPLACE>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_LAPLACE>&, hipStream_t);
 template int bluestein_xmix<1, 1, MixScale<SPEC_LINDHARD>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_LINDHARD>&, hipStream_t);
+#ifndef OFDFT_REAL_F32      // ofdft_precondition: fp64 library only
+template int bluestein_xmix<1, 1, MixScale<SPEC_SCREENED>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixScale<SPEC_SCREENED>&, hipStream_t);
+#endif
 template int bluestein_xmix<1, 3, MixDensity<false, true>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDensity<false, true>&, hipStream_t);
 template int bluestein_xmix<1, 4, MixDensity<true, true>>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDensity<true, true>&, hipStream_t);
 template int bluestein_xmix<3, 1, MixDiv>(ofdft_ctx*, const cplx* const*, cplx* const*, const MixDiv&, hipStream_t);

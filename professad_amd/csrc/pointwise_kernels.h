@@ -272,8 +272,8 @@ __device__ __forceinline__ float lindhard_shape(float eta) {
     return f;
 }
 
-enum { SPEC_HARTREE = 0, SPEC_LAPLACE = 1, SPEC_LINDHARD = 2, SPEC_LAPLACE_AC = 3 };
-// out = in * f(k); p0,p1 parameters (LINDHARD: p0 = prefactor, p1 = 1/(2 kF))
+enum { SPEC_HARTREE = 0, SPEC_LAPLACE = 1, SPEC_LINDHARD = 2, SPEC_LAPLACE_AC = 3, SPEC_SCREENED = 4 };
+// out = in * f(k); p0,p1 parameters (LINDHARD: p0 = prefactor, p1 = 1/(2 kF); SCREENED: p0 = kappa^2 > 0, f = 1 / (k^2 + kappa^2))
 template <int OP>
 __global__ void spec_scale_kernel(const cplx* __restrict__ in, cplx* __restrict__ out, KGeom kg, real p0, real p1) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < kg.g.total; i += (long long)gridDim.x * blockDim.x) {
@@ -282,6 +282,7 @@ __global__ void spec_scale_kernel(const cplx* __restrict__ in, cplx* __restrict_
         real f;
         if (OP == SPEC_HARTREE) f = (k2 != 0.0) ? 4.0 * kPiR / k2 : 0.0;              // functionals.py:67-70
         else if (OP == SPEC_LAPLACE) f = -k2;                                       // functional_tools.py:227
+        else if (OP == SPEC_SCREENED) f = (real)1.0 / (k2 + p0);                    // the kinetic preconditioner
         else f = p0 * lindhard_shape((k2 != 0.0) ? sqrt(k2) * p1 : 0.0);            // functionals.py:637-638,648
         const cplx a = in[i];
         out[i] = mkc(a.x * f, a.y * f);
@@ -728,6 +729,7 @@ template <int OP> struct MixScale {
         kvec_xyz(kg, x, y, z, kx, ky, kz, k2);
         if (OP == SPEC_HARTREE) return (k2 != 0.0) ? 4.0 * kPiR / k2 : 0.0;
         if (OP == SPEC_LAPLACE) return -k2;
+        if (OP == SPEC_SCREENED) return (real)1.0 / (k2 + p0);
         return p0 * lindhard_shape((k2 != 0.0) ? sqrt(k2) * p1 : 0.0);
     }
 };

@@ -6,6 +6,9 @@ namespace eng {
 template int xfused<3, 3, MixWgc>(ofdft_ctx*, const XfIo&, const MixWgc&, hipStream_t, const char*, const XfLayout&);
 template int xfused<1, 1, MixScale<SPEC_LAPLACE>>(ofdft_ctx*, const XfIo&, const MixScale<SPEC_LAPLACE>&, hipStream_t, const char*, const XfLayout&);
 template int xfused<1, 1, MixScale<SPEC_LAPLACE_AC>>(ofdft_ctx*, const XfIo&, const MixScale<SPEC_LAPLACE_AC>&, hipStream_t, const char*, const XfLayout&);
+#ifndef OFDFT_REAL_F32      // ofdft_precondition: fp64 library only
+template int xfused<1, 1, MixScale<SPEC_SCREENED>>(ofdft_ctx*, const XfIo&, const MixScale<SPEC_SCREENED>&, hipStream_t, const char*, const XfLayout&);
+#endif
 template int xfused<1, 1, MixScale<SPEC_LINDHARD>>(ofdft_ctx*, const XfIo&, const MixScale<SPEC_LINDHARD>&, hipStream_t, const char*, const XfLayout&);
 template int xfused<1, 1, MixNlk<1>>(ofdft_ctx*, const XfIo&, const MixNlk<1>&, hipStream_t, const char*, const XfLayout&);
 template int xfused<2, 2, MixNlk<2>>(ofdft_ctx*, const XfIo&, const MixNlk<2>&, hipStream_t, const char*, const XfLayout&);

@@ -537,6 +537,10 @@ class DistEngine:
         raise NotImplementedError('DistEngine.hessian_vector_chi: the Hessian-vector product (ofdft_hessian_vector_chi) is served by '
                                   'single-GPU contexts; slab-decomposed contexts have no second derivative')
 
+    def precondition(self, r, kappa2, out=None):
+        raise NotImplementedError('DistEngine.precondition: the kinetic preconditioner (ofdft_precondition) is served by '
+                                  'single-GPU contexts; slab-decomposed contexts have no second derivative to precondition')
+
     def query(self, what):
         return self.stages.query(what)
 

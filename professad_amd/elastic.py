@@ -84,7 +84,8 @@ def bulk_from_w2(W2, W1, volume):
     return (np.einsum('iikk->', W2) + 6.0 * volume * P) / (9.0 * volume), P
 
 
-def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b3', backend=None, pme_order=None):
+def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b3', backend=None, pme_order=None,
+                      precondition=None):
     """Elastic constants (Birch coefficients) C_ijkl = d sigma_ij / d eps_kl at the ground state `chi`, with the relaxation of the
     density under the strain included.
 
@@ -98,18 +99,23 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
     `symmetry_residual` = max|C - C^T| / max|C| of the 6 x 6 matrix before the reference's mirroring; `iterations`,
     `rel_residual`, `reason` (lists over the six solves, in the order xx, yy, zz, yz, xz, xy), `hvp_count`, and
     `ground_state_gradient` = max|g| / dV of the closure at `chi`.  A solve that ends for another reason than convergence raises
-    a warning: the conjugate gradients are unpreconditioned and their iteration count grows with the grid.
+    a warning: unpreconditioned, the iteration count of the conjugate gradients grows with the grid; `precondition` (None, 'auto'
+    or kappa^2 > 0, `optimize.HipCgBackend`) takes the grid out of it.
 
     NotImplementedError, before any device work and naming the cause: PME, a slab-decomposed engine, an fp32 engine, a term
     without a second derivative.  (`backend`: an object with HipElasticBackend's methods -- the tests' numpy double.)"""
     f = unit_factor(units)
     species, frac, charges = optimize.normalise_species(species)
+    optimize._own_backend_only('elastic_constants', backend, precondition)
+    optimize.check_precondition(precondition)
     if backend is None:
         why = refusal(engine, pme_order)
         if why:
             raise NotImplementedError('elastic_constants: ' + why)
     b = backend if backend is not None else HipElasticBackend(engine, box_vecs, species)
     try:
+        if precondition is not None:
+            b.cg.set_precondition(precondition)
         vol = b.volume
         n_elec = float(charges.sum())
         S = float((chi * chi).sum())

@@ -5,6 +5,7 @@ produced by the HIP library behind the C ABI.  There is no CPU path: constructio
 library or a GPU is missing.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -249,6 +250,29 @@ class Engine:
         self._check(self.lib.ofdft_hessian_vector_chi(self._ctx, _ptr(chi), _ptr(d), _ptr(g), float(n_elec), _ptr(out), s,
                                                       1 if reuse_density else 0, self._stream()), 'ofdft_hessian_vector_chi')
         return (dict(zip(N.HVC_NAMES, s)), out) if want_scalars else out
+
+    def precondition(self, r, kappa2, out=None):
+        """The kinetic preconditioner of the conjugate gradients (ofdft_precondition):
+        z = irfftn(rfftn(r) / (k^2 + kappa2)) with kappa2 > 0 [1/bohr^2] -> z (``out`` if given; never ``r`` itself).
+        Needs the cell only, not the terms; leaves what ``hessian_vector[_chi]`` retains for ``reuse_density=True`` valid.
+        Single GPU and fp64."""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.precondition: the kinetic preconditioner is fp64 work (libofdft_hip.so); '
+                                      'an fp32 engine does not serve it')
+        if self.shape != self.global_shape:
+            raise NotImplementedError('Engine.precondition: the kinetic preconditioner is served by single-GPU contexts')
+        kappa2 = float(kappa2)
+        if not (kappa2 > 0.0 and math.isfinite(kappa2)):
+            raise ValueError('Engine.precondition: kappa2 must be positive and finite, got %r' % kappa2)
+        r = self._grid_tensor(r, 'r')
+        if out is None:
+            out = torch.empty_like(r)
+        elif self._grid_tensor(out, 'out') is not out:
+            raise ValueError('out must be a contiguous grid tensor of this engine')
+        if out.data_ptr() == r.data_ptr():
+            raise ValueError('Engine.precondition: z is r -- the transform is not in place, give another `out`')
+        self._check(self.lib.ofdft_precondition(self._ctx, _ptr(r), _ptr(out), kappa2, self._stream()), 'ofdft_precondition')
+        return out
 
     @property
     def volume(self):

@@ -40,7 +40,7 @@ def refusal(engine, pme_order=None):
 
 
 def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b2',
-                    impose_asr=False, backend=None, pme_order=None):
+                    impose_asr=False, backend=None, pme_order=None, precondition=None):
     """Phi[p, b, i, j] = -dF[p, i] / dR[b, j] for p in `primitive_ion_indices` (default: every ion) and all ions b.
 
     engine: a single-GPU fp64 `Engine` with the caller's term set (it includes ion_electron) on the cell `box_vecs`.
@@ -54,8 +54,9 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
     max|sum_b Phi[p, b]| / max|Phi| -- the acoustic sum rule holds only as far as the fixed grid is translation invariant (the
     pointwise nonlinear terms alias: about 1e-3 at 16^3 for fcc Al), so this is reported, and `impose_asr=True` restores it by
     correcting the diagonal block with the row sum; `ground_state_gradient` = max|g| / dV of the closure at `chi`.
-    A solve that ends for another reason than convergence raises a warning: the conjugate gradients are unpreconditioned and their
-    iteration count grows with the grid (about 100 at 16^3, 400 at 64^3 for fcc Al), so larger grids need a larger `maxiter`.
+    A solve that ends for another reason than convergence raises a warning: unpreconditioned, the iteration count of the conjugate
+    gradients grows with the grid (about 100 at 16^3, 400 at 64^3 for fcc Al), so larger grids need a larger `maxiter` -- or
+    `precondition`: None, 'auto' or kappa^2 > 0 (`optimize.HipCgBackend`), the kinetic preconditioner, about 20 iterations at any grid.
 
     NotImplementedError, before any device work and naming the cause: PME, a slab-decomposed engine, an fp32 engine, a term
     without a second derivative.  (`backend`: an object with HipFcBackend's methods -- the tests' numpy double.)"""
@@ -66,12 +67,16 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
     rows = list(range(nions)) if primitive_ion_indices is None else [int(p) for p in primitive_ion_indices]
     if not rows or min(rows) < 0 or max(rows) >= nions:
         raise ValueError('primitive_ion_indices must name at least one ion, each in [0, %d)' % nions)
+    optimize._own_backend_only('force_constants', backend, precondition)
+    optimize.check_precondition(precondition)
     if backend is None:
         why = refusal(engine, pme_order)
         if why:
             raise NotImplementedError('force_constants: ' + why)
     b = backend if backend is not None else HipFcBackend(engine, box_vecs, species)
     try:
+        if precondition is not None:
+            b.cg.set_precondition(precondition)
         n_elec = float(charges.sum())
         S = float((chi * chi).sum())
         n = (n_elec / (S * b.dV)) * chi * chi

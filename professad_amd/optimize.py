@@ -19,7 +19,9 @@ of the direction in the basis {S_j, Y_j, g}.  On several ranks the sweep's local
 
 `TruncatedNewton` (`n_method='TN'`, the optimiser PROFESS itself defaults to) and `density_response` are the second-order
 consumers: both solve with the Hessian of E[chi] by conjugate gradients whose vectors live behind `ofdft_cg_*` and whose
-products are `ofdft_hessian_vector_chi` (`HipCgBackend`, `solve_projected`).  Single GPU, fp64.
+products are `ofdft_hessian_vector_chi` (`HipCgBackend`, `solve_projected`).  Single GPU, fp64.  With
+`precondition` (off by default) the solve is preconditioned by the kinetic operator 1 / (k^2 + kappa^2) (`ofdft_precondition`;
+DESIGN.md §9i), which takes the grid out of its iteration count.
 """
 import ctypes as C
 import math
@@ -449,14 +451,32 @@ def _vp(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def check_precondition(value):
+    """the `precondition` argument of the second-order entries: None (plain conjugate gradients), 'auto' or kappa^2 > 0"""
+    if value is None or value == 'auto':
+        return value
+    if isinstance(value, (int, float)) and not isinstance(value, bool) and value > 0.0 and math.isfinite(value):
+        return float(value)
+    raise ValueError("precondition must be None, 'auto' or a positive finite kappa^2 [1/bohr^2], got %r" % (value,))
+
+
+def kinetic_kappa2(n_elec, volume):
+    """kappa^2 = (4/3) k_F^2 of the mean density: the Thomas-Fermi part of the shift the Hessian adds to c dV (-lap)"""
+    return (4.0 / 3.0) * (3.0 * math.pi ** 2 * n_elec / volume) ** (2.0 / 3.0)
+
+
 class HipCgBackend:
     """Conjugate gradients for P H P x = b on the device (ofdft_cg_* and ofdft_hessian_vector_chi in libofdft_hip.so; no CPU
-    fallback): x, r, p, q live behind the handle, the engine's product reads p and writes q in place."""
+    fallback): x, r, p, q live behind the handle, the engine's product reads p and writes q in place.
+    `precondition`: None (plain), 'auto' (kappa^2 = (4/3) (3 pi^2 N / vol)^(2/3) from the `n_elec` of each solve) or kappa^2 > 0:
+    every iteration then opens with z = F^-1[r^ / (k^2 + kappa^2)] (`ofdft_precondition`) and `ofdft_cg_direction`; `set_precondition`
+    changes it between solves."""
 
-    def __init__(self, engine):
+    def __init__(self, engine, precondition=None):
         why = second_order_refusal(engine)
         if why:
             raise NotImplementedError(why)
+        self.precondition = check_precondition(precondition)
         self.eng, self.lib = engine, engine.lib
         self.dV = engine.volume / engine.npts
         self._h = C.c_void_p(0)
@@ -466,6 +486,15 @@ class HipCgBackend:
         self._p, self._q = C.c_void_p(0), C.c_void_p(0)
         self._check(self.lib.ofdft_cg_vectors(self._h, None, None, C.byref(self._p), C.byref(self._q)), 'ofdft_cg_vectors')
         self._scal = (C.c_double * 5)()
+        self._r, self._z = C.c_void_p(0), C.c_void_p(0)
+
+    @property
+    def preconditioned(self):
+        return self.precondition is not None
+
+    def set_precondition(self, precondition):
+        """takes effect at the next `start`"""
+        self.precondition = check_precondition(precondition)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -474,6 +503,10 @@ class HipCgBackend:
     def start(self, phi, b, rtol, maxiter):
         e = self.eng
         phi, b = e._grid_tensor(phi, 'chi'), e._grid_tensor(b, 'b')          # (held until the call returns)
+        self._check(self.lib.ofdft_cg_set_preconditioned(self._h, 1 if self.preconditioned else 0), 'ofdft_cg_set_preconditioned')
+        if self.preconditioned and not self._z:
+            self._check(self.lib.ofdft_cg_vectors(self._h, None, C.byref(self._r), None, None), 'ofdft_cg_vectors')
+            self._check(self.lib.ofdft_cg_z(self._h, C.byref(self._z)), 'ofdft_cg_z')
         self._check(self.lib.ofdft_cg_start(self._h, _vp(phi), _vp(b), float(rtol), int(maxiter), None, e._stream()), 'ofdft_cg_start')
 
     def product(self, phi, g, n_elec, reuse):
@@ -483,6 +516,16 @@ class HipCgBackend:
         e._check(self.lib.ofdft_hessian_vector_chi(e._ctx, _vp(phi), self._p, _vp(g), float(n_elec), self._q, self._scal,
                                                    1 if reuse else 0, e._stream()), 'ofdft_hessian_vector_chi')
         return self._scal[0], self._scal[1]
+
+    def pre_direction(self, phi, n_elec):
+        """preconditioned mode, in front of every product: z = M^-1 r, then p = P z + beta p -> exit reason"""
+        e = self.eng
+        kappa2 = kinetic_kappa2(n_elec, e.volume) if self.precondition == 'auto' else self.precondition
+        e._check(self.lib.ofdft_precondition(e._ctx, self._r, self._z, float(kappa2), e._stream()), 'ofdft_precondition')
+        reason = C.c_int(0)
+        phi = e._grid_tensor(phi, 'chi')
+        self._check(self.lib.ofdft_cg_direction(self._h, _vp(phi), None, C.byref(reason), e._stream()), 'ofdft_cg_direction')
+        return reason.value
 
     def step(self, phi, p_dot_q, phi_dot_q):
         reason = C.c_int(0)
@@ -519,11 +562,16 @@ class HipCgBackend:
 def solve_projected(backend, phi, g, b, n_elec, rtol, maxiter):
     """Conjugate gradients for P H P x = b at phi (P = I - phi phi^T / phi.phi; g: the closure gradient there, None at a stationary
     point) until |r| <= rtol |b|, `maxiter` iterations or non-positive curvature.  The first product runs with reuse_density = 0,
-    the others with 1.  -> (x, iterations, exit reason CG_*, |r| / |b|, products)"""
+    the others with 1.  A backend whose `preconditioned` is true forms its direction in `pre_direction` before every product
+    (z = M^-1 r, p = P z + beta p); the stopping rule is the same, on the unpreconditioned residual.
+    -> (x, iterations, exit reason CG_*, |r| / |b|, products)"""
     backend.start(phi, b, rtol, maxiter)
     _it, reason, _rel = backend.status()
+    pre = bool(getattr(backend, 'preconditioned', False))
     products = 0
     while reason == CG_RUNNING:
+        if pre and backend.pre_direction(phi, n_elec) != CG_RUNNING:
+            break
         pq, phiq = backend.product(phi, g, n_elec, products > 0)
         products += 1
         reason = backend.step(phi, pq, phiq)
@@ -581,14 +629,22 @@ class TruncatedNewton:
         return E
 
 
-def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=None):
+def _own_backend_only(who, backend, precondition):
+    if backend is not None and precondition is not None:
+        raise ValueError('%s: `precondition` configures the backend the call builds; with `backend` given, set it on that backend' % who)
+
+
+def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=None, precondition=None):
     """First-order change of the ground-state density under a perturbation `dv` of the external potential, at the ground state
     `chi` (any scale) of the engine's terms: the implicit derivative of the minimiser, one conjugate-gradient solve with the
     Hessian of E[chi],  P H P dchi = -2 c chi (dv - sum(dv n) dV / N) dV  with g = 0.  Returns a dict with dn = 2 c chi dchi
     (sum dn = 0), dmu = sum n (hv(n, dn) + dv) dV / N, the iteration count, the relative residual and the exit reason.
     Single GPU, fp64 and the terms `Engine.hessian_vector` serves; anything else raises NotImplementedError.  (`backend`: another
-    solver with HipCgBackend's methods -- the tests' numpy double.)"""
-    b = backend if backend is not None else HipCgBackend(engine)
+    solver with HipCgBackend's methods -- the tests' numpy double.)  `precondition`: None, 'auto' or kappa^2 > 0, as `HipCgBackend`
+    takes it: the kinetic preconditioner, which makes the iteration count independent of the grid; the result is the same
+    solution to `rtol`."""
+    _own_backend_only('density_response', backend, precondition)
+    b = backend if backend is not None else HipCgBackend(engine, precondition)
     dV = b.dV
     S = float((chi * chi).sum())
     c = n_elec / (S * dV)
@@ -665,8 +721,8 @@ def log_solve(log, r):
 
 
 def warn_unconverged(who, log, maxiter, what):
-    """The conjugate gradients are unpreconditioned: their iteration count grows with the grid, so a solve may end
-    at maxiter.  `what`: what is then not accurate."""
+    """Without `precondition` the iteration count of the conjugate gradients grows with the grid, so a solve
+    may end at maxiter.  `what`: what is then not accurate."""
     import warnings
     bad = sum(x != CG_CONVERGED for x in log['reason'])
     if bad:
@@ -676,7 +732,7 @@ def warn_unconverged(who, log, maxiter, what):
 
 def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_cond_count=3, n_step_size=0.1,
                      n_maxiter=1000, conv_target='dE', verbose=False, volume=None, optimizer='fused', n_method='LBFGS',
-                     tn_cg_maxiter=50, tn_gtol=1e-10):
+                     tn_cg_maxiter=50, tn_gtol=1e-10, tn_precondition=None):
     """Minimise E[n = N_e chi^2 / int chi^2] with the engine's terms.  Returns a dict with the converged density,
     chi, energy [Ha], iteration count and the convergence history.
 
@@ -690,11 +746,15 @@ def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_con
     `n_method`: 'LBFGS', 'TPGD' (the reference's two) or 'TN', truncated Newton (`TruncatedNewton`: at most `tn_cg_maxiter`
     Hessian-vector products per Newton equation, no step once |g|_2 <= `tn_gtol`); 'TN' needs a single-GPU fp64 `Engine` whose
     terms all have a second derivative, and raises NotImplementedError otherwise.  The result's `hvp_count` is the number of
-    Hessian-vector products taken (0 for the other methods)."""
+    Hessian-vector products taken (0 for the other methods).  `tn_precondition`: None, 'auto' or kappa^2 > 0, the kinetic
+    preconditioner of the Newton equations (`HipCgBackend`); ValueError with another method."""
     if conv_target not in ('dE', 'dEdchi', 'euler'):
         raise ValueError("Only 'dE', 'dEdchi' or 'euler' recognized as 'conv_target' argument")       # system.py:889-890
     if n_method not in ('LBFGS', 'TPGD', 'TN'):
         raise ValueError("Only 'LBFGS', 'TPGD' or 'TN' recognized for 'n_method' argument")           # system.py:826
+    if tn_precondition is not None and n_method != 'TN':
+        raise ValueError("tn_precondition belongs to n_method='TN'")
+    check_precondition(tn_precondition)
     if n_method == 'TN':
         why = second_order_refusal(engine)
         if why:
@@ -738,7 +798,7 @@ def optimize_density(engine, n_elec, vext=None, chi0=None, ntol=1e-7, n_conv_con
         return state['E'], g
 
     if n_method == 'TN':
-        opt = TruncatedNewton(chi, HipCgBackend(engine), n_elec, cg_maxiter=tn_cg_maxiter, tolerance_grad=tn_gtol)
+        opt = TruncatedNewton(chi, HipCgBackend(engine, tn_precondition), n_elec, cg_maxiter=tn_cg_maxiter, tolerance_grad=tn_gtol)
     elif n_method == 'TPGD':        # system.py:823-824
         hook = (lambda v: comm.all_reduce_sum(np.ascontiguousarray(v, dtype=np.float64), dev)) if multi else None
         opt = TwoPointGradientDescent(chi, lr=n_step_size, all_reduce=hook)
