@@ -30,7 +30,7 @@
  *   - precision: the ABI is built once per precision from the same sources -- libofdft_hip.so (OFDFT_F64, the
  *     reference's precision) and libofdft_hip_f32.so (OFDFT_F32, same symbols; grid arrays are float / float2, every
  *     host-visible scalar stays double).  ofdft_create refuses the dtype of the other build.  The fp32 library serves
- *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points, ofdft_hessian_vector, ofdft_hessian_vector_chi and ofdft_precondition are fp64-only and return OFDFT_EINVAL there.
+ *     the evaluation path and ofdft_lbfgs_*; the ion / stress entry points, ofdft_hessian_vector, ofdft_hessian_vector_chi[_multi] and ofdft_precondition[_multi] are fp64-only and return OFDFT_EINVAL there.
  *   - energies are Hartree; lengths bohr; box_vecs rows are the lattice vectors (reference layout).
  */
 #ifndef OFDFT_HIP_H
@@ -336,6 +336,29 @@ int  ofdft_hessian_vector_chi(ofdft_ctx* ctx, const void* chi_dev, const void* d
  * contexts return OFDFT_EINVAL, as do kappa2 <= 0 or non-finite and z_dev == r_dev.  Synchronises the stream.  No atomics. */
 int  ofdft_precondition(ofdft_ctx* ctx, const void* r_dev, void* z_dev, double kappa2, void* stream);
 
+/* Several right-hand sides per call.  The response drivers solve with the same Hessian for many perturbations;
+ * these entries run the stationary-point product (g = 0) and the preconditioner for ncols = 1 .. OFDFT_MULTI_MAX columns at once.
+ * Column j of a stack is base + j * stride elements (stride >= the points of a column; any parity).
+ *   ofdft_hessian_vector_chi_multi  out_j = H d_j as ofdft_hessian_vector_chi forms it with g_dev = NULL, to rounding (not
+ *       bitwise: the density-only factors of a point are formed once and serve every column).  One sweep and one fetch for all
+ *       a_j = phi . d_j and S; one head kernel that reads phi once and writes the density-only fields once; the transforms in
+ *       batches through the whole-grid transforms (chirp-z extents: up to four fields per launch; the fused radix extents one
+ *       field per launch); one spectral kernel over every spectrum; one combine kernel; one reduction; one shift; one
+ *       synchronisation.  scalars_host [ncols][OFDFT_HVC_NSCALARS], in the order of the single-column entry.  The retained
+ *       density fields are those of ofdft_hessian_vector_chi: with reuse_density = 1 either entry may follow a reuse_density = 0
+ *       call of the other on the same phi, cell and term set, and what invalidates them for one invalidates them for both.
+ *       OFDFT_Q_FFT_COUNT: 2 (D + ncols W), with reuse 2 ncols W (D density-only, W per-direction transforms of the term set).
+ *   ofdft_precondition_multi  z_j = irfftn(rfftn(r_j) / (k^2 + kappa2)), one synchronisation at the end; leaves the retained
+ *       fields alone like ofdft_precondition.
+ * OFDFT_EINVAL, the message naming the limit or the argument: ncols outside 1 .. OFDFT_MULTI_MAX, a stride below the points of a
+ * column, an output stack that overlaps the input stack, and whatever the single-column entries refuse.  fp64, single GPU. */
+#define OFDFT_MULTI_MAX 8
+int  ofdft_hessian_vector_chi_multi(ofdft_ctx* ctx, const void* chi_dev, const void* dirs_dev, long long dir_stride, int ncols,
+                                    double n_electrons, void* out_dev, long long out_stride,
+                                    double* scalars_host /* [ncols][OFDFT_HVC_NSCALARS] or NULL */, int reuse_density, void* stream);
+int  ofdft_precondition_multi(ofdft_ctx* ctx, const void* r_dev, long long r_stride, void* z_dev, long long z_stride, int ncols,
+                              double kappa2, void* stream);
+
 /* Ion-ion interaction: the real-space damped pair sum in a neutralising background of
  * ion_interaction_sum (ion_utils.py:293-333) with System.__ion_ion_interaction's parameters (system.py:733-754);
  * Rc <= 0 selects its default Rd = 2 h_max, Rc = 3 Rd^2 / h_max.  The pair list (torch-nl's neighbour list in the
@@ -508,6 +531,35 @@ int  ofdft_cg_solution(ofdft_cg* h, void* x_out_dev, void* stream);
 int  ofdft_cg_set_preconditioned(ofdft_cg* h, int on);
 int  ofdft_cg_z(ofdft_cg* h, void** z_dev);
 int  ofdft_cg_direction(ofdft_cg* h, const void* phi_dev, double* info_host /* [4] or NULL */, int* reason, void* stream);
+
+/* ---- the same solver for several right-hand sides in lockstep ------------------------------------
+ * A handle for (n, ncols_max <= OFDFT_MULTI_MAX, device) holds x, r, p, q, z as [ncols_max] columns at the stride that
+ * ofdft_cgm_vectors reports (n rounded up to even), and per column rho, phi . r, |r|^2, |r_0|^2, the iteration count and the exit
+ * reason.  Not block Krylov: the columns share phi and S only, and each runs the recurrence of ofdft_cg_* with its own alpha and
+ * beta, so a column's result, reason and count are those of a solo solve (its sums are formed in the solo kernels' order).
+ * Every sweep is one launch for all columns -- the column is the grid's y index, the per-column coefficients travel by value --
+ * and one fetch of all columns' sums.  A column that has ended (converged, curvature, maxiter, NaN) is frozen: no later sweep
+ * writes its x or r, and its reason and count stay.  The caller's product (ofdft_hessian_vector_chi_multi on p -> q of all
+ * ncols columns) goes on computing a frozen column's q, which nothing reads: the product's cost per column is small beside
+ * what the columns share, and the columns of one ground state end within a few iterations of each other.
+ *   ofdft_cgm_start      b_j at b_stride, ncols <= ncols_max; info_host [ncols][3] as ofdft_cg_start.  b_j = 0: converged, x_j = 0.
+ *   ofdft_cgm_step       p_dot_q [ncols], phi_dot_q [ncols] (those of ended columns are not read); *running = columns still running.
+ *   ofdft_cgm_direction  preconditioned mode, with z_j = M^-1 r_j written for the running columns; info_host [ncols][4].
+ *   ofdft_cgm_status     of column col.        ofdft_cgm_solution copies the x_j to the caller's stack at its stride.
+ * OFDFT_ESTATE as for ofdft_cg_*, "ended" meaning every column; OFDFT_EINVAL names the limit.  No atomics. */
+typedef struct ofdft_cgm ofdft_cgm;
+int  ofdft_cgm_create(ofdft_cgm** out, long long n, int ncols_max, int device_id);
+void ofdft_cgm_destroy(ofdft_cgm* h);
+const char* ofdft_cgm_last_error(const ofdft_cgm* h);
+int  ofdft_cgm_vectors(ofdft_cgm* h, void** x_dev, void** r_dev, void** p_dev, void** q_dev, long long* stride);
+int  ofdft_cgm_z(ofdft_cgm* h, void** z_dev);
+int  ofdft_cgm_set_preconditioned(ofdft_cgm* h, int on);
+int  ofdft_cgm_start(ofdft_cgm* h, const void* phi_dev, const void* b_dev, long long b_stride, int ncols, double rtol, int maxiter,
+                     double* info_host /* [ncols][3] or NULL */, void* stream);
+int  ofdft_cgm_step(ofdft_cgm* h, const void* phi_dev, const double* p_dot_q, const double* phi_dot_q, int* running, void* stream);
+int  ofdft_cgm_direction(ofdft_cgm* h, const void* phi_dev, double* info_host /* [ncols][4] or NULL */, int* running, void* stream);
+int  ofdft_cgm_status(const ofdft_cgm* h, int col, int* iterations, int* reason, double* rel_residual);
+int  ofdft_cgm_solution(ofdft_cgm* h, void* x_out_dev, long long stride, void* stream);
 
 /* Tuning / validation switches.  OFDFT_OPT_PIPELINE: 0 = automatic (power-of-two grids: fused x passes and z
  * passes that keep every real-space intermediate on chip), 1 = force the unfused pipeline (separate forward,

@@ -67,6 +67,7 @@ HVC_NAMES = ('dHd', 'phiHd', 'a', 'S', 'dmu')
 HVC_NSCALARS = len(HVC_NAMES)
 CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_CURVATURE = 0, 1, 2, 3
 CG_REASONS = {CG_RUNNING: 'running', CG_CONVERGED: 'converged', CG_MAXITER: 'maxiter', CG_CURVATURE: 'curvature'}
+MULTI_MAX = 8      # OFDFT_MULTI_MAX: columns per call of the *_multi entries and of an ofdft_cgm handle
 
 EXPORTS = ['ofdft_create', 'ofdft_destroy', 'ofdft_last_error', 'ofdft_set_cell', 'ofdft_set_terms',
            'ofdft_set_nlk_table', 'ofdft_energy_potential', 'ofdft_energy_grad_chi', 'ofdft_rfftn', 'ofdft_irfftn', 'ofdft_debug_math', 'ofdft_query',
@@ -74,7 +75,10 @@ EXPORTS = ['ofdft_create', 'ofdft_destroy', 'ofdft_last_error', 'ofdft_set_cell'
            'ofdft_dist_energies', 'ofdft_dist_chi_grad', 'ofdft_ipc_export', 'ofdft_ipc_attach', 'ofdft_ipc_detach', 'ofdft_dist_closure', 'ofdft_ionic_potential', 'ofdft_ion_electron_forces', 'ofdft_stress', 'ofdft_ion_electron_stress', 'ofdft_ion_ion', 'ofdft_ion_ion_cells', 'ofdft_ionic_potential_gradient', 'ofdft_ion_electron_curvature', 'ofdft_ion_ion_hessian',
            'ofdft_potential_strain_gradient', 'ofdft_ionic_potential_strain_gradient', 'ofdft_strain_hessian','ofdft_ion_electron_strain_hessian', 'ofdft_ion_ion_strain_hessian',
            'ofdft_hessian_vector', 'ofdft_hessian_vector_chi', 'ofdft_precondition', 'ofdft_cg_create', 'ofdft_cg_destroy', 'ofdft_cg_last_error', 'ofdft_cg_start',
-           'ofdft_cg_vectors', 'ofdft_cg_step', 'ofdft_cg_status', 'ofdft_cg_solution', 'ofdft_cg_set_preconditioned', 'ofdft_cg_z', 'ofdft_cg_direction', 'ofdft_lbfgs_create', 'ofdft_lbfgs_destroy', 'ofdft_lbfgs_last_error', 'ofdft_lbfgs_reset', 'ofdft_lbfgs_direction', 'ofdft_lbfgs_abs_step', 'ofdft_lbfgs_dots',
+           'ofdft_cg_vectors', 'ofdft_cg_step', 'ofdft_cg_status', 'ofdft_cg_solution', 'ofdft_cg_set_preconditioned', 'ofdft_cg_z', 'ofdft_cg_direction',
+           'ofdft_hessian_vector_chi_multi', 'ofdft_precondition_multi', 'ofdft_cgm_create', 'ofdft_cgm_destroy', 'ofdft_cgm_last_error',
+           'ofdft_cgm_vectors', 'ofdft_cgm_z', 'ofdft_cgm_set_preconditioned', 'ofdft_cgm_start', 'ofdft_cgm_step', 'ofdft_cgm_direction',
+           'ofdft_cgm_status', 'ofdft_cgm_solution', 'ofdft_lbfgs_create', 'ofdft_lbfgs_destroy', 'ofdft_lbfgs_last_error', 'ofdft_lbfgs_reset', 'ofdft_lbfgs_direction', 'ofdft_lbfgs_abs_step', 'ofdft_lbfgs_dots',
            'ofdft_lbfgs_commit', 'ofdft_lbfgs_update', 'ofdft_set_option', 'ofdft_set_collectives', 'ofdft_set_profiling', 'ofdft_profile_count', 'ofdft_profile_get']
 
 
@@ -160,6 +164,22 @@ def load(dtype=F64):
     lib.ofdft_cg_z.argtypes = [vp, C.POINTER(vp)]
     lib.ofdft_cg_direction.argtypes = [vp, vp, dp, C.POINTER(ip), vp]
     lib.ofdft_precondition.argtypes = [vp, vp, vp, C.c_double, vp]
+    ll = C.c_longlong
+    lib.ofdft_hessian_vector_chi_multi.argtypes = [vp, vp, vp, ll, ip, C.c_double, vp, ll, dp, ip, vp]
+    lib.ofdft_precondition_multi.argtypes = [vp, vp, ll, vp, ll, ip, C.c_double, vp]
+    lib.ofdft_cgm_create.argtypes = [C.POINTER(vp), ll, ip, ip]
+    lib.ofdft_cgm_destroy.argtypes = [vp]
+    lib.ofdft_cgm_destroy.restype = None
+    lib.ofdft_cgm_last_error.argtypes = [vp]
+    lib.ofdft_cgm_last_error.restype = C.c_char_p
+    lib.ofdft_cgm_vectors.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ll)]
+    lib.ofdft_cgm_z.argtypes = [vp, C.POINTER(vp)]
+    lib.ofdft_cgm_set_preconditioned.argtypes = [vp, ip]
+    lib.ofdft_cgm_start.argtypes = [vp, vp, vp, ll, ip, C.c_double, ip, dp, vp]
+    lib.ofdft_cgm_step.argtypes = [vp, vp, dp, dp, C.POINTER(ip), vp]
+    lib.ofdft_cgm_direction.argtypes = [vp, vp, dp, C.POINTER(ip), vp]
+    lib.ofdft_cgm_status.argtypes = [vp, ip, C.POINTER(ip), C.POINTER(ip), dp]
+    lib.ofdft_cgm_solution.argtypes = [vp, vp, ll, vp]
     lib.ofdft_ion_ion.argtypes = [vp, dp, dp, ip, C.c_double, dp, dp, dp, vp]
     lib.ofdft_ion_ion_cells.argtypes = [vp, dp, dp, ip, C.c_double, C.c_double, ip, ip, dp, dp, dp, vp]
     lib.ofdft_ionic_potential_gradient.argtypes = [vp, dp, ip, dp, dp, ip, C.c_double, ip, ip, vp, vp]

@@ -255,3 +255,320 @@ int ofdft_cg_status(const ofdft_cg* o, int* iterations, int* reason, double* rel
 }
 
 }  // extern "C"
+
+// ================================================================================================================================
+// Several solves in lockstep (include/ofdft_hip.h): ncols recurrences of the solver above behind one handle, every
+// sweep one launch and one fetch for all columns.  The columns share nothing but phi and S: each keeps its own alpha, beta, rho,
+// phi.r, exit reason and iteration count, and ends on its own; the run ends when every column has.
+struct ofdft_cgm {
+    long long n = 0, ld = 0;         // points per column; column stride of the handle's vectors (n rounded up to even)
+    int ncols_max = 0, ncols = 0, device = 0;
+    real *x = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *z = nullptr;      // [ncols_max][ld]; z on first use
+    bool pre_next = false, pre = false, dir_ready = false, dir_first = false, started = false;
+    double *d_partial = nullptr, *d_out = nullptr, *h_out = nullptr;
+    int maxiter = 0;
+    double S = 0.0, rtol = 0.0;
+    struct Col {
+        double rho = 0.0, phir = 0.0, rr = 0.0, bb = 0.0;
+        int iters = 0, reason = OFDFT_CG_RUNNING;
+    } col[kCgmMax];
+    char err[256] = "";
+};
+
+namespace {
+
+int mfail(ofdft_cgm* o, int code, const char* msg) {
+    if (o) std::snprintf(o->err, sizeof(o->err), "%s", msg);
+    return code;
+}
+#define CGM_TRY(o, expr)                                                          \
+    do {                                                                          \
+        hipError_t e_ = (expr);                                                   \
+        if (e_ != hipSuccess) return mfail(o, OFDFT_EHIP, hipGetErrorString(e_)); \
+    } while (0)
+
+int cgm_blocks(const ofdft_cgm* o) {
+    long long want = (o->n / 2 + kRedThreads) / kRedThreads;
+    return (int)(want < 1 ? 1 : (want > kRedBlocks ? kRedBlocks : want));
+}
+int cgm_ensure_z(ofdft_cgm* o) {
+    if (!o->z) CGM_TRY(o, hipMalloc((void**)&o->z, sizeof(real) * (size_t)o->ld * o->ncols_max));
+    return OFDFT_OK;
+}
+// second-level sums of `ns` scalars per column, all columns in one launch, to the host (one synchronisation): out[col * ns + s].
+// The sums of a column the sweep skipped are not defined; the caller reads those of the columns it ran.
+int cgm_fetch(ofdft_cgm* o, int blocks, int ns, hipStream_t st) {
+    hipLaunchKernelGGL(cgm_reduce_kernel, dim3(ns, o->ncols), dim3(kRedThreads), 0, st, (const double*)o->d_partial, blocks, ns, o->d_out);
+    CGM_TRY(o, hipMemcpyAsync(o->h_out, o->d_out, sizeof(double) * ns * o->ncols, hipMemcpyDeviceToHost, st));
+    CGM_TRY(o, hipStreamSynchronize(st));
+    CGM_TRY(o, hipGetLastError());
+    return OFDFT_OK;
+}
+int cgm_running(const ofdft_cgm* o) {
+    int k = 0;
+    for (int c = 0; c < o->ncols; ++c) k += o->col[c].reason == OFDFT_CG_RUNNING;
+    return k;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofdft_cgm_create(ofdft_cgm** out, long long n, int ncols_max, int device_id) {
+    if (!out || n < 1 || ncols_max < 1 || ncols_max > kCgmMax) return OFDFT_EINVAL;
+    *out = nullptr;
+    ofdft_cgm* o = new (std::nothrow) ofdft_cgm();
+    if (!o) return OFDFT_ENOMEM;
+    o->n = n;
+    o->ld = (n + 1) & ~1LL;
+    o->ncols_max = ncols_max;
+    o->device = device_id;
+    DeviceScope device_scope_(device_id);
+    hipError_t e = device_scope_.err;
+    const size_t vb = sizeof(real) * (size_t)o->ld * ncols_max;
+    for (real** v : {&o->x, &o->r, &o->p, &o->q})
+        if (e == hipSuccess) e = hipMalloc((void**)v, vb);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->d_partial, sizeof(double) * kRedBlocks * 3 * ncols_max);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->d_out, sizeof(double) * 3 * ncols_max);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_out, sizeof(double) * 3 * ncols_max);
+    if (e != hipSuccess) {
+        ofdft_cgm_destroy(o);
+        return e == hipErrorOutOfMemory ? OFDFT_ENOMEM : OFDFT_EHIP;
+    }
+    *out = o;
+    return OFDFT_OK;
+}
+
+void ofdft_cgm_destroy(ofdft_cgm* o) {
+    if (!o) return;
+    DeviceScope device_scope_(o->device);
+    for (real* v : {o->x, o->r, o->p, o->q, o->z})
+        if (v) (void)hipFree(v);
+    if (o->d_partial) (void)hipFree(o->d_partial);
+    if (o->d_out) (void)hipFree(o->d_out);
+    if (o->h_out) (void)hipHostFree(o->h_out);
+    delete o;
+}
+
+const char* ofdft_cgm_last_error(const ofdft_cgm* o) { return o ? o->err : "null handle"; }
+
+int ofdft_cgm_vectors(ofdft_cgm* o, void** x_dev, void** r_dev, void** p_dev, void** q_dev, long long* stride) {
+    if (!o) return OFDFT_EINVAL;
+    if (x_dev) *x_dev = o->x;
+    if (r_dev) *r_dev = o->r;
+    if (p_dev) *p_dev = o->p;
+    if (q_dev) *q_dev = o->q;
+    if (stride) *stride = o->ld;
+    return OFDFT_OK;
+}
+
+int ofdft_cgm_set_preconditioned(ofdft_cgm* o, int on) {
+    if (!o) return OFDFT_EINVAL;
+    o->pre_next = on != 0;
+    return OFDFT_OK;
+}
+
+int ofdft_cgm_z(ofdft_cgm* o, void** z_dev) {
+    if (!o || !z_dev) return OFDFT_EINVAL;
+    DeviceScope device_scope_(o->device);
+    CGM_TRY(o, device_scope_.err);
+    if (int rc = cgm_ensure_z(o)) return rc;
+    *z_dev = o->z;
+    return OFDFT_OK;
+}
+
+int ofdft_cgm_start(ofdft_cgm* o, const void* phi_dev, const void* b_dev, long long b_stride, int ncols, double rtol, int maxiter,
+                    double* info_host, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!o) return OFDFT_EINVAL;
+    if (!phi_dev || !b_dev || !(rtol >= 0.0) || maxiter < 1) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: null argument, negative rtol or maxiter < 1");
+    if (ncols < 1 || ncols > o->ncols_max) {
+        std::snprintf(o->err, sizeof(o->err), "ofdft_cgm_start: ncols = %d is outside 1 .. %d, the ncols_max of this handle (at most OFDFT_MULTI_MAX = %d)",
+                      ncols, o->ncols_max, kCgmMax);
+        return OFDFT_EINVAL;
+    }
+    if (b_stride < o->n) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: b_stride is below the points of a column");
+    DeviceScope device_scope_(o->device);
+    CGM_TRY(o, device_scope_.err);
+    o->started = false;
+    o->pre = o->pre_next;
+    if (o->pre)
+        if (int rc = cgm_ensure_z(o)) return rc;
+    o->ncols = ncols;
+    const real* phi = (const real*)phi_dev;
+    const real* b = (const real*)b_dev;
+    const int blocks = cgm_blocks(o);
+    hipLaunchKernelGGL(cgm_start_dots_kernel, dim3(blocks, ncols), dim3(kRedThreads), 0, st, phi, b, b_stride, o->n, o->d_partial);
+    if (int rc = cgm_fetch(o, blocks, 3, st)) return rc;
+    double s3[kCgmMax][3];
+    for (int c = 0; c < ncols; ++c)
+        for (int s = 0; s < 3; ++s) s3[c][s] = o->h_out[3 * c + s];
+    const double S = s3[0][1];
+    if (!(S > 0.0)) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: phi is zero everywhere");
+    CgmCols cols{};
+    for (int c = 0; c < ncols; ++c) cols.a[c] = (real)(s3[c][2] / S);
+    cols.active = (1u << ncols) - 1u;
+    hipLaunchKernelGGL(cgm_start_kernel, dim3(blocks, ncols), dim3(kRedThreads), 0, st, phi, b, b_stride, cols, o->x, o->r, o->p, o->ld, o->n,
+                       o->d_partial);
+    if (int rc = cgm_fetch(o, blocks, 1, st)) return rc;
+    o->S = S;
+    o->rtol = rtol;
+    o->maxiter = maxiter;
+    o->dir_ready = false;
+    o->dir_first = true;
+    for (int c = 0; c < ncols; ++c) {
+        ofdft_cgm::Col& k = o->col[c];
+        k.rr = k.bb = o->h_out[c];
+        k.rho = k.phir = 0.0;
+        k.iters = 0;
+        k.reason = k.rr > 0.0 ? OFDFT_CG_RUNNING : OFDFT_CG_CONVERGED;      // b = 0: x = 0 solves it
+        if (info_host) {
+            info_host[3 * c] = k.rr;
+            info_host[3 * c + 1] = S;
+            info_host[3 * c + 2] = s3[c][2];
+        }
+    }
+    o->started = true;
+    return OFDFT_OK;
+}
+
+int ofdft_cgm_step(ofdft_cgm* o, const void* phi_dev, const double* p_dot_q, const double* phi_dot_q, int* running, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!o) return OFDFT_EINVAL;
+    if (!phi_dev || !p_dot_q || !phi_dot_q || !running) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_step: null argument");
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: ofdft_cgm_start has not been called");
+    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: every column has ended (ofdft_cgm_status)");
+    if (o->pre && !o->dir_ready)
+        return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: preconditioned mode, and ofdft_cgm_direction has not formed the directions of this step");
+    DeviceScope device_scope_(o->device);
+    CGM_TRY(o, device_scope_.err);
+    const real* phi = (const real*)phi_dev;
+    const int blocks = cgm_blocks(o);
+    CgmCols up{};
+    for (int c = 0; c < o->ncols; ++c) {
+        ofdft_cgm::Col& k = o->col[c];
+        if (k.reason != OFDFT_CG_RUNNING) continue;
+        if (!(p_dot_q[c] > 0.0)) {          // non-positive curvature (or NaN): x stays; before the first update x = p, the steepest descent step
+            if (k.iters == 0)
+                CGM_TRY(o, hipMemcpyAsync(o->x + c * o->ld, o->p + c * o->ld, sizeof(real) * (size_t)o->n, hipMemcpyDeviceToDevice, st));
+            k.reason = OFDFT_CG_CURVATURE;
+            continue;
+        }
+        up.a[c] = (real)((o->pre ? k.rho : k.rr) / p_dot_q[c]);
+        up.b[c] = (real)(phi_dot_q[c] / o->S);
+        up.active |= 1u << c;
+    }
+    o->dir_ready = false;
+    if (up.active) {
+        hipLaunchKernelGGL(cgm_update_kernel, dim3(blocks, o->ncols), dim3(kRedThreads), 0, st, phi, (const real*)o->p, (const real*)o->q, up, o->x,
+                           o->r, o->ld, o->n, o->d_partial);
+        if (int rc = cgm_fetch(o, blocks, 2, st)) return rc;
+        CgmCols dir{};
+        for (int c = 0; c < o->ncols; ++c) {
+            if (!((up.active >> c) & 1u)) continue;
+            ofdft_cgm::Col& k = o->col[c];
+            k.iters++;
+            const double rr_old = k.rr;
+            k.rr = o->h_out[2 * c];
+            k.phir = o->h_out[2 * c + 1];
+            if (k.rr != k.rr) k.reason = OFDFT_CG_CURVATURE;      // a NaN in the product: nothing more to gain from this column
+            else if (!(k.rr > o->rtol * o->rtol * k.bb)) k.reason = OFDFT_CG_CONVERGED;
+            else if (k.iters >= o->maxiter) k.reason = OFDFT_CG_MAXITER;
+            else if (!o->pre) {
+                dir.a[c] = (real)(k.phir / o->S);
+                dir.b[c] = (real)(k.rr / rr_old);
+                dir.active |= 1u << c;
+            }
+        }
+        if (dir.active)
+            hipLaunchKernelGGL(cgm_direction_kernel, dim3(blocks, o->ncols), dim3(256), 0, st, phi, (const real*)o->r, dir, o->p, o->ld, o->n);
+    } else {
+        CGM_TRY(o, hipStreamSynchronize(st));      // (only first-step copies x = p were queued)
+    }
+    CGM_TRY(o, hipGetLastError());
+    *running = cgm_running(o);
+    return OFDFT_OK;
+}
+
+// preconditioned mode, between the update sweep of one step and the product of the next: with z_c = M^-1 r_c in place for every
+// running column, rho_c, beta_c and p_c = P z_c + beta_c p_c as ofdft_cg_direction forms them.  One synchronisation.
+int ofdft_cgm_direction(ofdft_cgm* o, const void* phi_dev, double* info_host, int* running, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!o) return OFDFT_EINVAL;
+    if (!phi_dev || !running) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_direction: null argument");
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: ofdft_cgm_start has not been called");
+    if (!o->pre) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: the solve runs in plain mode (ofdft_cgm_set_preconditioned before ofdft_cgm_start)");
+    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: every column has ended (ofdft_cgm_status)");
+    if (o->dir_ready) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: the directions of this step are already formed (ofdft_cgm_step)");
+    DeviceScope device_scope_(o->device);
+    CGM_TRY(o, device_scope_.err);
+    const real* phi = (const real*)phi_dev;
+    const int blocks = cgm_blocks(o);
+    CgmCols run{};
+    for (int c = 0; c < o->ncols; ++c)
+        if (o->col[c].reason == OFDFT_CG_RUNNING) run.active |= 1u << c;
+    hipLaunchKernelGGL(cgm_pre_dots_kernel, dim3(blocks, o->ncols), dim3(kRedThreads), 0, st, phi, (const real*)o->r, (const real*)o->z, run, o->ld,
+                       o->n, o->d_partial);
+    if (int rc = cgm_fetch(o, blocks, 2, st)) return rc;
+    CgmCols dir{};
+    for (int c = 0; c < o->ncols; ++c) {
+        if (info_host)
+            for (int s = 0; s < 4; ++s) info_host[4 * c + s] = 0.0;
+        if (!((run.active >> c) & 1u)) continue;
+        ofdft_cgm::Col& k = o->col[c];
+        const double rz = o->h_out[2 * c], phiz = o->h_out[2 * c + 1];
+        const double rho = rz - k.phir * phiz / o->S;
+        const double beta = o->dir_first ? 0.0 : rho / k.rho;
+        if (info_host) {
+            info_host[4 * c] = rz;
+            info_host[4 * c + 1] = phiz;
+            info_host[4 * c + 2] = rho;
+            info_host[4 * c + 3] = beta;
+        }
+        if (!(rho > 0.0)) {                // M is positive definite: only a NaN or a vanished residual comes here; x stays
+            k.reason = OFDFT_CG_CURVATURE;
+            continue;
+        }
+        dir.a[c] = (real)(phiz / o->S);
+        dir.b[c] = (real)beta;
+        dir.active |= 1u << c;
+        k.rho = rho;
+    }
+    if (dir.active) {
+        if (o->dir_first)
+            hipLaunchKernelGGL(cgm_pre_direction_kernel<true>, dim3(blocks, o->ncols), dim3(kRedThreads), 0, st, phi, (const real*)o->z, dir, o->p,
+                               o->ld, o->n);
+        else
+            hipLaunchKernelGGL(cgm_pre_direction_kernel<false>, dim3(blocks, o->ncols), dim3(kRedThreads), 0, st, phi, (const real*)o->z, dir, o->p,
+                               o->ld, o->n);
+    }
+    CGM_TRY(o, hipGetLastError());
+    o->dir_first = false;
+    o->dir_ready = true;
+    *running = cgm_running(o);
+    return OFDFT_OK;
+}
+
+// x of every column of the solve, copied to the caller's stack at its stride (the stream's order; no wait)
+int ofdft_cgm_solution(ofdft_cgm* o, void* x_out_dev, long long stride, void* stream) {
+    if (!o) return OFDFT_EINVAL;
+    if (!x_out_dev) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_solution: null argument");
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_solution: ofdft_cgm_start has not been called");
+    if (stride < o->n) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_solution: stride is below the points of a column");
+    DeviceScope device_scope_(o->device);
+    CGM_TRY(o, device_scope_.err);
+    CGM_TRY(o, hipMemcpy2DAsync(x_out_dev, sizeof(real) * (size_t)stride, o->x, sizeof(real) * (size_t)o->ld, sizeof(real) * (size_t)o->n,
+                                (size_t)o->ncols, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return OFDFT_OK;
+}
+
+int ofdft_cgm_status(const ofdft_cgm* o, int col, int* iterations, int* reason, double* rel_residual) {
+    if (!o || col < 0 || col >= o->ncols_max) return OFDFT_EINVAL;
+    const ofdft_cgm::Col& k = o->col[col];
+    if (iterations) *iterations = k.iters;
+    if (reason) *reason = k.reason;
+    if (rel_residual) *rel_residual = k.bb > 0.0 ? std::sqrt(k.rr / k.bb) : 0.0;
+    return OFDFT_OK;
+}
+
+}  // extern "C"

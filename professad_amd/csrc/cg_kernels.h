@@ -113,6 +113,160 @@ static __global__ __launch_bounds__(kRedThreads) void cg_pre_direction_kernel(co
         cg_st(p, i, n2, n, pi);
     }
 }
+
+// ================================================================================================================================
+// Several solves in lockstep (ofdft_cgm_*): the sweeps above with the column as the grid's y index.  Column c of a
+// vector is v + c * ld (ld even, so every column is pair-aligned).  One launch serves every column; a block whose column is not in
+// `active` leaves at once, so an ended column's x and r are never written again.  The x extent of the grid, the loop and the
+// block reduction are those of the single-column kernels: a column's sums are bitwise the sums a solo solve forms from the same
+// vectors.  Partial sums: partial[(c * gridDim.x + block) * NS + s].  The per-column coefficients travel by value.
+constexpr int kCgmMax = 8;      // OFDFT_MULTI_MAX
+struct CgmCols {
+    real a[kCgmMax];            // s of the start / direction sweeps, alpha of the update
+    real b[kCgmMax];            // s of the update, beta of the direction sweeps
+    unsigned active;            // bit c: the sweep runs on column c
+};
+#define CGM_COLUMN(cols)                                        \
+    const int col = blockIdx.y;                                 \
+    if (!(((cols).active >> col) & 1u)) return;                 \
+    const long long off = (long long)col * ld;                  \
+    acc_t* const part = partial + (long long)col * gridDim.x * NS
+// a column of the caller's stack may start at an odd element (odd stride): two scalar loads per pair there
+__device__ __forceinline__ cplx cg_ld_any(const real* p, long long i, long long n2, long long n) {
+    if (i >= n2) return mkc(p[n - 1], 0.0);
+    if ((reinterpret_cast<unsigned long long>(p) & (2 * sizeof(real) - 1)) == 0) return reinterpret_cast<const cplx*>(p)[i];
+    return mkc(p[2 * i], p[2 * i + 1]);
+}
+
+// start, first sweep: b_c.b_c, phi.phi, phi.b_c per column
+static __global__ __launch_bounds__(kRedThreads) void cgm_start_dots_kernel(const real* __restrict__ phi, const real* __restrict__ b,
+                                                                            long long bstride, long long n, acc_t* __restrict__ partial) {
+    constexpr int NS = 3;
+    const real* bc = b + (long long)blockIdx.y * bstride;
+    acc_t* const part = partial + (long long)blockIdx.y * gridDim.x * NS;
+    acc_t acc[3] = {0.0, 0.0, 0.0};
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), v = cg_ld_any(bc, i, n2, n);
+        acc[0] += v.x * v.x + v.y * v.y;
+        acc[1] += f.x * f.x + f.y * f.y;
+        acc[2] += f.x * v.x + f.y * v.y;
+    }
+    block_reduce_store<3>(acc, part);
+}
+
+// start, second sweep: x_c = 0, r_c = p_c = b_c - s_c phi; sum r_c.r_c
+static __global__ __launch_bounds__(kRedThreads) void cgm_start_kernel(const real* __restrict__ phi, const real* __restrict__ b, long long bstride,
+                                                                       CgmCols cols, real* __restrict__ x, real* __restrict__ r,
+                                                                       real* __restrict__ p, long long ld, long long n,
+                                                                       acc_t* __restrict__ partial) {
+    constexpr int NS = 1;
+    CGM_COLUMN(cols);
+    const real* bc = b + (long long)col * bstride;
+    const real s = cols.a[col];
+    acc_t acc[1] = {0.0};
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), v = cg_ld_any(bc, i, n2, n);
+        const cplx ri = mkc(v.x - s * f.x, v.y - s * f.y);
+        cg_st(x + off, i, n2, n, mkc(0.0, 0.0));
+        cg_st(r + off, i, n2, n, ri);
+        cg_st(p + off, i, n2, n, ri);
+        acc[0] += ri.x * ri.x + ri.y * ri.y;
+    }
+    block_reduce_store<1>(acc, part);
+}
+
+// update sweep (alpha_c = cols.a, s_c = phi.q_c / S = cols.b); sums r_c.r_c and phi.r_c of the new residual
+static __global__ __launch_bounds__(kRedThreads) void cgm_update_kernel(const real* __restrict__ phi, const real* __restrict__ p,
+                                                                        const real* __restrict__ q, CgmCols cols, real* __restrict__ x,
+                                                                        real* __restrict__ r, long long ld, long long n,
+                                                                        acc_t* __restrict__ partial) {
+    constexpr int NS = 2;
+    CGM_COLUMN(cols);
+    const real alpha = cols.a[col], s = cols.b[col];
+    acc_t acc[2] = {0.0, 0.0};
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), pi = cg_ld(p + off, i, n2, n), qi = cg_ld(q + off, i, n2, n);
+        cplx xi = cg_ld(x + off, i, n2, n), ri = cg_ld(r + off, i, n2, n);
+        xi.x += alpha * pi.x;
+        xi.y += alpha * pi.y;
+        ri.x -= alpha * (qi.x - s * f.x);
+        ri.y -= alpha * (qi.y - s * f.y);
+        cg_st(x + off, i, n2, n, xi);
+        cg_st(r + off, i, n2, n, ri);
+        acc[0] += ri.x * ri.x + ri.y * ri.y;
+        acc[1] += f.x * ri.x + f.y * ri.y;
+    }
+    block_reduce_store<2>(acc, part);
+}
+
+// direction sweep (s_c = phi.r_c / S = cols.a, beta_c = cols.b)
+static __global__ __launch_bounds__(kRedThreads) void cgm_direction_kernel(const real* __restrict__ phi, const real* __restrict__ r, CgmCols cols,
+                                                                           real* __restrict__ p, long long ld, long long n) {
+    const int col = blockIdx.y;
+    if (!((cols.active >> col) & 1u)) return;
+    const long long off = (long long)col * ld;
+    const real s = cols.a[col], beta = cols.b[col];
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), ri = cg_ld(r + off, i, n2, n);
+        cplx pi = cg_ld(p + off, i, n2, n);
+        pi.x = (ri.x - s * f.x) + beta * pi.x;
+        pi.y = (ri.y - s * f.y) + beta * pi.y;
+        cg_st(p + off, i, n2, n, pi);
+    }
+}
+
+// preconditioned mode: sums r_c.z_c and phi.z_c
+static __global__ __launch_bounds__(kRedThreads) void cgm_pre_dots_kernel(const real* __restrict__ phi, const real* __restrict__ r,
+                                                                          const real* __restrict__ z, CgmCols cols, long long ld, long long n,
+                                                                          acc_t* __restrict__ partial) {
+    constexpr int NS = 2;
+    CGM_COLUMN(cols);
+    acc_t acc[2] = {0.0, 0.0};
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), ri = cg_ld(r + off, i, n2, n), zi = cg_ld(z + off, i, n2, n);
+        acc[0] += ri.x * zi.x + ri.y * zi.y;
+        acc[1] += f.x * zi.x + f.y * zi.y;
+    }
+    block_reduce_store<2>(acc, part);
+}
+
+// preconditioned direction sweep (s_c = phi.z_c / S = cols.a, beta_c = cols.b): p_c = (z_c - s_c phi) + beta_c p_c; FIRST: beta = 0
+template <bool FIRST>
+static __global__ __launch_bounds__(kRedThreads) void cgm_pre_direction_kernel(const real* __restrict__ phi, const real* __restrict__ z,
+                                                                               CgmCols cols, real* __restrict__ p, long long ld, long long n) {
+    const int col = blockIdx.y;
+    if (!((cols.active >> col) & 1u)) return;
+    const long long off = (long long)col * ld;
+    const real s = cols.a[col], beta = cols.b[col];
+    CG_FOR_PAIRS(n) {
+        const cplx f = cg_ld(phi, i, n2, n), zi = cg_ld(z + off, i, n2, n);
+        cplx pi = mkc(zi.x - s * f.x, zi.y - s * f.y);
+        if (!FIRST) {
+            const cplx po = cg_ld(p + off, i, n2, n);
+            pi.x += beta * po.x;
+            pi.y += beta * po.y;
+        }
+        cg_st(p + off, i, n2, n, pi);
+    }
+}
+
+// second level: partial[col][rows][ns] -> out[col * ns + s]; grid (ns, columns), the tree of reduce_partials_kernel
+static __global__ __launch_bounds__(kRedThreads) void cgm_reduce_kernel(const acc_t* __restrict__ partial, int rows, int ns,
+                                                                        acc_t* __restrict__ out) {
+    const int s = blockIdx.x, col = blockIdx.y;
+    const acc_t* part = partial + (long long)col * rows * ns;
+    acc_t acc = 0.0;
+    for (int r = threadIdx.x; r < rows; r += kRedThreads) acc += part[(long long)r * ns + s];
+    __shared__ acc_t red[kRedThreads];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = kRedThreads / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[col * ns + s] = red[0];
+}
+#undef CGM_COLUMN
 #undef CG_FOR_PAIRS
 
 }  // namespace ofdft

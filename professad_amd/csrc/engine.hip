@@ -1665,6 +1665,10 @@ int ofdft_ion_electron_stress(ofdft_ctx* c, const void*, const double*, int, con
 int ofdft_hessian_vector(ofdft_ctx* c, const void*, const void*, void*, double*, int, void*) { return OFDFT_F64_ONLY(c); }
 int ofdft_hessian_vector_chi(ofdft_ctx* c, const void*, const void*, const void*, double, void*, double*, int, void*) { return OFDFT_F64_ONLY(c); }
 int ofdft_precondition(ofdft_ctx* c, const void*, void*, double, void*) { return OFDFT_F64_ONLY(c); }
+int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void*, const void*, long long, int, double, void*, long long, double*, int, void*) {
+    return OFDFT_F64_ONLY(c);
+}
+int ofdft_precondition_multi(ofdft_ctx* c, const void*, long long, void*, long long, int, double, void*) { return OFDFT_F64_ONLY(c); }
 int ofdft_ion_ion(ofdft_ctx* c, const double*, const double*, int, double, double*, double*, double*, void*) {
     return OFDFT_F64_ONLY(c);
 }

@@ -10,6 +10,8 @@
 // hvp_core schedules this once for both entries.  ofdft_hessian_vector hands it (n, w); ofdft_hessian_vector_chi hands it
 // (phi, d) with HvpChi set: head and combine then run their chi-space instantiations, which form n and dn on the fly, and the
 // call adds one two-sum sweep over (phi, d) in front and one shift of the output by the constant d mu behind.
+// ofdft_hessian_vector_chi_multi and ofdft_precondition_multi (end of the file) run the chi-space schedule and the preconditioner
+// for up to OFDFT_MULTI_MAX columns per call, sharing the density-side fields with the entries above.
 namespace {
 
 // the retained fields belong to the entry that made them: hvp_valid is kHvpNone, kHvpDensity or kHvpChi (every `= false` elsewhere clears it)
@@ -276,6 +278,293 @@ int ofdft_precondition(ofdft_ctx* c, const void* r_dev, void* z_dev, double kapp
         OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_SCREENED>), dim3(grid_for(c->g.total)), dim3(256), 0, (const cplx*)s0, s0, c->kg,
                      (real)kappa2, (real)0.0);
         if (int rc = irfftn_internal(c, s0, z, inv_n, st)) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipGetLastError());
+    if (c->profiling) prof_collect(c);
+    return OFDFT_OK;
+}
+
+// ---- several columns per call (include/ofdft_hip.h) ------------------------------------------------------------
+namespace {
+
+// Workspaces of the multi entries.  The density-side fields ("hv:lap", "hv:A", "hv:B" and their spectra) are the ones the
+// single-column entries write: that is what lets either entry reuse the other's.  The per-direction fields are per column: column
+// 0 takes the single-column workspaces under their own names ("hv:vh", "s0", ...), column j > 0 the same name with "#j" appended.
+void col_name(char (&name)[32], const char* base, int j) {
+    if (j) std::snprintf(name, sizeof(name), "%s#%d", base, j);
+    else std::snprintf(name, sizeof(name), "%s", base);
+}
+int real_ws_col(ofdft_ctx* c, const char* base, int j, real** out) {
+    char name[32];
+    col_name(name, base, j);
+    return real_ws(c, name, out);
+}
+int spec_ws_col(ofdft_ctx* c, const char* base, int j, cplx** out) {
+    char name[32];
+    col_name(name, base, j);
+    return spec_ws(c, name, out);
+}
+
+#define HVM_CASE(NC, ...) \
+    case NC: {            \
+        constexpr int kNC = NC; \
+        __VA_ARGS__;      \
+    } break;
+// runs the statement with kNC = nc as a compile-time constant (1 .. kMultiMax)
+#define HVM_DISPATCH(nc, ...)                                                                                                       \
+    switch (nc) {                                                                                                                   \
+        HVM_CASE(1, __VA_ARGS__) HVM_CASE(2, __VA_ARGS__) HVM_CASE(3, __VA_ARGS__) HVM_CASE(4, __VA_ARGS__) HVM_CASE(5, __VA_ARGS__) \
+        HVM_CASE(6, __VA_ARGS__) HVM_CASE(7, __VA_ARGS__) HVM_CASE(8, __VA_ARGS__)                                                  \
+    }
+static_assert(kMultiMax == 8 && OFDFT_MULTI_MAX == kMultiMax, "HVM_DISPATCH lists the column counts");
+
+// [a, a + na) and [b, b + nb) share an element
+bool ranges_overlap(const real* a, long long na, const real* b, long long nb) { return a < b + nb && b < a + na; }
+
+// the argument checks the two multi entries share; `who` names the entry
+int multi_checks(ofdft_ctx* c, const char* who, int ncols, long long in_stride, long long out_stride) {
+    if (ncols < 1 || ncols > kMultiMax)
+        return fail(c, OFDFT_EINVAL, "%s: ncols = %d is outside 1 .. %d (OFDFT_MULTI_MAX)", who, ncols, kMultiMax);
+    if (in_stride < c->npts || out_stride < c->npts)
+        return fail(c, OFDFT_EINVAL, "%s: a column stride (%lld in, %lld out) is below the %lld points of a column", who, in_stride, out_stride,
+                    c->npts);
+    return 0;
+}
+
+}  // namespace
+
+int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void* dirs_dev, long long dir_stride, int ncols, double n_electrons,
+                                   void* out_dev, long long out_stride, double* scalars_host, int reuse_density, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    const char* who = "ofdft_hessian_vector_chi_multi";
+    const bool retained = c->hvp_valid == kHvpChi;         // (the chi-space fields of either entry)
+    const double S_kept = c->hvp_chi_S;
+    if (int rc = begin_call(c, st)) return rc;
+    if (!chi_dev || !dirs_dev || !out_dev) return fail(c, OFDFT_EINVAL, "null argument");
+    if (int rc = multi_checks(c, who, ncols, dir_stride, out_stride)) return rc;
+    if (!(n_electrons > 0.0)) return fail(c, OFDFT_EINVAL, "%s: n_electrons must be positive", who);
+    if (int rc = hvp_checks(c, who)) return rc;
+    const long long npts = c->npts;
+    const real* phi = (const real*)chi_dev;
+    const real* d = (const real*)dirs_dev;
+    real* out = (real*)out_dev;
+    if (ranges_overlap(d, (ncols - 1) * dir_stride + npts, out, (ncols - 1) * out_stride + npts))
+        return fail(c, OFDFT_EINVAL, "%s: out_dev overlaps dirs_dev (the product is not in place)", who);
+    if (reuse_density && !retained)
+        return fail(c, OFDFT_ESTATE, "%s: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set", who);
+    const bool reuse = reuse_density != 0;
+    const unsigned mask = c->mask;
+    const bool has_h = mask & OFDFT_HARTREE, has_vw = mask & OFDFT_VW, has_wt = mask & OFDFT_WT_NL;
+    const TermScalars ts = term_scalars(c, n_electrons);
+    const bool two = has_wt && ts.nlp.two;
+    const double inv_n = 1.0 / (double)npts;
+
+    // a_j = phi.d_j of every column and S: one sweep, one fetch
+    const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
+    HVM_DISPATCH(ncols, OFDFT_LAUNCH(c, st, "hvm_dots", hvm_dots_kernel<kNC>, dim3(blocks), dim3(kRedThreads), 0, phi, d, dir_stride, npts, c->d_partial));
+    double pre[kMultiMax + 1];
+    if (int rc = fetch_partials(c, blocks, ncols + 1, pre, st)) return rc;
+    const double S = reuse ? S_kept : pre[ncols];
+    if (!(S > 0.0)) return fail(c, OFDFT_EINVAL, "%s: chi is zero everywhere", who);
+    const double cs = n_electrons / (S * c->dV), c2 = 2.0 * cs * c->dV;
+
+    // one item per transform, the density-only ones first
+    const real* fin[kHvpMultiSpectra];
+    cplx* spec[kHvpMultiSpectra];
+    real* fout[kHvpMultiSpectra];
+    int op[kHvpMultiSpectra];
+    int ns = 0;
+    auto item = [&](real* field, cplx* s, int o) {
+        fin[ns] = field;
+        spec[ns] = s;
+        fout[ns] = field;
+        op[ns++] = o;
+    };
+    real *lap = nullptr, *A = nullptr, *B = nullptr;
+    real *vh[kMultiMax] = {}, *dlap[kMultiMax] = {}, *Cb[kMultiMax] = {}, *Ca[kMultiMax] = {};
+    cplx* s;
+    if (has_vw) {
+        if (int rc = real_ws(c, "hv:lap", &lap)) return rc;
+        if (!reuse) {
+            if (int rc = spec_ws(c, "svw", &s)) return rc;
+            item(lap, s, SPEC_LAPLACE);
+        }
+    }
+    if (has_wt) {
+        if (int rc = real_ws(c, "hv:A", &A)) return rc;
+        if (!reuse) {
+            if (int rc = spec_ws(c, "swb", &s)) return rc;
+            item(A, s, SPEC_LINDHARD);
+        }
+        if (two) {
+            if (int rc = real_ws(c, "hv:B", &B)) return rc;
+            if (!reuse) {
+                if (int rc = spec_ws(c, "swa", &s)) return rc;
+                item(B, s, SPEC_LINDHARD);
+            }
+        }
+    }
+    for (int j = 0; j < ncols; ++j) {
+        if (has_h) {            // the head writes dn_j into "hv:vh"; transformed in place
+            if (int rc = real_ws_col(c, "hv:vh", j, &vh[j])) return rc;
+            if (int rc = spec_ws_col(c, "s0", j, &s)) return rc;
+            item(vh[j], s, SPEC_HARTREE);
+        }
+        if (has_vw) {
+            if (int rc = real_ws_col(c, "hv:dlap", j, &dlap[j])) return rc;
+            if (int rc = spec_ws_col(c, "s1", j, &s)) return rc;
+            item(dlap[j], s, SPEC_LAPLACE);
+        }
+        if (has_wt) {
+            if (int rc = real_ws_col(c, "hv:Cb", j, &Cb[j])) return rc;
+            if (int rc = spec_ws_col(c, "s2", j, &s)) return rc;
+            item(Cb[j], s, SPEC_LINDHARD);
+            if (two) {
+                if (int rc = real_ws_col(c, "hv:Ca", j, &Ca[j])) return rc;
+                if (int rc = spec_ws_col(c, "s3", j, &s)) return rc;
+                item(Ca[j], s, SPEC_LINDHARD);
+            }
+        }
+    }
+    if (ns) {
+        HvmHeadArgs ha{};
+        ha.phi = phi;
+        ha.d = d;
+        ha.stride = dir_stride;
+        ha.npts = npts;
+        ha.chi = lap;
+        ha.pb = A;
+        ha.pa = B;
+        for (int j = 0; j < ncols; ++j) {
+            ha.dn[j] = vh[j];
+            ha.dchi[j] = dlap[j];
+            ha.pbw[j] = Cb[j];
+            ha.paw[j] = Ca[j];
+            ha.k[j] = 2.0 * pre[j] / S;
+        }
+        ha.cs = cs;
+        ha.al = ts.nlp.al;
+        ha.be = ts.nlp.be;
+        ha.flags = (has_vw ? HVP_VW : 0) | (has_wt ? HVP_WT : 0) | (two ? HVP_WT2 : 0) | (reuse ? HVP_REUSE : 0);
+        HVM_DISPATCH(ncols, OFDFT_LAUNCH(c, st, "hvm_head", hvm_head_kernel<kNC>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, ha));
+        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
+            if (int rc = rfftn_internal_multi(c, fin + b0, spec + b0, std::min(kBsBatch, ns - b0), st)) return rc;
+        HvmSpecArgs sa{};
+        for (int j = 0; j < ns; ++j) {
+            sa.s[j] = spec[j];
+            sa.op[j] = (unsigned char)op[j];
+        }
+        sa.ns = ns;
+        sa.lindhard = has_wt ? 1 : 0;
+        sa.kg = c->kg;
+        sa.pref = ts.wt_pref;
+        sa.inv2kf = ts.wt_inv2kf;
+        OFDFT_LAUNCH(c, st, "hvm_spec", hvm_spec_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, sa);
+        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
+            if (int rc = irfftn_internal_multi(c, spec + b0, fout + b0, std::min(kBsBatch, ns - b0), inv_n, st)) return rc;
+    }
+    HvmCombineArgs ca{};
+    ca.phi = phi;
+    ca.d = d;
+    ca.dstride = dir_stride;
+    ca.lap = lap;
+    ca.A = A;
+    ca.B = B;
+    for (int j = 0; j < ncols; ++j) {
+        ca.vh[j] = vh[j];
+        ca.dlap[j] = dlap[j];
+        ca.Cb[j] = Cb[j];
+        ca.Ca[j] = Ca[j];
+        ca.k[j] = 2.0 * pre[j] / S;
+    }
+    ca.out = out;
+    ca.ostride = out_stride;
+    ca.npts = npts;
+    ca.mask = mask;
+    ca.two = two ? 1 : 0;
+    ca.al = ts.nlp.al;
+    ca.be = ts.nlp.be;
+    ca.cs = cs;
+    ca.c2 = c2;
+    const int nsum = kHvpMultiScalars * ncols;
+    HVM_DISPATCH(ncols, OFDFT_LAUNCH(c, st, "hvm_combine", hvm_combine_kernel<kNC>, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial));
+    OFDFT_REDUCE(c, st, c->d_partial, blocks, nsum, c->d_reduced);
+    OFDFT_LAUNCH(c, st, "hvm_shift", hvm_shift_kernel, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, phi, out, out_stride, ncols, npts,
+                 (const acc_t*)c->d_reduced, (real)c->dV, (real)(1.0 / n_electrons), (real)c2);
+    if (scalars_host) HIP_TRY(c, hipMemcpyAsync(c->h_partial, c->d_reduced, sizeof(double) * nsum, hipMemcpyDeviceToHost, st));
+    if (int rc = end_call(c, st)) return rc;
+    c->hvp_valid = kHvpChi;
+    c->hvp_nel = n_electrons;
+    c->hvp_chi_S = S;
+    if (scalars_host)
+        for (int j = 0; j < ncols; ++j) {
+            const double* sums = c->h_partial + kHvpMultiScalars * j;
+            const double dmu = sums[0] * c->dV / n_electrons;
+            double* o = scalars_host + OFDFT_HVC_NSCALARS * j;
+            o[OFDFT_HVC_DHD] = sums[1] - c2 * dmu * pre[j];
+            o[OFDFT_HVC_PHIHD] = sums[2] - c2 * dmu * S;
+            o[OFDFT_HVC_A] = pre[j];
+            o[OFDFT_HVC_S] = S;
+            o[OFDFT_HVC_DMU] = dmu;
+        }
+    return OFDFT_OK;
+}
+
+// z_j = irfftn(rfftn(r_j) / (k^2 + kappa2)) for ncols columns: the pipelines of ofdft_precondition, `kBsBatch` columns at a time where a
+// pass takes several fields (the chirp-z helpers), one column per launch through the fused radix passes, one synchronisation at the
+// end.  Like the single-column entry it goes round begin_call; its spectra ("s0", "s0#1", ...) are transient in every product.
+int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride, void* z_dev, long long z_stride, int ncols, double kappa2,
+                             void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    const char* who = "ofdft_precondition_multi";
+    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no preconditioner", who);
+    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
+    if (!r_dev || !z_dev) return fail(c, OFDFT_EINVAL, "null argument");
+    if (int rc = multi_checks(c, who, ncols, r_stride, z_stride)) return rc;
+    if (!(kappa2 > 0.0) || !std::isfinite(kappa2)) return fail(c, OFDFT_EINVAL, "%s: kappa2 must be positive and finite", who);
+    const real* r = (const real*)r_dev;
+    real* z = (real*)z_dev;
+    if (ranges_overlap(r, (ncols - 1) * r_stride + c->npts, z, (ncols - 1) * z_stride + c->npts))
+        return fail(c, OFDFT_EINVAL, "%s: z_dev overlaps r_dev (the transform is not in place)", who);
+    const double inv_n = 1.0 / (double)c->npts;
+    const MixScale<SPEC_SCREENED> mix{c->kg, (real)kappa2, (real)0.0};
+    cplx* sp[kBsBatch];
+    for (int a = 0; a < std::min(kBsBatch, ncols); ++a)
+        if (int rc = spec_ws_col(c, "s0", a, &sp[a])) return rc;
+    for (int j0 = 0; j0 < ncols; j0 += kBsBatch) {
+        const int nb = std::min(kBsBatch, ncols - j0);
+        const real* in[kBsBatch];
+        real* out[kBsBatch];
+        for (int a = 0; a < nb; ++a) {
+            in[a] = r + (j0 + a) * r_stride;
+            out[a] = z + (j0 + a) * z_stride;
+        }
+        if (c->fast && !c->force_unfused) {
+            for (int a = 0; a < nb; ++a) {
+                if (int rc = fwd_zy(c, in[a], sp[a], st)) return rc;
+                XfIo io{};
+                io.in[0] = sp[a];
+                io.out[0] = sp[a];
+                if (int rc = xfused<1, 1>(c, io, mix, st, "xfused_pre")) return rc;
+                if (int rc = inv_yz(c, sp[a], out[a], inv_n, st)) return rc;
+            }
+        } else if (bluestein_xmix_ok(c) && !c->force_unfused) {
+            if (int rc = bluestein_fwd_zy_multi(c, in, sp, nb, st)) return rc;
+            for (int a = 0; a < nb; ++a)
+                if (int rc = bluestein_xmix<1, 1>(c, sp + a, sp + a, mix, st)) return rc;
+            if (int rc = bluestein_inv_yz_multi(c, sp, out, nb, inv_n, st)) return rc;
+        } else {
+            if (int rc = rfftn_internal_multi(c, in, sp, nb, st)) return rc;
+            for (int a = 0; a < nb; ++a)
+                OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_SCREENED>), dim3(grid_for(c->g.total)), dim3(256), 0, (const cplx*)sp[a],
+                             sp[a], c->kg, (real)kappa2, (real)0.0);
+            if (int rc = irfftn_internal_multi(c, sp, out, nb, inv_n, st)) return rc;
+        }
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     HIP_TRY(c, hipGetLastError());

@@ -339,4 +339,235 @@ static __global__ void hvp_chi_shift_kernel(const real* __restrict__ phi, real* 
     if ((npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[npts - 1] -= s * phi[npts - 1];
 }
 
+// ================================================================================================================================
+// Several directions per call (ofdft_hessian_vector_chi_multi): the chi-space product at a stationary point (g = 0)
+// for NC <= kMultiMax directions d_j at once.  Same schedule, the column count a dimension: phi, the density-side fields and
+// every density-only factor (n, its roots and powers, the second derivatives of the local terms) are read or formed once per
+// point and serve all columns.  NC is a template parameter, so the per-column accumulators and pointers stay in registers.
+constexpr int kMultiMax = 8;                                   // OFDFT_MULTI_MAX
+constexpr int kHvpMultiScalars = 3;                            // per column: sum dv n, d.P, phi.P  (g.d = 0)
+constexpr int kHvpMultiSpectra = 3 + 4 * kMultiMax;            // density-only spectra + four per column
+static_assert(kHvpMultiScalars * kMultiMax <= kMaxScalars && kMultiMax + 1 <= kMaxScalars, "the multi sums use the context's partial buffers");
+
+// pair i of an array of n reals (n2 = n / 2 pairs, then the odd last element alone with a zero partner).  A column of a caller's
+// stack may start at an odd element (odd stride): such a base takes two scalar accesses per pair.
+__device__ __forceinline__ bool hvm_pair_aligned(const real* p) { return (reinterpret_cast<unsigned long long>(p) & (2 * sizeof(real) - 1)) == 0; }
+__device__ __forceinline__ cplx hvm_ld(const real* p, long long i, long long n2, long long n) {
+    if (i >= n2) return mkc(p[n - 1], 0.0);
+    if (hvm_pair_aligned(p)) return reinterpret_cast<const cplx*>(p)[i];
+    return mkc(p[2 * i], p[2 * i + 1]);
+}
+__device__ __forceinline__ void hvm_st(real* p, long long i, long long n2, long long n, cplx v) {
+    if (i >= n2) {
+        p[n - 1] = v.x;
+    } else if (hvm_pair_aligned(p)) {
+        reinterpret_cast<cplx*>(p)[i] = v;
+    } else {
+        p[2 * i] = v.x;
+        p[2 * i + 1] = v.y;
+    }
+}
+#define HVM_FOR_PAIRS(n)                                                                                                  \
+    const long long n2 = (n) >> 1;                                                                                       \
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2 + ((n) & 1); i += (long long)gridDim.x * blockDim.x)
+
+// ---- before the head: a_j = phi.d_j for every column and S = phi.phi (slot NC), the latter summed exactly as hvp_chi_dots_kernel
+// sums it, so that either entry may reuse the other's density fields
+template <int NC>
+static __global__ __launch_bounds__(kRedThreads) void hvm_dots_kernel(const real* __restrict__ phi, const real* __restrict__ d, long long stride,
+                                                                      long long npts, acc_t* __restrict__ partial) {
+    acc_t acc[NC + 1];
+#pragma unroll
+    for (int s = 0; s <= NC; ++s) acc[s] = 0.0;
+    const long long n2 = npts >> 1;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        const cplx p = hvm_ld(phi, i, n2, npts);
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const cplx q = hvm_ld(d + j * stride, i, n2, npts);
+            acc[j] += p.x * q.x + p.y * q.y;
+        }
+        acc[NC] += p.x * p.x + p.y * p.y;
+    }
+    if ((npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {      // (the odd last element where hvp_chi_dots_kernel adds it)
+#pragma unroll
+        for (int j = 0; j < NC; ++j) acc[j] += phi[npts - 1] * d[j * stride + npts - 1];
+        acc[NC] += phi[npts - 1] * phi[npts - 1];
+    }
+    block_reduce_store<NC + 1>(acc, partial);
+}
+
+// ---- head: phi once, the density-only fields once (not with HVP_REUSE), then dn_j, d chi_j, n^(beta-1) dn_j, n^(alpha-1) dn_j per column
+struct HvmHeadArgs {
+    const real* phi;
+    const real* d;               // column j at d + j * stride
+    long long stride, npts;
+    real* chi;  real* pb;  real* pa;                                   // sqrt n, n^beta, n^alpha ("hv:lap", "hv:A", "hv:B")
+    real* dn[kMultiMax];                                                // nullptr: no transform takes dn itself
+    real* dchi[kMultiMax];  real* pbw[kMultiMax];  real* paw[kMultiMax];
+    real k[kMultiMax];                                                  // 2 a_j / S
+    real cs, al, be;
+    unsigned flags;
+};
+template <int NC>
+static __global__ void hvm_head_kernel(HvmHeadArgs a) {
+    const bool vw = a.flags & HVP_VW, wt = a.flags & HVP_WT, wt2 = a.flags & HVP_WT2, dens = !(a.flags & HVP_REUSE);
+    HVM_FOR_PAIRS(a.npts) {
+        const cplx phi = hvm_ld(a.phi, i, n2, a.npts);
+        const bool pair = i < n2;                       // the odd last element has no partner: its y lane is not formed
+        const real n0 = a.cs * phi.x * phi.x, n1 = pair ? a.cs * phi.y * phi.y : (real)1.0;
+        real c0 = 0.0, c1 = 0.0, b0 = 0.0, b1 = 0.0, a0 = 0.0, a1 = 0.0;
+        if (vw) {
+            c0 = sqrt(n0);
+            c1 = sqrt(n1);
+            if (dens) hvm_st(a.chi, i, n2, a.npts, mkc(c0, c1));
+        }
+        if (wt) {
+            b0 = pow(n0, a.be - 1.0);
+            b1 = pow(n1, a.be - 1.0);
+            if (dens) hvm_st(a.pb, i, n2, a.npts, mkc(b0 * n0, b1 * n1));
+        }
+        if (wt2) {
+            a0 = pow(n0, a.al - 1.0);
+            a1 = pow(n1, a.al - 1.0);
+            if (dens) hvm_st(a.pa, i, n2, a.npts, mkc(a0 * n0, a1 * n1));
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const cplx d = hvm_ld(a.d + j * a.stride, i, n2, a.npts);
+            const real w0 = 2.0 * a.cs * phi.x * d.x - a.k[j] * n0, w1 = pair ? 2.0 * a.cs * phi.y * d.y - a.k[j] * n1 : (real)0.0;
+            if (a.dn[j]) hvm_st(a.dn[j], i, n2, a.npts, mkc(w0, w1));
+            if (vw) hvm_st(a.dchi[j], i, n2, a.npts, mkc(w0 / (2.0 * c0), w1 / (2.0 * c1)));
+            if (wt) hvm_st(a.pbw[j], i, n2, a.npts, mkc(b0 * w0, b1 * w1));
+            if (wt2) hvm_st(a.paw[j], i, n2, a.npts, mkc(a0 * w0, a1 * w1));
+        }
+    }
+}
+
+// ---- spectral: every spectrum of every column times its operator, in place; k, eta and the Lindhard kernel once per k-point
+struct HvmSpecArgs {
+    cplx* s[kHvpMultiSpectra];
+    unsigned char op[kHvpMultiSpectra + 1];
+    int ns, lindhard;
+    KGeom kg;
+    real pref, inv2kf;
+};
+static __global__ void hvm_spec_kernel(HvmSpecArgs a) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.kg.g.total; i += (long long)gridDim.x * blockDim.x) {
+        real kx, ky, kz, k2;
+        kvec(a.kg, i, kx, ky, kz, k2);
+        const real fh = (k2 != 0.0) ? 4.0 * kPiR / k2 : 0.0;
+        const real fl = -k2;
+        const real fk = a.lindhard ? a.pref * lindhard_shape((k2 != 0.0) ? sqrt(k2) * a.inv2kf : 0.0) : 0.0;
+        for (int j = 0; j < a.ns; ++j) {                  // (uniform index into the kernel arguments: scalar loads)
+            const int o = a.op[j];
+            const real fj = o == SPEC_HARTREE ? fh : (o == SPEC_LAPLACE ? fl : fk);
+            cplx* s = a.s[j];
+            const cplx v = s[i];
+            s[i] = mkc(v.x * fj, v.y * fj);
+        }
+    }
+}
+
+// ---- combine: the density-only factors of a point once, then out_j = c2 phi dv_j and the three sums per column
+struct HvmCombineArgs {
+    const real* phi;
+    const real* d;
+    long long dstride;
+    const real* lap;  const real* A;  const real* B;                   // density side, shared by the columns
+    const real* vh[kMultiMax];  const real* dlap[kMultiMax];  const real* Cb[kMultiMax];  const real* Ca[kMultiMax];
+    real* out;
+    long long ostride, npts;
+    real k[kMultiMax];
+    unsigned mask;
+    int two;
+    real al, be, cs, c2;
+};
+// what a point contributes to every column: dv = vh + w g0 + v1 (dlap - w v2) + wb Cb + wa Ca   (w = dn_j)
+struct HvmFactors { real n, g0, v1, v2, wb, wa; };
+__device__ __forceinline__ HvmFactors hvm_factors(const HvmCombineArgs& a, real n, real lap, real A, real B) {
+    HvmFactors f{};
+    f.n = n;
+    const real n13 = cbrt(n);
+    if (a.mask & OFDFT_TF) f.g0 += (10.0 / 9.0) * kCtf / n13;
+    if (a.mask & OFDFT_LDA_X) f.g0 += (4.0 / 9.0) * kCx / (n13 * n13);
+    if (a.mask & (OFDFT_PZ_C | OFDFT_PW_C | OFDFT_CHACHIYO_C)) f.g0 += hvp_corr_second(n, a.mask);      // (linear in the flavours set)
+    if (a.mask & OFDFT_VW) {                       // -1/2 [lap(d chi) - lap(chi) w / (2 n)] / chi
+        f.v1 = -0.5 / sqrt(n);
+        f.v2 = lap / (2.0 * n);
+    }
+    if (a.mask & OFDFT_WT_NL) {
+        const real a2 = pow(n, a.al - 2.0), a1 = a2 * n;
+        if (a.two) {
+            const real b2 = pow(n, a.be - 2.0), b1 = b2 * n;
+            f.g0 += kCtf * (a.al * (a.al - 1.0) * a2 * A + a.be * (a.be - 1.0) * b2 * B);
+            f.wb = kCtf * a.al * a.be * a1;
+            f.wa = kCtf * a.al * a.be * b1;
+        } else {
+            f.g0 += kCtf * 2.0 * a.al * (a.al - 1.0) * a2 * A;
+            f.wb = kCtf * 2.0 * a.al * a.al * a1;
+        }
+    }
+    return f;
+}
+__device__ __forceinline__ real hvm_point(const HvmCombineArgs& a, const HvmFactors& f, real phi, real d, real k, real vh, real dlap, real Cb,
+                                          real Ca, acc_t* acc) {
+    const real w = 2.0 * a.cs * phi * d - k * f.n;
+    real dv = w * f.g0;
+    if (a.mask & OFDFT_HARTREE) dv += vh;
+    if (a.mask & OFDFT_VW) dv += f.v1 * (dlap - w * f.v2);
+    if (a.mask & OFDFT_WT_NL) {
+        dv += f.wb * Cb;
+        if (a.two) dv += f.wa * Ca;
+    }
+    const real P = a.c2 * phi * dv;
+    acc[0] += dv * f.n;
+    acc[1] += d * P;
+    acc[2] += phi * P;
+    return P;
+}
+template <int NC>
+static __global__ __launch_bounds__(kRedThreads) void hvm_combine_kernel(HvmCombineArgs a, acc_t* __restrict__ partial) {
+    acc_t acc[kHvpMultiScalars * NC];
+#pragma unroll
+    for (int s = 0; s < kHvpMultiScalars * NC; ++s) acc[s] = 0.0;
+    const bool has_h = a.mask & OFDFT_HARTREE, has_vw = a.mask & OFDFT_VW, has_wt = a.mask & OFDFT_WT_NL;
+    const cplx zero = mkc(0.0, 0.0);
+    HVM_FOR_PAIRS(a.npts) {
+        const cplx phi = hvm_ld(a.phi, i, n2, a.npts);
+        const bool pair = i < n2;
+        const cplx lp = has_vw ? hvm_ld(a.lap, i, n2, a.npts) : zero, A = has_wt ? hvm_ld(a.A, i, n2, a.npts) : zero;
+        const cplx B = (has_wt && a.two) ? hvm_ld(a.B, i, n2, a.npts) : zero;
+        const HvmFactors f0 = hvm_factors(a, a.cs * phi.x * phi.x, lp.x, A.x, B.x);
+        const HvmFactors f1 = hvm_factors(a, pair ? a.cs * phi.y * phi.y : (real)1.0, lp.y, A.y, B.y);
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const cplx d = hvm_ld(a.d + j * a.dstride, i, n2, a.npts);
+            const cplx vh = has_h ? hvm_ld(a.vh[j], i, n2, a.npts) : zero, dl = has_vw ? hvm_ld(a.dlap[j], i, n2, a.npts) : zero;
+            const cplx Cb = has_wt ? hvm_ld(a.Cb[j], i, n2, a.npts) : zero, Ca = (has_wt && a.two) ? hvm_ld(a.Ca[j], i, n2, a.npts) : zero;
+            const real h0 = hvm_point(a, f0, phi.x, d.x, a.k[j], vh.x, dl.x, Cb.x, Ca.x, acc + kHvpMultiScalars * j);
+            real h1 = 0.0;
+            if (pair) h1 = hvm_point(a, f1, phi.y, d.y, a.k[j], vh.y, dl.y, Cb.y, Ca.y, acc + kHvpMultiScalars * j);
+            hvm_st(a.out + j * a.ostride, i, n2, a.npts, mkc(h0, h1));
+        }
+    }
+    block_reduce_store<kHvpMultiScalars * NC>(acc, partial);
+}
+
+// ---- after the combine: out_j -= c2 phi d mu_j with d mu_j = sums[3 j] dV / N from the reduced sums, phi read once for all columns
+static __global__ void hvm_shift_kernel(const real* __restrict__ phi, real* __restrict__ out, long long ostride, int ncols, long long npts,
+                                        const acc_t* __restrict__ sums, real dV, real inv_nel, real c2) {
+    HVM_FOR_PAIRS(npts) {
+        const cplx p = hvm_ld(phi, i, n2, npts);
+        for (int j = 0; j < ncols; ++j) {
+            const real s = c2 * ((sums[kHvpMultiScalars * j] * dV) * inv_nel);
+            cplx o = hvm_ld(out + j * ostride, i, n2, npts);
+            o.x -= s * p.x;
+            o.y -= s * p.y;
+            hvm_st(out + j * ostride, i, n2, npts, o);
+        }
+    }
+}
+#undef HVM_FOR_PAIRS
+
 }  // namespace ofdft

@@ -541,6 +541,14 @@ class DistEngine:
         raise NotImplementedError('DistEngine.precondition: the kinetic preconditioner (ofdft_precondition) is served by '
                                   'single-GPU contexts; slab-decomposed contexts have no second derivative to precondition')
 
+    def hessian_vector_chi_multi(self, chi, dirs, n_elec, reuse_density=False, want_scalars=False, out=None):
+        raise NotImplementedError('DistEngine.hessian_vector_chi_multi: the Hessian-vector product (ofdft_hessian_vector_chi_multi) is '
+                                  'served by single-GPU contexts; slab-decomposed contexts have no second derivative')
+
+    def precondition_multi(self, r, kappa2, out=None):
+        raise NotImplementedError('DistEngine.precondition_multi: the kinetic preconditioner (ofdft_precondition_multi) is served by '
+                                  'single-GPU contexts; slab-decomposed contexts have no second derivative to precondition')
+
     def query(self, what):
         return self.stages.query(what)
 

@@ -85,7 +85,7 @@ def bulk_from_w2(W2, W1, volume):
 
 
 def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b3', backend=None, pme_order=None,
-                      precondition=None):
+                      precondition=None, batch=None):
     """Elastic constants (Birch coefficients) C_ijkl = d sigma_ij / d eps_kl at the ground state `chi`, with the relaxation of the
     density under the strain included.
 
@@ -100,7 +100,10 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
     `rel_residual`, `reason` (lists over the six solves, in the order xx, yy, zz, yz, xz, xy), `hvp_count`, and
     `ground_state_gradient` = max|g| / dV of the closure at `chi`.  A solve that ends for another reason than convergence raises
     a warning: unpreconditioned, the iteration count of the conjugate gradients grows with the grid; `precondition` (None, 'auto'
-    or kappa^2 > 0, `optimize.HipCgBackend`) takes the grid out of it.
+    or kappa^2 > 0, `optimize.HipCgBackend`) takes the grid out of it.  `batch`: None, or 1 .. 8: the six right-hand sides, in the
+    same order, go `batch` columns at a time through batched solves (`optimize.density_response_multi`); the
+    returned dict is the same, `hvp_count` then counting batched products.  With `backend` given, `batch` is that backend's own
+    attribute, as `precondition` is.
 
     NotImplementedError, before any device work and naming the cause: PME, a slab-decomposed engine, an fp32 engine, a term
     without a second derivative.  (`backend`: an object with HipElasticBackend's methods -- the tests' numpy double.)"""
@@ -108,6 +111,7 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
     species, frac, charges = optimize.normalise_species(species)
     optimize._own_backend_only('elastic_constants', backend, precondition)
     optimize.check_precondition(precondition)
+    batch = optimize.resolve_batch('elastic_constants', backend, batch)
     if backend is None:
         why = refusal(engine, pme_order)
         if why:
@@ -127,11 +131,17 @@ def elastic_constants(engine, box_vecs, species, chi, Rc=None, rtol=1e-10, maxit
         V = b.potential_strain_gradient(n)
         log = optimize.new_solve_log()
         R6 = np.zeros((6, 6))
-        for c in range(6):
-            r = optimize.density_response(engine, chi, n_elec, V[c], rtol=rtol, maxiter=maxiter, backend=b.cg)
-            for a in range(6):
-                R6[a, c] = float((V[a] * r['dn']).sum()) * b.dV
-            optimize.log_solve(log, r)
+        if batch is None:
+            for c in range(6):
+                r = optimize.density_response(engine, chi, n_elec, V[c], rtol=rtol, maxiter=maxiter, backend=b.cg)
+                for a in range(6):
+                    R6[a, c] = float((V[a] * r['dn']).sum()) * b.dV
+                optimize.log_solve(log, r)
+        else:               # the same six right-hand sides in the same order, `batch` columns per solve
+            for c, r in enumerate(optimize.batched_responses(b, engine, chi, n_elec, [V[c] for c in range(6)], batch, rtol, maxiter)):
+                for a in range(6):
+                    R6[a, c] = float((V[a] * r['dn']).sum()) * b.dV
+                optimize.log_solve(log, r)
     finally:
         if backend is None:
             b.close()

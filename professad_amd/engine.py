@@ -274,6 +274,70 @@ class Engine:
         self._check(self.lib.ofdft_precondition(self._ctx, _ptr(r), _ptr(out), kappa2, self._stream()), 'ofdft_precondition')
         return out
 
+    # -- several columns per call (ofdft_*_multi)
+    def _multi_refusal(self, who, what):
+        """NotImplementedError, before any device work, where the multi entries are not served"""
+        if self.dtype != torch.double:
+            raise NotImplementedError('Engine.%s: %s is fp64 work (libofdft_hip.so); an fp32 engine does not serve it' % (who, what))
+        if self.shape != self.global_shape:
+            raise NotImplementedError('Engine.%s: %s is served by single-GPU contexts' % (who, what))
+
+    def _grid_stack(self, t, name):
+        """a stack [B, *shape] of 1 .. MULTI_MAX grid fields as the multi entries take it: contiguous fp64 on this device -> B"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor' % name)
+        if t.dim() != 4 or tuple(t.shape[1:]) != self.shape:
+            raise ValueError('%s has shape %s; a stack [B, %d, %d, %d] of grid fields is needed' % ((name, tuple(t.shape)) + self.shape))
+        if not 1 <= t.shape[0] <= N.MULTI_MAX:
+            raise ValueError('%s stacks %d columns; the multi entries take 1 .. %d (OFDFT_MULTI_MAX)' % (name, t.shape[0], N.MULTI_MAX))
+        if t.device != self._dev_exact or t.dtype != self.dtype or not t.is_contiguous() or t.requires_grad:
+            raise ValueError('%s must be a contiguous %s stack on %s without requires_grad' % (name, self.dtype, self._dev_exact))
+        return int(t.shape[0])
+
+    def _stack_out(self, out, src, who):
+        if out is None:
+            return torch.empty_like(src)
+        if self._grid_stack(out, 'out') != src.shape[0]:
+            raise ValueError('Engine.%s: out stacks %d columns, the input %d' % (who, out.shape[0], src.shape[0]))
+        nbytes = src.numel() * src.element_size()
+        if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError('Engine.%s: out aliases the input stack -- the call is not in place, give another `out`' % who)
+        return out
+
+    def hessian_vector_chi_multi(self, chi, dirs, n_elec, reuse_density=False, want_scalars=False, out=None):
+        """``hessian_vector_chi`` at a stationary point (g = 0) for a stack ``dirs`` [B, *shape] of B = 1 .. 8 directions in one call
+        (ofdft_hessian_vector_chi_multi): chi, the density-side fields and the density-only factors are read or
+        formed once for all columns.  -> H dirs [B, *shape], or with ``want_scalars`` (list of B dicts as ``hessian_vector_chi``
+        returns them; H dirs).  Each column agrees with the single-column entry to rounding.  ``reuse_density=True`` may follow a
+        call of either entry made without it on the same chi.  Single GPU and fp64, the terms of ``hessian_vector``."""
+        self._multi_refusal('hessian_vector_chi_multi', 'the Hessian-vector product')
+        from . import optimize
+        why = optimize.second_order_refusal(self)
+        if why:
+            raise NotImplementedError('Engine.hessian_vector_chi_multi: ' + why)
+        B = self._grid_stack(dirs, 'dirs')
+        chi = self._grid_tensor(chi, 'chi')
+        out = self._stack_out(out, dirs, 'hessian_vector_chi_multi')
+        s = (C.c_double * (N.HVC_NSCALARS * B))() if want_scalars else None
+        self._check(self.lib.ofdft_hessian_vector_chi_multi(self._ctx, _ptr(chi), _ptr(dirs), self.npts, B, float(n_elec), _ptr(out), self.npts,
+                                                            s, 1 if reuse_density else 0, self._stream()), 'ofdft_hessian_vector_chi_multi')
+        if not want_scalars:
+            return out
+        return [dict(zip(N.HVC_NAMES, s[N.HVC_NSCALARS * j:N.HVC_NSCALARS * (j + 1)])) for j in range(B)], out
+
+    def precondition_multi(self, r, kappa2, out=None):
+        """``precondition`` for a stack ``r`` [B, *shape] of B = 1 .. 8 fields in one call with one synchronisation
+        (ofdft_precondition_multi) -> z [B, *shape] (``out`` if given; it must not overlap ``r``)."""
+        self._multi_refusal('precondition_multi', 'the kinetic preconditioner')
+        kappa2 = float(kappa2)
+        if not (kappa2 > 0.0 and math.isfinite(kappa2)):
+            raise ValueError('Engine.precondition_multi: kappa2 must be positive and finite, got %r' % kappa2)
+        B = self._grid_stack(r, 'r')
+        out = self._stack_out(out, r, 'precondition_multi')
+        self._check(self.lib.ofdft_precondition_multi(self._ctx, _ptr(r), self.npts, _ptr(out), self.npts, B, kappa2, self._stream()),
+                    'ofdft_precondition_multi')
+        return out
+
     @property
     def volume(self):
         """cell volume of the last set_cell"""

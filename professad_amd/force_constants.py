@@ -40,7 +40,7 @@ def refusal(engine, pme_order=None):
 
 
 def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b2',
-                    impose_asr=False, backend=None, pme_order=None, precondition=None):
+                    impose_asr=False, backend=None, pme_order=None, precondition=None, batch=None):
     """Phi[p, b, i, j] = -dF[p, i] / dR[b, j] for p in `primitive_ion_indices` (default: every ion) and all ions b.
 
     engine: a single-GPU fp64 `Engine` with the caller's term set (it includes ion_electron) on the cell `box_vecs`.
@@ -57,6 +57,9 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
     A solve that ends for another reason than convergence raises a warning: unpreconditioned, the iteration count of the conjugate
     gradients grows with the grid (about 100 at 16^3, 400 at 64^3 for fcc Al), so larger grids need a larger `maxiter` -- or
     `precondition`: None, 'auto' or kappa^2 > 0 (`optimize.HipCgBackend`), the kinetic preconditioner, about 20 iterations at any grid.
+    `batch`: None, or 1 .. 8: the 3 P right-hand sides, in the same p-major order, go `batch` columns at a time through batched
+    solves (`optimize.density_response_multi`).  The returned dict is the same, `hvp_count` then counting batched
+    products.  With `backend` given, `batch` is that backend's own attribute, as `precondition` is.
 
     NotImplementedError, before any device work and naming the cause: PME, a slab-decomposed engine, an fp32 engine, a term
     without a second derivative.  (`backend`: an object with HipFcBackend's methods -- the tests' numpy double.)"""
@@ -69,6 +72,7 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
         raise ValueError('primitive_ion_indices must name at least one ion, each in [0, %d)' % nions)
     optimize._own_backend_only('force_constants', backend, precondition)
     optimize.check_precondition(precondition)
+    batch = optimize.resolve_batch('force_constants', backend, batch)
     if backend is None:
         why = refusal(engine, pme_order)
         if why:
@@ -86,12 +90,22 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
         direct = np.zeros_like(ion_ion)
         response = np.zeros_like(ion_ion)
         log = optimize.new_solve_log()
-        for q, p in enumerate(rows):
-            direct[q, p] = D[p]
-            dv = b.potential_gradient(p)
-            for i in range(3):
-                r = optimize.density_response(engine, chi, n_elec, dv[i], rtol=rtol, maxiter=maxiter, backend=b.cg)
-                response[q, :, i, :] = -b.ion_electron_forces(r['dn'])
+        if batch is None:
+            for q, p in enumerate(rows):
+                direct[q, p] = D[p]
+                dv = b.potential_gradient(p)
+                for i in range(3):
+                    r = optimize.density_response(engine, chi, n_elec, dv[i], rtol=rtol, maxiter=maxiter, backend=b.cg)
+                    response[q, :, i, :] = -b.ion_electron_forces(r['dn'])
+                    optimize.log_solve(log, r)
+        else:               # the same 3 P right-hand sides in the same order, `batch` columns per solve, across ions
+            dvs = []
+            for q, p in enumerate(rows):
+                direct[q, p] = D[p]
+                dv = b.potential_gradient(p)
+                dvs.extend(dv[i] for i in range(3))
+            for k, r in enumerate(optimize.batched_responses(b, engine, chi, n_elec, dvs, batch, rtol, maxiter)):
+                response[k // 3, :, k % 3, :] = -b.ion_electron_forces(r['dn'])
                 optimize.log_solve(log, r)
     finally:
         if backend is None:

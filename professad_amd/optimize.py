@@ -21,7 +21,10 @@ of the direction in the basis {S_j, Y_j, g}.  On several ranks the sweep's local
 consumers: both solve with the Hessian of E[chi] by conjugate gradients whose vectors live behind `ofdft_cg_*` and whose
 products are `ofdft_hessian_vector_chi` (`HipCgBackend`, `solve_projected`).  Single GPU, fp64.  With
 `precondition` (off by default) the solve is preconditioned by the kinetic operator 1 / (k^2 + kappa^2) (`ofdft_precondition`;
-DESIGN.md §9i), which takes the grid out of its iteration count.
+DESIGN.md §9i), which takes the grid out of its iteration count.  `density_response_multi` (and `batch=` of the drivers in
+force_constants.py and elastic.py) runs up to eight such solves in lockstep on `HipCgMultiBackend` (`ofdft_cgm_*`,
+`ofdft_hessian_vector_chi_multi`, `ofdft_precondition_multi`): one product, one preconditioner call and one launch
+per sweep for all right-hand sides.
 """
 import ctypes as C
 import math
@@ -659,6 +662,202 @@ def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=N
     return dict(dn=dn, dmu=dmu, iterations=iters, rel_residual=rel, reason=reason, hvp_count=nprod)
 
 
+# ---- several right-hand sides per solve
+MULTI_MAX = 8      # OFDFT_MULTI_MAX
+
+
+def check_batch(value):
+    """the `batch` argument of the response drivers: None (one solve per right-hand side) or an integer 1 .. 8 columns per solve"""
+    if value is None:
+        return None
+    if isinstance(value, (int, np.integer)) and not isinstance(value, bool) and 1 <= int(value) <= MULTI_MAX:
+        return int(value)
+    raise ValueError('batch must be None or an integer in 1 .. %d (OFDFT_MULTI_MAX), got %r' % (MULTI_MAX, value))
+
+
+def _stack(fields):
+    return torch.stack(list(fields)) if isinstance(fields[0], torch.Tensor) else np.stack(list(fields))
+
+
+class HipCgMultiBackend:
+    """`HipCgBackend` for up to `ncols` right-hand sides in lockstep (ofdft_cgm_*, ofdft_hessian_vector_chi_multi and
+    ofdft_precondition_multi in libofdft_hip.so; no CPU fallback): the columns of x, r, p, q, z live behind the
+    handle, one product call forms q_j = H p_j for all of them.  The methods of `HipCgBackend`, taking a stack `bs` [B, *shape]
+    and returning per-column lists.  Not block Krylov: each column is the recurrence a solo solve runs, with its own
+    coefficients, exit reason and iteration count; a column that has ended is frozen while the others go on."""
+
+    def __init__(self, engine, ncols, precondition=None):
+        why = second_order_refusal(engine)
+        if why:
+            raise NotImplementedError(why)
+        if check_batch(ncols) is None:
+            raise ValueError('ncols must be an integer in 1 .. %d' % MULTI_MAX)
+        self.precondition = check_precondition(precondition)
+        self.eng, self.lib, self.ncols_max = engine, engine.lib, int(ncols)
+        self.dV = engine.volume / engine.npts
+        self._h = C.c_void_p(0)
+        rc = self.lib.ofdft_cgm_create(C.byref(self._h), engine.npts, self.ncols_max, engine._dev_index)
+        if rc != 0:
+            raise RuntimeError('ofdft_cgm_create failed with code %d' % rc)
+        self._r, self._p, self._q, self._z = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        ld = C.c_longlong(0)
+        self._check(self.lib.ofdft_cgm_vectors(self._h, None, C.byref(self._r), C.byref(self._p), C.byref(self._q), C.byref(ld)),
+                    'ofdft_cgm_vectors')
+        self._ld = ld.value
+        self._scal = (C.c_double * (5 * MULTI_MAX))()
+        self._pq, self._phiq = (C.c_double * MULTI_MAX)(), (C.c_double * MULTI_MAX)()
+        self.ncols = 0
+
+    preconditioned = HipCgBackend.preconditioned
+    set_precondition = HipCgBackend.set_precondition
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (what, rc, self.lib.ofdft_cgm_last_error(self._h).decode()))
+
+    def start(self, phi, bs, rtol, maxiter):
+        e = self.eng
+        phi = e._grid_tensor(phi, 'chi')
+        B = e._grid_stack(bs, 'bs')
+        if B > self.ncols_max:
+            raise ValueError('bs stacks %d columns, this backend was built for %d' % (B, self.ncols_max))
+        self._check(self.lib.ofdft_cgm_set_preconditioned(self._h, 1 if self.preconditioned else 0), 'ofdft_cgm_set_preconditioned')
+        if self.preconditioned and not self._z:
+            self._check(self.lib.ofdft_cgm_z(self._h, C.byref(self._z)), 'ofdft_cgm_z')
+        self._check(self.lib.ofdft_cgm_start(self._h, _vp(phi), _vp(bs), e.npts, B, float(rtol), int(maxiter), None, e._stream()),
+                    'ofdft_cgm_start')
+        self.ncols = B
+
+    def product(self, phi, n_elec, reuse):
+        """q_j = H p_j for every column -> (p_j.q_j, phi.q_j) as two lists"""
+        e = self.eng
+        phi = e._grid_tensor(phi, 'chi')
+        e._check(self.lib.ofdft_hessian_vector_chi_multi(e._ctx, _vp(phi), self._p, self._ld, self.ncols, float(n_elec), self._q, self._ld,
+                                                         self._scal, 1 if reuse else 0, e._stream()), 'ofdft_hessian_vector_chi_multi')
+        return [self._scal[5 * j] for j in range(self.ncols)], [self._scal[5 * j + 1] for j in range(self.ncols)]
+
+    def _reasons(self):
+        return [s[1] for s in self.status()]
+
+    def pre_direction(self, phi, n_elec):
+        """preconditioned mode, in front of every product: z_j = M^-1 r_j, then p_j = P z_j + beta_j p_j -> exit reasons"""
+        e = self.eng
+        kappa2 = kinetic_kappa2(n_elec, e.volume) if self.precondition == 'auto' else self.precondition
+        e._check(self.lib.ofdft_precondition_multi(e._ctx, self._r, self._ld, self._z, self._ld, self.ncols, float(kappa2), e._stream()),
+                 'ofdft_precondition_multi')
+        running = C.c_int(0)
+        phi = e._grid_tensor(phi, 'chi')
+        self._check(self.lib.ofdft_cgm_direction(self._h, _vp(phi), None, C.byref(running), e._stream()), 'ofdft_cgm_direction')
+        return self._reasons()
+
+    def step(self, phi, p_dot_q, phi_dot_q):
+        running = C.c_int(0)
+        phi = self.eng._grid_tensor(phi, 'chi')
+        for j in range(self.ncols):
+            self._pq[j], self._phiq[j] = float(p_dot_q[j]), float(phi_dot_q[j])
+        self._check(self.lib.ofdft_cgm_step(self._h, _vp(phi), self._pq, self._phiq, C.byref(running), self.eng._stream()), 'ofdft_cgm_step')
+        return self._reasons()
+
+    def status(self):
+        """-> [(iterations, reason, |r| / |b|)] per column"""
+        out = []
+        it, reason, rel = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        for j in range(self.ncols):
+            self._check(self.lib.ofdft_cgm_status(self._h, j, C.byref(it), C.byref(reason), C.byref(rel)), 'ofdft_cgm_status')
+            out.append((it.value, reason.value, rel.value))
+        return out
+
+    def solution(self):
+        x = torch.empty((self.ncols,) + tuple(self.eng.shape), dtype=self.eng.dtype, device=self.eng._dev_exact)
+        self._check(self.lib.ofdft_cgm_solution(self._h, C.c_void_p(x.data_ptr()), self.eng.npts, self.eng._stream()), 'ofdft_cgm_solution')
+        return x
+
+    def hv(self, den, w):
+        return self.eng.hessian_vector(den, w)
+
+    def close(self):
+        if self._h:
+            self.lib.ofdft_cgm_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_projected_multi(backend, phi, bs, n_elec, rtol, maxiter):
+    """`solve_projected` at a stationary point (g = 0) for the stack `bs` [B, ...] of right-hand sides, the B recurrences in
+    lockstep on a backend with `HipCgMultiBackend`'s methods: one product call per iteration serves every column, a column that
+    has ended stays as it ended, and the run ends when every column has.
+    -> (x [B, ...], iterations [B], exit reasons [B], |r| / |b| [B], batched products)"""
+    backend.start(phi, bs, rtol, maxiter)
+    reasons = [s[1] for s in backend.status()]
+    pre = bool(getattr(backend, 'preconditioned', False))
+    products = 0
+    while any(r == CG_RUNNING for r in reasons):
+        if pre:
+            reasons = backend.pre_direction(phi, n_elec)
+            if not any(r == CG_RUNNING for r in reasons):
+                break
+        pq, phiq = backend.product(phi, n_elec, products > 0)
+        products += 1
+        reasons = backend.step(phi, pq, phiq)
+    st = backend.status()
+    return backend.solution(), [s[0] for s in st], [s[1] for s in st], [s[2] for s in st], products
+
+
+def density_response_multi(engine, chi, n_elec, dvs, rtol=1e-10, maxiter=500, backend=None, precondition=None):
+    """`density_response` to the B = 1 .. 8 perturbations stacked in `dvs` [B, ...] by one batched solve (`solve_projected_multi`).
+    Returns the keys of `density_response`: `dn` as [B, ...]; `dmu`, `iterations`, `rel_residual` and `reason` as lists over the
+    columns; `hvp_count` counts batched products.  Column j is the result `density_response` gives for dvs[j], to rounding; each
+    dmu_j is defined exactly as there.  (`backend`: another solver with HipCgMultiBackend's methods -- the tests' numpy double.)"""
+    _own_backend_only('density_response_multi', backend, precondition)
+    B = len(dvs)
+    if check_batch(B) is None:
+        raise ValueError('dvs must stack 1 .. %d perturbations' % MULTI_MAX)
+    b = backend if backend is not None else HipCgMultiBackend(engine, B, precondition)
+    try:
+        dV = b.dV
+        S = float((chi * chi).sum())
+        c = n_elec / (S * dV)
+        n = c * chi * chi
+        rhs = []
+        for j in range(B):
+            shift = float((dvs[j] * n).sum()) * dV / n_elec
+            rhs.append((-2.0 * c * dV) * chi * (dvs[j] - shift))
+        dchi, iters, reasons, rels, nprod = solve_projected_multi(b, chi, _stack(rhs), n_elec, rtol, maxiter)
+        dn = [2.0 * c * chi * dchi[j] for j in range(B)]
+        dmu = [float((n * (b.hv(n, dn[j]) + dvs[j])).sum()) * dV / n_elec for j in range(B)]
+    finally:
+        if backend is None:
+            b.close()
+    return dict(dn=_stack(dn), dmu=dmu, iterations=iters, rel_residual=rels, reason=reasons, hvp_count=nprod)
+
+
+def resolve_batch(who, backend, batch):
+    """the `batch` argument of a driver: it configures the backend the call builds; a caller's backend carries its own (`batch`
+    attribute, None without one), as it carries its own preconditioner"""
+    if backend is not None and batch is not None:
+        raise ValueError('%s: `batch` configures the backend the call builds; with `backend` given, set it on that backend' % who)
+    return check_batch(batch if backend is None else getattr(backend, 'batch', None))
+
+
+def batched_responses(b, engine, chi, n_elec, dvs, batch, rtol, maxiter):
+    """the results `density_response` would give for each of the perturbations `dvs` (a list), in their order, from batched solves
+    of `batch` columns on the driver backend's multi solver `b.cgm(batch)`; `hvp_count` of the first of a group carries the group's
+    batched products, the others 0"""
+    out = []
+    for j0 in range(0, len(dvs), batch):
+        group = dvs[j0:j0 + batch]
+        r = density_response_multi(engine, chi, n_elec, _stack(group), rtol=rtol, maxiter=maxiter, backend=b.cgm(batch))
+        for j in range(len(group)):      # (dn: a field of its own, not a view into the stack)
+            out.append(dict(dn=r['dn'][j].clone() if isinstance(r['dn'], torch.Tensor) else r['dn'][j].copy(), dmu=r['dmu'][j], iterations=r['iterations'][j], rel_residual=r['rel_residual'][j],
+                            reason=r['reason'][j], hvp_count=r['hvp_count'] if j == 0 else 0))
+    return out
+
+
 # ---- what the drivers over `density_response` share (force_constants.py, elastic.py)
 A_PER_BOHR = 5.29177210903e-11 * 1e10      # system.py:27-33 (CODATA 2018)
 
@@ -696,6 +895,16 @@ class HipResponseBackend:
         self.volume = engine.volume
         self.dV = engine.volume / engine.npts
         self.cg = HipCgBackend(engine)
+        self._cgm = None
+
+    def cgm(self, ncols):
+        """the solver of the batched solves (`batch`), built on first use for `ncols` columns with the preconditioner of `cg`"""
+        if self._cgm is None or self._cgm.ncols_max < ncols:
+            if self._cgm is not None:
+                self._cgm.close()
+            self._cgm = HipCgMultiBackend(self.eng, ncols)
+        self._cgm.set_precondition(self.cg.precondition)
+        return self._cgm
 
     def ground_state_gradient(self, chi, n_elec):
         """max|g| / dV of the closure at chi with v_ext rebuilt from the ions"""
@@ -706,6 +915,8 @@ class HipResponseBackend:
 
     def close(self):
         self.cg.close()
+        if self._cgm is not None:
+            self._cgm.close()
 
 
 def new_solve_log():
