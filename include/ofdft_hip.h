@@ -295,13 +295,21 @@ int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double
  * Served: ion_electron (hv = 0, no vext needed), hartree, tf, vw, wt_nl (any alpha, beta), lda_x, pz_c, pw_c, chachiyo_c.  In wt_nl the
  * n0 of the kernel is mean(den) vol of the den passed in and a CONSTANT of the differentiation (functionals.py:646-647 take it with
  * .item()), so a finite difference of the potential along a w of non-zero mean differs.  Refused with OFDFT_EINVAL, the message
- * naming the term: wgc99_nl, pbe_x, pbe_c, gga_k, vwgtf, nlk, OFDFT_P_WTS_KIND = 1; slab-decomposed contexts; the fp32 library.
+ * naming the term: wgc99_nl, pbe_x, pbe_c (these two unless OFDFT_OPT_HVP_GGA = 1, below), gga_k, vwgtf, nlk, OFDFT_P_WTS_KIND = 1;
+ * slab-decomposed contexts; the fp32 library.
  * reuse_density: 0 computes everything and leaves the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) in workspaces of their
  * own; 1 = the caller asserts den holds the values of the previous call made with 0 and those transforms are skipped (Hartree 1 + 1
  * transforms either way; vW 2 + 2, with reuse 1 + 1; wt_nl 2 + 2 / 1 + 1 for alpha = beta, else 4 + 4 / 2 + 2) -- bitwise the same
  * hv.  ofdft_set_cell, ofdft_set_terms, ofdft_set_option and every other evaluation (energy, stress, ofdft_dist_*, ofdft_rfftn /
  * ofdft_irfftn) invalidate the retained fields; 1 with nothing valid retained returns OFDFT_ESTATE.  Sets OFDFT_Q_FFT_COUNT,
- * OFDFT_Q_LAUNCH_COUNT and OFDFT_Q_KERNEL_MS as the energy calls do.  No atomics: bitwise reproducible. */
+ * OFDFT_Q_LAUNCH_COUNT and OFDFT_Q_KERNEL_MS as the energy calls do.  No atomics: bitwise reproducible.
+ * With OFDFT_OPT_HVP_GGA = 1 this entry and ofdft_hessian_vector_chi also serve pbe_x and pbe_c: for
+ * E = dV sum f(n, sigma), sigma = sum_a (D_a n)^2, dsigma = 2 sum_a D_a n D_a w,
+ *     hv = f_nn w + f_nsigma dsigma - 2 sum_a D_a [(f_sigma,n w + f_sigma,sigma dsigma) D_a n + f_sigma D_a w]
+ * in two transform stages around a pointwise mid kernel: 2 + 6 + 3 + 1 = 12 transforms more, 8 with reuse_density = 1 (grad n joins
+ * the retained fields; the second partials are formed again on every call).  quad_terms_host reports pbe_x and pbe_c from
+ * sum f_nn w^2 + 2 f_nsigma w dsigma + f_sigma,sigma dsigma^2 + 2 f_sigma |grad w|^2.  Limits: den > 0 everywhere, as for
+ * evaluating PBE itself; single GPU; fp64. */
 int  ofdft_hessian_vector(ofdft_ctx* ctx, const void* den_dev, const void* dir_dev, void* hv_dev,
                           double* quad_terms_host /* [OFDFT_NTERMS] or NULL */, int reuse_density, void* stream);
 
@@ -619,6 +627,10 @@ int  ofdft_cgm_solution(ofdft_cgm* h, void* x_out_dev, long long stride, void* s
 #define OFDFT_OPT_WGC_FOLD 28    /* 1 (default): on cells with orthogonal axes the cross-wave x pass reads the WGC99 table entry of x > n0 / 2 at
                                      n0 - x (|k| is even along a line there; functionals.py:968-972 depends on |k| only): both uses of an entry
                                      fall into one tile, the second is a cache hit, the pass' table traffic halves.  0: every k-point its own entry */
+#define OFDFT_OPT_HVP_GGA 18      /* 0 (default): the second-derivative entries refuse pbe_x and pbe_c by name; 1: ofdft_hessian_vector and
+                                     ofdft_hessian_vector_chi serve them (second transform stage, see there).  ofdft_hessian_vector_chi_multi,
+                                     ofdft_potential_strain_gradient and ofdft_strain_hessian refuse them under either value.  Any other value:
+                                     OFDFT_EINVAL.  Both libraries accept it; it matters in the fp64 one */
 #define OFDFT_OPT_XWAVE 8         /* fused x passes: 1 (default) = the cross-wave kernel (whole runs of memory-adjacent lines per access, the
                                      radix-4 / -8 step of the line transform across the waves of a workgroup) for 256- and 512-point lines
                                      and, for passes over three or more spectra, 1024-point lines; elsewhere the wave-local kernel (a line of

@@ -6,6 +6,10 @@
 //   forward batch, one spectral kernel over every spectrum, inverse batch
 //   combine  n, w, the inverse-transformed fields -> hv, per-term sums of w hv_t
 // Density-only fields (lap sqrt n, K * n^beta, K * n^alpha) stay in "hv:lap", "hv:A", "hv:B" for calls with reuse_density = 1.
+// With pbe_x or pbe_c in the term set (OFDFT_OPT_HVP_GGA = 1) a second stage runs in front of that batch:
+//   forward n, w | spec_grad | inverse -> grad n ("hv:gn0..2", density-only: retained too), grad w
+//   mid      n, w, grad n, grad w -> f_nn w + f_ns dsigma ("hv:gpw"), the flux over grad w, the sums of pbe_x and pbe_c
+//   forward flux | spec_div | inverse -> "hv:gdiv";   the combine kernel then starts hv from gpw - 2 gdiv
 //
 // hvp_core schedules this once for both entries.  ofdft_hessian_vector hands it (n, w); ofdft_hessian_vector_chi hands it
 // (phi, d) with HvpChi set: head and combine then run their chi-space instantiations, which form n and dn on the fly, and the
@@ -25,11 +29,16 @@ struct HvpChi {                  // chi-space call: nullptr for the n-space prod
     bool want;
 };
 
-const char* hvp_refusal(ofdft_ctx* c) {
+// which entry asks: the two single-column products serve pbe_x / pbe_c under OFDFT_OPT_HVP_GGA = 1 (the second stage of hvp_core); the
+// multi-column product and the strain entries have no PBE kernels and keep refusing them whatever the option says
+enum HvpCaller { kHvpNoGga = 0, kHvpGga = 1 };
+
+const char* hvp_refusal(ofdft_ctx* c, HvpCaller caller) {
     static const struct { unsigned bit; const char* name; } refused[] = {
         {OFDFT_WGC99_NL, "wgc99_nl"}, {OFDFT_PBE_X, "pbe_x"}, {OFDFT_PBE_C, "pbe_c"}, {OFDFT_GGA_K, "gga_k"}, {OFDFT_VWGTF, "vwgtf"}, {OFDFT_NLK, "nlk"}};
+    const unsigned served = (caller == kHvpGga && c->hvp_gga) ? (OFDFT_PBE_X | OFDFT_PBE_C) : 0u;
     for (const auto& r : refused)
-        if (c->mask & r.bit) return r.name;
+        if (c->mask & r.bit & ~served) return r.name;
     return nullptr;
 }
 
@@ -41,6 +50,7 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
     const long long npts = c->npts;
     const double inv_n = 1.0 / (double)npts;
     const bool has_h = mask & OFDFT_HARTREE, has_vw = mask & OFDFT_VW, has_wt = mask & OFDFT_WT_NL;
+    const bool has_gga = mask & (OFDFT_PBE_X | OFDFT_PBE_C);         // (hvp_checks let it through: OFDFT_OPT_HVP_GGA = 1)
 
     double nel = c->hvp_nel;
     if (chi) {
@@ -67,9 +77,23 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
         op[ns++] = o;
         return 0;
     };
-    if (has_h) {
+    if (has_h || (chi && has_gga))
         if (int rc = real_ws(c, "hv:vh", &vh)) return rc;
+    if (has_h)
         if (int rc = item(chi ? vh : w, "s0", SPEC_HARTREE, vh)) return rc;      // chi space: the head writes dn into "hv:vh"; transformed in place
+    // PBE: grad n ("hv:gn0..2", density-only: retained), grad w -> flux ("hv:gw0..2"), the mid kernel's pointwise part and div flux
+    real *gn[3] = {}, *gw[3] = {}, *gpw = nullptr, *gdiv = nullptr, *nfield = nullptr;
+    if (has_gga) {
+        static const char* const gn_name[3] = {"hv:gn0", "hv:gn1", "hv:gn2"};
+        static const char* const gw_name[3] = {"hv:gw0", "hv:gw1", "hv:gw2"};
+        for (int a = 0; a < 3; ++a) {
+            if (int rc = real_ws(c, gn_name[a], &gn[a])) return rc;
+            if (int rc = real_ws(c, gw_name[a], &gw[a])) return rc;
+        }
+        if (int rc = real_ws(c, "hv:gpw", &gpw)) return rc;
+        if (int rc = real_ws(c, "hv:gdiv", &gdiv)) return rc;
+        if (chi)
+            if (int rc = real_ws(c, "hv:gn", &nfield)) return rc;                // chi space: the head writes n here for its transform
     }
     if (has_vw) {
         if (int rc = real_ws(c, "hv:lap", &lap)) return rc;
@@ -92,7 +116,7 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
             if (int rc = item(Ca, "s3", SPEC_LINDHARD, Ca)) return rc;
         }
     }
-    if (has_vw || has_wt || (chi && has_h)) {
+    if (has_vw || has_wt || (chi && (has_h || has_gga))) {
         HvpChiHeadArgs ha{};
         ha.n = den;
         ha.w = w;
@@ -107,10 +131,66 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
             ha.cs = chi->cs;
             ha.k = 2.0 * chi->a / chi->S;
             ha.dn = vh;
+            ha.nout = nfield;
             OFDFT_LAUNCH(c, st, "hvp_head", hvp_head_kernel<HvpChiHeadArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, ha);
         } else {
             OFDFT_LAUNCH(c, st, "hvp_head", hvp_head_kernel<HvpHeadArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, (HvpHeadArgs)ha);
         }
+    }
+    double gga_sums[kHvpGgaScalars] = {0.0, 0.0};
+    if (has_gga) {
+        // stage 1: n^ (not with reuse) and w^ -> their gradients; stage 2 behind the mid kernel: the three flux fields -> div flux.
+        // It runs in front of the batch below: in chi space that batch transforms "hv:vh" (dn) in place, and this one reads it.
+        const real* wsrc = chi ? vh : w;
+        const real* nsrc = chi ? nfield : den;
+        cplx *sw[4], *sn[4];
+        static const char* const sw_name[4] = {"sg:w", "s1", "s2", "s3"};
+        static const char* const sn_name[4] = {"sg:n", "sg:n0", "sg:n1", "sg:n2"};
+        for (int a = 0; a < 4; ++a) {
+            if (int rc = spec_ws(c, sw_name[a], &sw[a])) return rc;
+            if (!reuse)
+                if (int rc = spec_ws(c, sn_name[a], &sn[a])) return rc;
+        }
+        const real* gin[2] = {wsrc, nsrc};
+        cplx* gsp[2] = {sw[0], reuse ? nullptr : sn[0]};
+        if (int rc = rfftn_internal_multi(c, gin, gsp, reuse ? 1 : 2, st)) return rc;
+        const int sp_grid = grid_for(c->g.total);
+        OFDFT_LAUNCH(c, st, "spec_grad", spec_grad_kernel, dim3(sp_grid), dim3(256), 0, (const cplx*)sw[0], sw[1], sw[2], sw[3], c->kg);
+        cplx* isp[6] = {sw[1], sw[2], sw[3], nullptr, nullptr, nullptr};
+        real* iout[6] = {gw[0], gw[1], gw[2], gn[0], gn[1], gn[2]};
+        int ni = 3;
+        if (!reuse) {
+            OFDFT_LAUNCH(c, st, "spec_grad", spec_grad_kernel, dim3(sp_grid), dim3(256), 0, (const cplx*)sn[0], sn[1], sn[2], sn[3], c->kg);
+            for (int a = 0; a < 3; ++a) isp[ni++] = sn[1 + a];
+        }
+        for (int b0 = 0; b0 < ni; b0 += kBsBatch)
+            if (int rc = irfftn_internal_multi(c, isp + b0, iout + b0, std::min(kBsBatch, ni - b0), inv_n, st)) return rc;
+        HvpChiGgaMidArgs ma{};
+        ma.n = den;
+        ma.w = w;
+        for (int a = 0; a < 3; ++a) {
+            ma.gn[a] = gn[a];
+            ma.gw[a] = gw[a];
+        }
+        ma.pw = gpw;
+        ma.npts = npts;
+        ma.x = (mask & OFDFT_PBE_X) ? 1 : 0;
+        ma.c = (mask & OFDFT_PBE_C) ? 1 : 0;
+        const int mblocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
+        if (chi) {
+            ma.cs = chi->cs;
+            ma.k = 2.0 * chi->a / chi->S;
+            OFDFT_LAUNCH(c, st, "hvp_gga_mid", hvp_gga_mid_kernel<HvpChiGgaMidArgs>, dim3(mblocks), dim3(kRedThreads), 0, ma, c->d_partial);
+        } else {
+            OFDFT_LAUNCH(c, st, "hvp_gga_mid", hvp_gga_mid_kernel<HvpGgaMidArgs>, dim3(mblocks), dim3(kRedThreads), 0, (HvpGgaMidArgs)ma, c->d_partial);
+            if (quad_terms)            // (before the combine kernel takes the partial buffer)
+                if (int rc = fetch_partials(c, mblocks, kHvpGgaScalars, gga_sums, st)) return rc;
+        }
+        const real* fl[3] = {gw[0], gw[1], gw[2]};
+        if (int rc = rfftn_internal_multi(c, fl, sw + 1, 3, st)) return rc;
+        OFDFT_LAUNCH(c, st, "spec_div", spec_div_kernel, dim3(sp_grid), dim3(256), 0, (const cplx*)sw[1], (const cplx*)sw[2], (const cplx*)sw[3], sw[0],
+                     c->kg);
+        if (int rc = irfftn_internal_multi(c, sw, &gdiv, 1, inv_n, st)) return rc;
     }
     if (ns) {
         for (int b0 = 0; b0 < ns; b0 += kBsBatch)
@@ -145,22 +225,32 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
     ca.two = two ? 1 : 0;
     ca.al = ts.nlp.al;
     ca.be = ts.nlp.be;
+    ca.gpw = gpw;
+    ca.gdiv = gdiv;
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
     if (chi) {
         ca.g = chi->g;
         ca.cs = chi->cs;
         ca.k = 2.0 * chi->a / chi->S;
         ca.c2 = 2.0 * chi->cs * c->dV;
-        OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpChiCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
+        if (has_gga)
+            OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpChiCombineArgs, true>), dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
+        else
+            OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpChiCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
         OFDFT_REDUCE(c, st, c->d_partial, blocks, kHvpChiScalars, c->d_reduced);
         OFDFT_LAUNCH(c, st, "hvp_chi_shift", hvp_chi_shift_kernel, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, first, out, npts,
                      (const acc_t*)c->d_reduced, (real)c->dV, (real)(1.0 / chi->nel), ca.c2);
         if (chi->want) HIP_TRY(c, hipMemcpyAsync(c->h_partial, c->d_reduced, sizeof(double) * kHvpChiScalars, hipMemcpyDeviceToHost, st));
     } else {
-        OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca, c->d_partial);
+        if (has_gga)
+            OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpCombineArgs, true>), dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca,
+                         c->d_partial);
+        else
+            OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca, c->d_partial);
         if (quad_terms) {
             double sums[kHvpScalars];
-            if (int rc = fetch_partials(c, blocks, kHvpScalars, sums, st)) return rc;
+            if (int rc = fetch_partials(c, blocks, kHvpCombineScalars, sums, st)) return rc;
+            for (int s = 0; s < kHvpGgaScalars; ++s) sums[kHvpCombineScalars + s] = gga_sums[s];       // bits 10, 11: pbe_x, pbe_c
             for (int t = 0; t < OFDFT_NTERMS; ++t) quad_terms[t] = (t < kHvpScalars && ((mask >> t) & 1)) ? sums[t] * c->dV : 0.0;
         }
     }
@@ -173,10 +263,10 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
 }
 
 // the checks both entries share, after begin_call; `who` names the entry in the messages
-int hvp_checks(ofdft_ctx* c, const char* who) {
+int hvp_checks(ofdft_ctx* c, const char* who, HvpCaller caller) {
     if (!c->mask) return fail(c, OFDFT_ESTATE, "ofdft_set_terms has not been called");
     if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no second derivative", who);
-    if (const char* name = hvp_refusal(c)) return fail(c, OFDFT_EINVAL, "%s: no second derivative of the term %s", who, name);
+    if (const char* name = hvp_refusal(c, caller)) return fail(c, OFDFT_EINVAL, "%s: no second derivative of the term %s", who, name);
     if (wts_active(c))
         return fail(c, OFDFT_EINVAL, "%s: no second derivative of the stabilised Wang-Teter style functional (OFDFT_P_WTS_KIND = 1, wts_kind)", who);
     return 0;
@@ -192,7 +282,7 @@ int ofdft_hessian_vector(ofdft_ctx* c, const void* den_dev, const void* dir_dev,
     const bool retained = c->hvp_valid == kHvpDensity;
     if (int rc = begin_call(c, st)) return rc;         // (clears hvp_valid: a failed call leaves nothing to reuse)
     if (!den_dev || !dir_dev || !hv_dev) return fail(c, OFDFT_EINVAL, "null argument");
-    if (int rc = hvp_checks(c, "ofdft_hessian_vector")) return rc;
+    if (int rc = hvp_checks(c, "ofdft_hessian_vector", kHvpGga)) return rc;
     if (reuse_density && !retained)
         return fail(c, OFDFT_ESTATE, "ofdft_hessian_vector: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set");
     return hvp_core(c, (const real*)den_dev, (const real*)dir_dev, (real*)hv_dev, quad_terms, reuse_density != 0, nullptr, st);
@@ -209,7 +299,7 @@ int ofdft_hessian_vector_chi(ofdft_ctx* c, const void* chi_dev, const void* dir_
     if (int rc = begin_call(c, st)) return rc;
     if (!chi_dev || !dir_dev || !out_dev) return fail(c, OFDFT_EINVAL, "null argument");
     if (!(n_electrons > 0.0)) return fail(c, OFDFT_EINVAL, "ofdft_hessian_vector_chi: n_electrons must be positive");
-    if (int rc = hvp_checks(c, "ofdft_hessian_vector_chi")) return rc;
+    if (int rc = hvp_checks(c, "ofdft_hessian_vector_chi", kHvpGga)) return rc;
     if (reuse_density && !retained)
         return fail(c, OFDFT_ESTATE, "ofdft_hessian_vector_chi: reuse_density = 1 without a preceding call with reuse_density = 0 on this cell and term set");
     const real* phi = (const real*)chi_dev;
@@ -346,7 +436,7 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
     if (!chi_dev || !dirs_dev || !out_dev) return fail(c, OFDFT_EINVAL, "null argument");
     if (int rc = multi_checks(c, who, ncols, dir_stride, out_stride)) return rc;
     if (!(n_electrons > 0.0)) return fail(c, OFDFT_EINVAL, "%s: n_electrons must be positive", who);
-    if (int rc = hvp_checks(c, who)) return rc;
+    if (int rc = hvp_checks(c, who, kHvpNoGga)) return rc;
     const long long npts = c->npts;
     const real* phi = (const real*)chi_dev;
     const real* d = (const real*)dirs_dev;

@@ -57,7 +57,7 @@ int ofdft_potential_strain_gradient(ofdft_ctx* c, const void* den_dev, void* out
     OFDFT_ON_DEVICE(c, c->device);
     if (int rc = begin_call(c, st)) return rc;         // (clears hvp_valid)
     if (!den_dev || !out6_dev) return fail(c, OFDFT_EINVAL, "null argument");
-    if (int rc = hvp_checks(c, "ofdft_potential_strain_gradient")) return rc;
+    if (int rc = hvp_checks(c, "ofdft_potential_strain_gradient", kHvpNoGga)) return rc;
     const double* den = (const double*)den_dev;
     const unsigned mask = c->mask;
     const long long npts = c->npts;
@@ -156,7 +156,7 @@ int ofdft_strain_hessian(ofdft_ctx* c, const void* den_dev, double* w2, void* st
     OFDFT_ON_DEVICE(c, c->device);
     if (int rc = begin_call(c, st)) return rc;         // (clears hvp_valid)
     if (!den_dev || !w2) return fail(c, OFDFT_EINVAL, "null argument");
-    if (int rc = hvp_checks(c, "ofdft_strain_hessian")) return rc;
+    if (int rc = hvp_checks(c, "ofdft_strain_hessian", kHvpNoGga)) return rc;
     const double* den = (const double*)den_dev;
     const unsigned mask = c->mask;
     const double invN = 1.0 / (double)c->npts, invN2 = invN * invN;

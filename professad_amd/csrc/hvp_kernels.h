@@ -9,7 +9,10 @@
 namespace ofdft {
 
 constexpr int kHvpMaxSpectra = 7;      // w | sqrt n, d sqrt n | n^beta, n^(beta-1) w | n^alpha, n^(alpha-1) w
-constexpr int kHvpScalars = 10;        // per-term sums of w hv_t, indexed by the term's bit position (ion_electron .. chachiyo_c)
+constexpr int kHvpScalars = 12;        // per-term sums of w hv_t, indexed by the term's bit position (ion_electron .. pbe_c)
+constexpr int kHvpCombineScalars = 10; // ... of which the combine kernel reduces ion_electron .. chachiyo_c; pbe_x, pbe_c: the GGA mid kernel
+constexpr int kHvpGgaScalars = 2;
+static_assert(kHvpCombineScalars + kHvpGgaScalars == kHvpScalars, "bits 10 and 11 follow the combine kernel's sums");
 enum { HVP_VW = 1, HVP_WT = 2, HVP_WT2 = 4, HVP_REUSE = 8 };
 
 // ---- head: n, w -> the real fields of the active terms (with HVP_REUSE only those that depend on w)
@@ -50,6 +53,7 @@ struct HvpChiHeadArgs : HvpHeadArgs {
     static constexpr bool kChi = true;
     real cs, k;
     real* dn;                    // nullptr: no transform takes dn itself
+    real* nout;                  // nullptr: no transform takes n itself (the GGA gradient does; not written with HVP_REUSE)
 };
 __device__ __forceinline__ void hvp_chi_density(real cs, real k, real phi, real d, real& n, real& dn) {
     n = cs * phi * phi;
@@ -67,6 +71,7 @@ static __global__ void hvp_head_kernel(Args a) {
             hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
             hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
             if (a.dn) ST2(a.dn, w.x, w.y);
+            if (a.nout && dens) ST2(a.nout, n.x, n.y);
         }
         const HvpHeadPoint p0 = hvp_head_point(a, n.x, w.x), p1 = hvp_head_point(a, n.y, w.y);
         if (vw) {
@@ -89,6 +94,7 @@ static __global__ void hvp_head_kernel(Args a) {
         if constexpr (Args::kChi) {
             hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
             if (a.dn) a.dn[i] = w;
+            if (a.nout && dens) a.nout[i] = n;
         }
         const HvpHeadPoint p = hvp_head_point(a, n, w);
         if (vw) {
@@ -187,11 +193,12 @@ struct HvpCombineArgs {
     unsigned mask;
     int two;
     real al, be;
+    const real* gpw;  const real* gdiv;   // GGA (kGga instantiations): the mid kernel's pointwise part, div flux
 };
 struct HvpPoint { real n, w, vh, lap, dlap, A, Cb, B, Ca; };
-__device__ __forceinline__ real hvp_combine_point(const HvpCombineArgs& a, const HvpPoint& p, acc_t (&acc)[kHvpScalars]) {
+__device__ __forceinline__ real hvp_combine_point(const HvpCombineArgs& a, const HvpPoint& p, acc_t (&acc)[kHvpCombineScalars], real hv0 = 0.0) {
     const real n = p.n, w = p.w;
-    real hv = 0.0;
+    real hv = hv0;                               // PBE: f_nn w + f_nsigma dsigma - 2 div flux (their w hv_t come from the mid kernel)
     if (a.mask & OFDFT_HARTREE) {
         acc[1] += w * p.vh;
         hv += p.vh;
@@ -263,11 +270,11 @@ __device__ __forceinline__ real hvp_chi_point(const HvpChiCombineArgs& a, real p
     return P;
 }
 // (every array pointer is valid: the host points the fields of absent terms at `n`, as for combine_kernel)
-template <class Args>
+template <class Args, bool kGga = false>
 static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a, acc_t* __restrict__ partial) {
-    acc_t acc[kHvpScalars];
+    acc_t acc[kHvpCombineScalars];
 #pragma unroll
-    for (int s = 0; s < kHvpScalars; ++s) acc[s] = 0.0;
+    for (int s = 0; s < kHvpCombineScalars; ++s) acc[s] = 0.0;
     acc_t cacc[kHvpChiScalars] = {0.0, 0.0, 0.0, 0.0};
     (void)cacc;
     const long long n2 = a.npts >> 1;
@@ -275,35 +282,109 @@ static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a,
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
         cplx n = LD2(a.n), w = LD2(a.w);
         const cplx vh = LD2(a.vh), lp = LD2(a.lap), dl = LD2(a.dlap), A = LD2(a.A), Cb = LD2(a.Cb), B = LD2(a.B), Ca = LD2(a.Ca);
+        cplx g0 = mkc(0.0, 0.0);
+        if constexpr (kGga) {
+            const cplx pw = LD2(a.gpw), dv = LD2(a.gdiv);
+            g0 = mkc(pw.x - 2.0 * dv.x, pw.y - 2.0 * dv.y);
+        }
         if constexpr (Args::kChi) {
             const cplx phi = n, d = w, g = a.g ? LD2(a.g) : mkc(0.0, 0.0);
             hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
             hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
-            const real v0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc);
-            const real v1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc);
+            const real v0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc, g0.x);
+            const real v1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc, g0.y);
             const real h0 = hvp_chi_point(a, phi.x, d.x, g.x, n.x, v0, cacc);
             const real h1 = hvp_chi_point(a, phi.y, d.y, g.y, n.y, v1, cacc);
             reinterpret_cast<cplx*>(a.hv)[i] = mkc(h0, h1);
         } else {
-            const real h0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc);
-            const real h1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc);
+            const real h0 = hvp_combine_point(a, HvpPoint{n.x, w.x, vh.x, lp.x, dl.x, A.x, Cb.x, B.x, Ca.x}, acc, g0.x);
+            const real h1 = hvp_combine_point(a, HvpPoint{n.y, w.y, vh.y, lp.y, dl.y, A.y, Cb.y, B.y, Ca.y}, acc, g0.y);
             reinterpret_cast<cplx*>(a.hv)[i] = mkc(h0, h1);
         }
     }
 #undef LD2
     if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const long long i = a.npts - 1;
+        real g0 = 0.0;
+        if constexpr (kGga) g0 = a.gpw[i] - 2.0 * a.gdiv[i];
         if constexpr (Args::kChi) {
             real n, w;
             hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
-            const real dv = hvp_combine_point(a, HvpPoint{n, w, a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc);
+            const real dv = hvp_combine_point(a, HvpPoint{n, w, a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc, g0);
             a.hv[i] = hvp_chi_point(a, a.n[i], a.w[i], a.g ? a.g[i] : (real)0.0, n, dv, cacc);
         } else {
-            a.hv[i] = hvp_combine_point(a, HvpPoint{a.n[i], a.w[i], a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc);
+            a.hv[i] = hvp_combine_point(a, HvpPoint{a.n[i], a.w[i], a.vh[i], a.lap[i], a.dlap[i], a.A[i], a.Cb[i], a.B[i], a.Ca[i]}, acc, g0);
         }
     }
     if constexpr (Args::kChi) block_reduce_store<kHvpChiScalars>(cacc, partial);      // (the per-term sums are not kept: dead code here)
-    else block_reduce_store<kHvpScalars>(acc, partial);
+    else block_reduce_store<kHvpCombineScalars>(acc, partial);
+}
+
+// ---- GGA mid stage (PBE exchange / correlation): between the two transform stages of a product with pbe_x or pbe_c.
+// With sigma = |grad n|^2, dsigma = 2 grad n . grad w and the second partials of f(n, sigma) summed over the terms set,
+//   c = f_sn w + f_ss dsigma,     flux = c grad n + f_s grad w   (over grad w, in place),     pw = f_nn w + f_ns dsigma,
+// and per term  q_t = sum f_nn w^2 + 2 f_ns w dsigma + f_ss dsigma^2 + 2 f_s |grad w|^2  (= sum w hv_t by D_a^T = -D_a; slots 0: x, 1: c).
+// The chi-space instantiation forms n and w = dn from (phi, d) on the fly, as head and combine do, and reduces nothing.
+struct HvpGgaMidArgs {
+    static constexpr bool kChi = false;
+    const real* n;
+    const real* w;
+    const real* gn[3];          // grad n ("hv:gn0..2": density-only, retained)
+    real* gw[3];                // grad w in, flux out
+    real* pw;
+    long long npts;
+    int x, c;                   // pbe_x, pbe_c set
+};
+struct HvpChiGgaMidArgs : HvpGgaMidArgs {
+    static constexpr bool kChi = true;
+    real cs, k;
+};
+struct HvpGgaPoint { real pw, f0, f1, f2; };
+__device__ __forceinline__ HvpGgaPoint hvp_gga_point(const HvpGgaMidArgs& a, real n, real w, real a0, real a1, real a2, real b0, real b1, real b2,
+                                                     acc_t (&acc)[kHvpGgaScalars]) {
+    const real sigma = a0 * a0 + a1 * a1 + a2 * a2, ds = 2.0 * (a0 * b0 + a1 * b1 + a2 * b2), gw2 = b0 * b0 + b1 * b1 + b2 * b2;
+    PbeSecond x, c;
+    pbe_second(n, sigma, a.x != 0, a.c != 0, x, c);
+    acc[0] += x.fnn * w * w + 2.0 * x.fns * w * ds + x.fss * ds * ds + 2.0 * x.fs * gw2;
+    acc[1] += c.fnn * w * w + 2.0 * c.fns * w * ds + c.fss * ds * ds + 2.0 * c.fs * gw2;
+    const real fs = x.fs + c.fs, fnn = x.fnn + c.fnn, fns = x.fns + c.fns, fss = x.fss + c.fss;
+    const real cc = fns * w + fss * ds;
+    return HvpGgaPoint{fnn * w + fns * ds, cc * a0 + fs * b0, cc * a1 + fs * b1, cc * a2 + fs * b2};
+}
+template <class Args>
+static __global__ __launch_bounds__(kRedThreads) void hvp_gga_mid_kernel(Args a, acc_t* __restrict__ partial) {
+    acc_t acc[kHvpGgaScalars] = {0.0, 0.0};
+    const long long n2 = a.npts >> 1;
+#define LD2(ptr) reinterpret_cast<const cplx*>(ptr)[i]
+#define ST2(ptr, u, v) reinterpret_cast<cplx*>(ptr)[i] = mkc(u, v)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        cplx n = LD2(a.n), w = LD2(a.w);
+        const cplx a0 = LD2(a.gn[0]), a1 = LD2(a.gn[1]), a2 = LD2(a.gn[2]), b0 = LD2(a.gw[0]), b1 = LD2(a.gw[1]), b2 = LD2(a.gw[2]);
+        if constexpr (Args::kChi) {
+            const cplx phi = n, d = w;
+            hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
+            hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
+        }
+        const HvpGgaPoint p0 = hvp_gga_point(a, n.x, w.x, a0.x, a1.x, a2.x, b0.x, b1.x, b2.x, acc);
+        const HvpGgaPoint p1 = hvp_gga_point(a, n.y, w.y, a0.y, a1.y, a2.y, b0.y, b1.y, b2.y, acc);
+        ST2(a.pw, p0.pw, p1.pw);
+        ST2(a.gw[0], p0.f0, p1.f0);
+        ST2(a.gw[1], p0.f1, p1.f1);
+        ST2(a.gw[2], p0.f2, p1.f2);
+    }
+#undef LD2
+#undef ST2
+    if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long i = a.npts - 1;
+        real n = a.n[i], w = a.w[i];
+        if constexpr (Args::kChi) hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
+        const HvpGgaPoint p = hvp_gga_point(a, n, w, a.gn[0][i], a.gn[1][i], a.gn[2][i], a.gw[0][i], a.gw[1][i], a.gw[2][i], acc);
+        a.pw[i] = p.pw;
+        a.gw[0][i] = p.f0;
+        a.gw[1][i] = p.f1;
+        a.gw[2][i] = p.f2;
+    }
+    if constexpr (!Args::kChi) block_reduce_store<kHvpGgaScalars>(acc, partial);
 }
 
 // ---- chi space, before the head: phi.d and phi.phi (fixed order, as every reduction here)

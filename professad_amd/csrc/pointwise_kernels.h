@@ -991,6 +991,88 @@ __device__ __forceinline__ PbePoint pbe_point(real n, real gn2, const GgaSel& se
     return r;
 }
 
+// ---- second partials of the PBE energy densities f(n, sigma), sigma = |grad n|^2 (the Hessian-vector product's mid stage,
+// hvp_kernels.h): the x and c bodies of pbe_point restated over second-order jets -- J1 for what depends on n alone (value, d/dn,
+// d2/dn2), J2 for the rest (value, two first, three second partials) -- from the same roots, the same lean rcp / log / exp, the
+// same constants and the same two 1e-30 guards (constants of the differentiation).  fp64 library only, like the product itself.
+#ifndef OFDFT_REAL_F32
+struct J1 { real v, d, dd; };
+struct J2 { real v, n, s, nn, ns, ss; };
+__device__ __forceinline__ J1 operator+(const J1& a, const J1& b) { return {a.v + b.v, a.d + b.d, a.dd + b.dd}; }
+__device__ __forceinline__ J1 operator+(const J1& a, real c) { return {a.v + c, a.d, a.dd}; }
+__device__ __forceinline__ J1 operator*(const J1& a, real c) { return {a.v * c, a.d * c, a.dd * c}; }
+__device__ __forceinline__ J1 operator*(const J1& a, const J1& b) {
+    return {a.v * b.v, a.d * b.v + a.v * b.d, a.dd * b.v + 2.0 * a.d * b.d + a.v * b.dd};
+}
+// g(a) from g, g', g'' at a.v
+__device__ __forceinline__ J1 jchain(const J1& a, real g0, real g1, real g2) { return {g0, g1 * a.d, g2 * a.d * a.d + g1 * a.dd}; }
+__device__ __forceinline__ J2 operator+(const J2& a, const J2& b) { return {a.v + b.v, a.n + b.n, a.s + b.s, a.nn + b.nn, a.ns + b.ns, a.ss + b.ss}; }
+__device__ __forceinline__ J2 operator+(const J2& a, real c) { return {a.v + c, a.n, a.s, a.nn, a.ns, a.ss}; }
+__device__ __forceinline__ J2 operator*(const J2& a, real c) { return {a.v * c, a.n * c, a.s * c, a.nn * c, a.ns * c, a.ss * c}; }
+__device__ __forceinline__ J2 operator*(const J2& a, const J2& b) {
+    return {a.v * b.v,
+            a.n * b.v + a.v * b.n,
+            a.s * b.v + a.v * b.s,
+            a.nn * b.v + 2.0 * a.n * b.n + a.v * b.nn,
+            a.ns * b.v + a.n * b.s + a.s * b.n + a.v * b.ns,
+            a.ss * b.v + 2.0 * a.s * b.s + a.v * b.ss};
+}
+__device__ __forceinline__ J2 operator*(const J2& a, const J1& b) {
+    return {a.v * b.v, a.n * b.v + a.v * b.d, a.s * b.v, a.nn * b.v + 2.0 * a.n * b.d + a.v * b.dd, a.ns * b.v + a.s * b.d, a.ss * b.v};
+}
+__device__ __forceinline__ J2 jchain(const J2& a, real g0, real g1, real g2) {
+    return {g0, g1 * a.n, g1 * a.s, g2 * a.n * a.n + g1 * a.nn, g2 * a.n * a.s + g1 * a.ns, g2 * a.s * a.s + g1 * a.ss};
+}
+template <class J> __device__ __forceinline__ J jrcp(const J& a) {
+    const real r = fm::rcp(a.v), r2 = r * r;
+    return jchain(a, r, -r2, 2.0 * r2 * r);
+}
+template <class J> __device__ __forceinline__ J jlog(const J& a) {
+    const real r = fm::rcp(a.v);
+    return jchain(a, fm::log(a.v), r, -r * r);
+}
+template <class J> __device__ __forceinline__ J jexp(const J& a) {
+    const real e = fm::exp(a.v);
+    return jchain(a, e, e, e);
+}
+// p = n^e as a jet, from its value and 1 / n
+__device__ __forceinline__ J1 jpow_n(real p, real e, real inv_n) { return {p, e * p * inv_n, e * (e - 1.0) * p * inv_n * inv_n}; }
+
+struct PbeSecond { real fs, fnn, fns, fss; };      // df/dsigma, d2f/dn2, d2f/dn dsigma, d2f/dsigma2
+// -> the four partials per term (a term switched off returns zeros); n > 0
+__device__ __forceinline__ void pbe_second(real n, real sigma, bool do_x, bool do_c, PbeSecond& x, PbeSecond& c) {
+    x = PbeSecond{0.0, 0.0, 0.0, 0.0};
+    c = PbeSecond{0.0, 0.0, 0.0, 0.0};
+    const fm::Roots<real> q = fm::roots(n);
+    const real inv_n = q.inv_n;
+    const J2 sg{sigma, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (do_x) {                       // f = kCx n^(4/3) Fx(s2), s2 = kCs2 sigma n^(-8/3)
+        const real kappa = 0.804, mu = 0.066725 * kPiR * kPiR / 3.0;
+        const J2 s2 = sg * jpow_n(kCs2 * inv_n * inv_n * q.inv13 * q.inv13, -(8.0 / 3.0), inv_n);
+        const J2 Fx = jrcp(s2 * (mu / kappa) + 1.0) * (-kappa) + (1.0 + kappa);
+        const J2 f = Fx * jpow_n(kCx * q.n13 * n, 4.0 / 3.0, inv_n);
+        x = PbeSecond{f.s, f.nn, f.ns, f.ss};
+    }
+    if (do_c) {                       // f = (eps_c(rs) + H(rs, t2)) n
+        const real A1 = 0.0310907, a1 = 0.2137, b1 = 7.5957, b2 = 3.5876, b3 = 1.6382, b4 = 0.49294;
+        const real beta = 0.066725, gam = kPbeGamma, igam = kPbeInvGamma;
+        const J1 sr = jpow_n(kSqrtCrs * q.y, -(1.0 / 6.0), inv_n);       // sqrt(rs)
+        const J1 rs = sr * sr;
+        const J1 zeta = (sr * ((sr * ((sr * ((sr * b4) + b3)) + b2)) + b1)) * (2.0 * A1);
+        const J1 lg = jlog(jrcp(zeta) + 1.0);
+        const J1 eps = ((rs * a1) + 1.0) * lg * (-2.0 * A1);
+        const J1 A = jrcp((jexp(eps * (-igam)) + (-1.0)) + 1e-30) * (beta * igam);
+        const real ct = (1.0 / 16.0) * kCbrtPiOver3;
+        const J2 t2 = sg * jpow_n(ct * fmin(inv_n * inv_n * q.inv13, (real)1e30), -(7.0 / 3.0), inv_n);
+        const J2 At2 = t2 * A;
+        const J2 frac = (At2 + 1.0) * jrcp(At2 * At2 + At2 + 1.0);
+        const J2 H = jlog(t2 * frac * (beta * igam) + 1.0) * gam;
+        const J2 f = (H + J2{eps.v, eps.d, 0.0, eps.dd, 0.0, 0.0}) * J1{n, 1.0, 0.0};
+        c = PbeSecond{f.s, f.nn, f.ns, f.ss};
+    }
+}
+#endif
+
 // Pauli-Gaussian with the Laplacian-dependent terms (functionals.py:336-403; tools_for_tests.py:86-118):
 //   f = tau_TF (exp(-mu s^2) + beta q^2 - lambda q s^2 + sigma s^4),  q = lap n / (4 (3 pi^2)^(2/3) n^(5/3))
 // adds f, df/dn, df/d|grad n|^2 to p and returns df/d(lap n)

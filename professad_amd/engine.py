@@ -50,6 +50,7 @@ class Engine:
         self._terms_key = None
         self._terms_memo = {}
         self._nlk_table_key = None
+        self._options = {}           # option number -> the value last given to set_option (Engine.option)
         self.npts = int(np.prod(self.shape))
         self._dev_index = idx
         self._dev_exact = torch.device('cuda', idx)
@@ -312,7 +313,7 @@ class Engine:
         call of either entry made without it on the same chi.  Single GPU and fp64, the terms of ``hessian_vector``."""
         self._multi_refusal('hessian_vector_chi_multi', 'the Hessian-vector product')
         from . import optimize
-        why = optimize.second_order_refusal(self)
+        why = optimize.second_order_refusal(self, gga_missing='batch')
         if why:
             raise NotImplementedError('Engine.hessian_vector_chi_multi: ' + why)
         B = self._grid_stack(dirs, 'dirs')
@@ -378,7 +379,13 @@ class Engine:
 
     def set_option(self, option, value):
         self._check(self.lib.ofdft_set_option(self._ctx, int(option), float(value)), 'ofdft_set_option')
+        self._options[int(option)] = float(value)
         return self
+
+    def option(self, option):
+        """the value last given to ``set_option`` for this option on this engine, or None if it was never set (the library's default holds)"""
+        return self._options.get(int(option))
+
 
     def stress(self, den):
         """per-term stress tensors {term name: 3x3 numpy array, Ha/bohr^3} for the active terms at fixed electron number
@@ -407,6 +414,10 @@ class Engine:
         nothing here (ions.ionic_potential_strain_gradient).  Single GPU and fp64, the terms of ``hessian_vector``."""
         if self.dtype != torch.double:
             raise NotImplementedError('Engine.potential_strain_gradient is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+        from . import optimize
+        why = optimize.gga_strain_refusal(self)
+        if why:
+            raise NotImplementedError('Engine.potential_strain_gradient: ' + why)
         den = self._grid_tensor(den, 'den')
         out = torch.empty((6,) + tuple(den.shape), dtype=den.dtype, device=den.device)
         self._check(self.lib.ofdft_potential_strain_gradient(self._ctx, _ptr(den), _ptr(out), self._stream()),
@@ -422,6 +433,10 @@ class Engine:
         their sum is meaningful.  The ion_electron entry is zero (ions.ion_electron_strain_hessian).  Single GPU and fp64."""
         if self.dtype != torch.double:
             raise NotImplementedError('Engine.strain_hessian is fp64 work (libofdft_hip.so); an fp32 engine does not serve it')
+        from . import optimize
+        why = optimize.gga_strain_refusal(self)
+        if why:
+            raise NotImplementedError('Engine.strain_hessian: ' + why)
         den = self._grid_tensor(den, 'den')
         buf = (C.c_double * (N.NTERMS * 81))()
         self._check(self.lib.ofdft_strain_hessian(self._ctx, _ptr(den), buf, self._stream()), 'ofdft_strain_hessian')

@@ -39,6 +39,12 @@ def refusal(engine, pme_order=None):
     return optimize.response_refusal(engine, pme_order)
 
 
+def batch_refusal(engine):
+    """None, or why `force_constants(batch=k)` cannot run where `batch=None` can: with the engine's OPT_HVP_GGA at 1 pbe_x / pbe_c pass
+    the single-column solves, and the batched ones keep refusing them by name"""
+    return optimize.second_order_refusal(engine, gga_missing='batch')
+
+
 def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, Rc=None, rtol=1e-10, maxiter=500, units='Ha/b2',
                     impose_asr=False, backend=None, pme_order=None, precondition=None, batch=None):
     """Phi[p, b, i, j] = -dF[p, i] / dR[b, j] for p in `primitive_ion_indices` (default: every ion) and all ions b.
@@ -74,7 +80,7 @@ def force_constants(engine, box_vecs, species, chi, primitive_ion_indices=None, 
     optimize.check_precondition(precondition)
     batch = optimize.resolve_batch('force_constants', backend, batch)
     if backend is None:
-        why = refusal(engine, pme_order)
+        why = refusal(engine, pme_order) or (batch_refusal(engine) if batch is not None else None)
         if why:
             raise NotImplementedError('force_constants: ' + why)
     b = backend if backend is not None else HipFcBackend(engine, box_vecs, species)

@@ -432,18 +432,50 @@ class TwoPointGradientDescent:
 # ------------------------------------------------------------------------------------------------ second order
 CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_CURVATURE = 0, 1, 2, 3      # exit reasons of a solve (OFDFT_CG_*; _native.CG_REASONS)
 _UNSERVED = ('wgc99_nl', 'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk')    # terms without a second derivative (ofdft_hessian_vector)
+_GGA_OPT_IN = ('pbe_x', 'pbe_c')           # ... served by the single-column products once the engine's OPT_HVP_GGA is 1
+_GGA_MISSING = {
+    'batch': 'batching is what is missing -- the multi-column product has no PBE stage; use the single-column path (batch=None, '
+             'density_response, Engine.hessian_vector_chi)',
+    'strain': 'the strain derivative of PBE is not built (elastic constants, bulk modulus, Engine.strain_hessian, '
+              'Engine.potential_strain_gradient)',
+}
 
 
-def second_order_refusal(engine):
-    """None, or why the engine cannot serve Hessian-vector products in chi (what ofdft_hessian_vector_chi itself refuses)"""
+def hvp_gga_enabled(engine):
+    """the engine's OPT_HVP_GGA is 1 (an engine without `Engine.option`, such as a test's fake, counts as off)"""
+    from . import _native as N
+    option = getattr(engine, 'option', None)
+    return option is not None and option(N.OPT_HVP_GGA) == 1
+
+
+def gga_strain_refusal(engine):
+    """None, or -- with the engine's OPT_HVP_GGA at 1 and pbe_x / pbe_c among its terms -- why its strain entries do not serve them:
+    the products then let these terms through, the strain entries say so before any device work"""
+    from . import _native as N
+    if hvp_gga_enabled(engine) and engine._terms_key is not None:
+        for name in _GGA_OPT_IN:
+            if engine._mask() & N.TERM_BITS[name]:
+                return 'no second derivative of the term %s here: %s' % (name, _GGA_MISSING['strain'])
+    return None
+
+
+def second_order_refusal(engine, gga_missing=None):
+    """None, or why the engine cannot serve Hessian-vector products in chi (what ofdft_hessian_vector_chi itself refuses).
+    pbe_x / pbe_c pass when the engine's OPT_HVP_GGA is 1 -- unless `gga_missing` names what the asking path lacks for them
+    ('batch': the multi-column entries, 'strain': the elastic entries), which keep refusing them by name."""
     from . import _native as N
     if getattr(engine, 'comm', None) is not None:
         return 'the Hessian-vector product is served by single-GPU contexts; a slab-decomposed DistEngine has no second derivative'
     if engine.dtype != torch.double:
         return 'the Hessian-vector product is fp64 work (libofdft_hip.so); an fp32 engine does not serve it'
     mask = engine._mask()
+    gga_on = hvp_gga_enabled(engine)
     for name in _UNSERVED:
         if mask & N.TERM_BITS[name]:
+            if name in _GGA_OPT_IN and gga_on:
+                if gga_missing is None:
+                    continue
+                return 'no second derivative of the term %s here: %s' % (name, _GGA_MISSING[gga_missing])
             return 'no second derivative of the term %s' % name
     if mask & N.TERM_BITS['wt_nl'] and np.frombuffer(engine._terms_key[1], dtype=np.float64)[12] != 0.0:
         return 'no second derivative of the stabilised Wang-Teter style functional (wts_kind)'
@@ -687,7 +719,7 @@ class HipCgMultiBackend:
     coefficients, exit reason and iteration count; a column that has ended is frozen while the others go on."""
 
     def __init__(self, engine, ncols, precondition=None):
-        why = second_order_refusal(engine)
+        why = second_order_refusal(engine, gga_missing='batch')
         if why:
             raise NotImplementedError(why)
         if check_batch(ncols) is None:
@@ -871,13 +903,14 @@ def normalise_species(species):
     return species, frac, charges
 
 
-def response_refusal(engine, pme_order=None):
-    """None, or why a driver over `density_response` with ions cannot run on this engine (raised before any device work)"""
+def response_refusal(engine, pme_order=None, gga_missing=None):
+    """None, or why a driver over `density_response` with ions cannot run on this engine (raised before any device work);
+    `gga_missing` as `second_order_refusal` takes it"""
     from . import _native as N
     if pme_order:
         return ('particle-mesh Ewald (PME, pme_order=%r) is not served: the derivative of the B-spline spread is not built; '
                 'use the exact structure factor' % (pme_order,))
-    why = second_order_refusal(engine)
+    why = second_order_refusal(engine, gga_missing)
     if why:
         return why
     if not engine._mask() & N.TERM_BITS['ion_electron']:
