@@ -295,7 +295,8 @@ int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double
  * Served: ion_electron (hv = 0, no vext needed), hartree, tf, vw, wt_nl (any alpha, beta), lda_x, pz_c, pw_c, chachiyo_c.  In wt_nl the
  * n0 of the kernel is mean(den) vol of the den passed in and a CONSTANT of the differentiation (functionals.py:646-647 take it with
  * .item()), so a finite difference of the potential along a w of non-zero mean differs.  Refused with OFDFT_EINVAL, the message
- * naming the term: wgc99_nl, pbe_x, pbe_c (these two unless OFDFT_OPT_HVP_GGA = 1, below), gga_k, vwgtf, nlk, OFDFT_P_WTS_KIND = 1;
+ * naming the term: wgc99_nl (unless OFDFT_OPT_HVP_WGC = 1, below), pbe_x, pbe_c (unless OFDFT_OPT_HVP_GGA = 1, below), gga_k, vwgtf, nlk,
+ * OFDFT_P_WTS_KIND = 1;
  * slab-decomposed contexts; the fp32 library.
  * reuse_density: 0 computes everything and leaves the density-only fields (lap sqrt n, K * n^beta, K * n^alpha) in workspaces of their
  * own; 1 = the caller asserts den holds the values of the previous call made with 0 and those transforms are skipped (Hartree 1 + 1
@@ -309,7 +310,14 @@ int  ofdft_ion_electron_stress(ofdft_ctx* ctx, const void* den_dev, const double
  * in two transform stages around a pointwise mid kernel: 2 + 6 + 3 + 1 = 12 transforms more, 8 with reuse_density = 1 (grad n joins
  * the retained fields; the second partials are formed again on every call).  quad_terms_host reports pbe_x and pbe_c from
  * sum f_nn w^2 + 2 f_nsigma w dsigma + f_sigma,sigma dsigma^2 + 2 f_sigma |grad w|^2.  Limits: den > 0 everywhere, as for
- * evaluating PBE itself; single GPU; fp64. */
+ * evaluating PBE itself; single GPU; fp64.
+ * With OFDFT_OPT_HVP_WGC = 1 the two entries also serve wgc99_nl.  n_ref = kappa round(N) / vol is a CONSTANT of the
+ * differentiation (functionals.py:952-954 take round(N) with .item(); N = mean(den) vol of the den passed in, n_electrons in chi
+ * space), so with theta = n - n_ref, a = (A, A theta, A theta^2 / 2), A = n^beta, p likewise with n^alpha, and the symmetric block M of
+ * the evaluation's kernel tables, E = c dV sum p . (M a), U = M a, G = M p and
+ *     hv = c sum_i [ p_i'' w U_i + p_i' (M (a' w))_i + a_i'' w G_i + a_i' (M (p' w))_i ]
+ * from a head kernel, four triples of transforms around the evaluation's spectral mix and a tail kernel: 6 + 6 + 6 + 6 = 24 transforms
+ * more, 12 with reuse_density = 1 (U and G join the retained fields).  quad_terms_host reports wgc99_nl from sum w hv of that field. */
 int  ofdft_hessian_vector(ofdft_ctx* ctx, const void* den_dev, const void* dir_dev, void* hv_dev,
                           double* quad_terms_host /* [OFDFT_NTERMS] or NULL */, int reuse_density, void* stream);
 
@@ -630,6 +638,10 @@ int  ofdft_cgm_solution(ofdft_cgm* h, void* x_out_dev, long long stride, void* s
 #define OFDFT_OPT_HVP_GGA 18      /* 0 (default): the second-derivative entries refuse pbe_x and pbe_c by name; 1: ofdft_hessian_vector and
                                      ofdft_hessian_vector_chi serve them (second transform stage, see there).  ofdft_hessian_vector_chi_multi,
                                      ofdft_potential_strain_gradient and ofdft_strain_hessian refuse them under either value.  Any other value:
+                                     OFDFT_EINVAL.  Both libraries accept it; it matters in the fp64 one */
+#define OFDFT_OPT_HVP_WGC 19      /* 0 (default): the second-derivative entries refuse wgc99_nl by name; 1: ofdft_hessian_vector and
+                                     ofdft_hessian_vector_chi serve it (a stage of its own, see there).  ofdft_hessian_vector_chi_multi,
+                                     ofdft_potential_strain_gradient and ofdft_strain_hessian refuse it under either value.  Any other value:
                                      OFDFT_EINVAL.  Both libraries accept it; it matters in the fp64 one */
 #define OFDFT_OPT_XWAVE 8         /* fused x passes: 1 (default) = the cross-wave kernel (whole runs of memory-adjacent lines per access, the
                                      radix-4 / -8 step of the line transform across the waves of a workgroup) for 256- and 512-point lines

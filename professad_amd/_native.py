@@ -61,6 +61,7 @@ OPT_BS_FUSED = 15
 OPT_POT_SPECTRUM = 16
 OPT_AXIS_PASSES = 17
 OPT_HVP_GGA = 18
+OPT_HVP_WGC = 19
 OPT_WGC_FOLD = 28
 
 # scalars of ofdft_hessian_vector_chi (OFDFT_HVC_*) and exit reasons of the conjugate-gradient solver (OFDFT_CG_*)

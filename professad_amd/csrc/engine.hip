@@ -1778,6 +1778,10 @@ int ofdft_set_option(ofdft_ctx* c, int option, double value) {
             if (value != 0.0 && value != 1.0) return fail(c, OFDFT_EINVAL, "OFDFT_OPT_HVP_GGA takes 0 or 1");
             c->hvp_gga = (int)value;
             return OFDFT_OK;
+        case OFDFT_OPT_HVP_WGC:
+            if (value != 0.0 && value != 1.0) return fail(c, OFDFT_EINVAL, "OFDFT_OPT_HVP_WGC takes 0 or 1");
+            c->hvp_wgc = (int)value;
+            return OFDFT_OK;
         case OFDFT_OPT_TEST_FAULT:
             c->test_fault = (int)value;
             if (c->test_fault == 2) c->res_fits = 0;

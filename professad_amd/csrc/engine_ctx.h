@@ -166,6 +166,7 @@ struct ofdft_ctx {
     // (0: nothing retained; 1: by ofdft_hessian_vector; 2: by ofdft_hessian_vector_chi, whose fields belong to n[phi] -- engine_hvp.inc.h)
     unsigned char hvp_valid = false;
     int hvp_gga = 0;             // OFDFT_OPT_HVP_GGA: 1 = ofdft_hessian_vector and ofdft_hessian_vector_chi serve pbe_x / pbe_c (fp64 library)
+    int hvp_wgc = 0;             // OFDFT_OPT_HVP_WGC: 1 = ... serve wgc99_nl (fp64 library)
     double hvp_chi_S = 0.0;            // sum phi^2 of the chi-space call that retained them
     double hvp_nel = 0.0;              // mean(den) vol of that call: the n0 of the Wang-Teter kernel (functionals.py:646-647)
     char err[512] = "";

@@ -10,6 +10,10 @@
 //   forward n, w | spec_grad | inverse -> grad n ("hv:gn0..2", density-only: retained too), grad w
 //   mid      n, w, grad n, grad w -> f_nn w + f_ns dsigma ("hv:gpw"), the flux over grad w, the sums of pbe_x and pbe_c
 //   forward flux | spec_div | inverse -> "hv:gdiv";   the combine kernel then starts hv from gpw - 2 gdiv
+// With wgc99_nl in the term set (OFDFT_OPT_HVP_WGC = 1) a stage of its own runs behind that one:
+//   wgc head  n, w -> a, p (density-only) and a' w, p' w, three fields each
+//   per triple: forward | spec_wgc_mix | inverse, in place -> U = M a, G = M p ("hv:wU0..2", "hv:wG0..2": retained), M (a' w), M (p' w)
+//   wgc tail  -> its hv, the sum of wgc99_nl; the combine kernel starts hv from that field (added to "hv:gpw" where PBE runs too)
 //
 // hvp_core schedules this once for both entries.  ofdft_hessian_vector hands it (n, w); ofdft_hessian_vector_chi hands it
 // (phi, d) with HvpChi set: head and combine then run their chi-space instantiations, which form n and dn on the fly, and the
@@ -29,14 +33,17 @@ struct HvpChi {                  // chi-space call: nullptr for the n-space prod
     bool want;
 };
 
-// which entry asks: the two single-column products serve pbe_x / pbe_c under OFDFT_OPT_HVP_GGA = 1 (the second stage of hvp_core); the
-// multi-column product and the strain entries have no PBE kernels and keep refusing them whatever the option says
+// which entry asks: the two single-column products serve pbe_x / pbe_c under OFDFT_OPT_HVP_GGA = 1 and wgc99_nl under OFDFT_OPT_HVP_WGC = 1
+// (the stages of hvp_core); the multi-column product and the strain entries have no kernels for them and keep refusing them whatever
+// the options say
 enum HvpCaller { kHvpNoGga = 0, kHvpGga = 1 };
 
 const char* hvp_refusal(ofdft_ctx* c, HvpCaller caller) {
     static const struct { unsigned bit; const char* name; } refused[] = {
         {OFDFT_WGC99_NL, "wgc99_nl"}, {OFDFT_PBE_X, "pbe_x"}, {OFDFT_PBE_C, "pbe_c"}, {OFDFT_GGA_K, "gga_k"}, {OFDFT_VWGTF, "vwgtf"}, {OFDFT_NLK, "nlk"}};
-    const unsigned served = (caller == kHvpGga && c->hvp_gga) ? (OFDFT_PBE_X | OFDFT_PBE_C) : 0u;
+    unsigned served = 0u;
+    if (caller == kHvpGga && c->hvp_gga) served |= OFDFT_PBE_X | OFDFT_PBE_C;
+    if (caller == kHvpGga && c->hvp_wgc) served |= OFDFT_WGC99_NL;
     for (const auto& r : refused)
         if (c->mask & r.bit & ~served) return r.name;
     return nullptr;
@@ -51,11 +58,13 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
     const double inv_n = 1.0 / (double)npts;
     const bool has_h = mask & OFDFT_HARTREE, has_vw = mask & OFDFT_VW, has_wt = mask & OFDFT_WT_NL;
     const bool has_gga = mask & (OFDFT_PBE_X | OFDFT_PBE_C);         // (hvp_checks let it through: OFDFT_OPT_HVP_GGA = 1)
+    const bool has_wgc = mask & OFDFT_WGC99_NL;                      // (... OFDFT_OPT_HVP_WGC = 1)
 
     double nel = c->hvp_nel;
     if (chi) {
         nel = chi->nel;                    // sum n dV = N by construction
-    } else if (has_wt && !reuse) {         // n0 = mean(den) vol of THIS density: a constant of the differentiation (functionals.py:646-647)
+    } else if ((has_wt || has_wgc) && !reuse) {      // n0 = mean(den) vol of THIS density: a constant of the differentiation
+                                                     // (functionals.py:646-647; WGC99 rounds it, :952-954)
         double nsum;
         if (int rc = device_sum(c, den, false, &nsum, st)) return rc;
         nel = nsum * inv_n * c->vol;
@@ -192,6 +201,63 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
                      c->kg);
         if (int rc = irfftn_internal_multi(c, sw, &gdiv, 1, inv_n, st)) return rc;
     }
+    // WGC99: four triples through the evaluation's tables and mix, each in place; U and G (density-only) are retained.  Behind the PBE
+    // stage, whose pointwise field the tail adds to; the spectra are transient and leave "s0" to ofdft_precondition.
+    double wgc_sum[kHvpWgcScalars] = {0.0};
+    real* whv = nullptr;
+    if (has_wgc) {
+        static const char* const fname[4][3] = {{"hv:wU0", "hv:wU1", "hv:wU2"}, {"hv:wG0", "hv:wG1", "hv:wG2"},
+                                                {"hv:wa0", "hv:wa1", "hv:wa2"}, {"hv:wp0", "hv:wp1", "hv:wp2"}};
+        static const char* const sname[3] = {"s1", "s2", "s3"};
+        real* f[4][3];
+        cplx* sp[3];
+        for (int t = 0; t < 4; ++t)
+            for (int j = 0; j < 3; ++j)
+                if (int rc = real_ws(c, fname[t][j], &f[t][j])) return rc;
+        for (int j = 0; j < 3; ++j)
+            if (int rc = spec_ws(c, sname[j], &sp[j])) return rc;
+        double nref;
+        if (int rc = ensure_wgc_tables(c, ts.nel_r, st, &nref)) return rc;
+        HvpChiWgcArgs wa{};
+        wa.n = den;
+        wa.w = w;
+        for (int j = 0; j < 3; ++j) {
+            wa.a[j] = f[0][j];
+            wa.p[j] = f[1][j];
+            wa.da[j] = f[2][j];
+            wa.dp[j] = f[3][j];
+        }
+        whv = has_gga ? gpw : f[2][0];       // without PBE the tail writes over its first direction field
+        wa.add = has_gga ? gpw : nullptr;
+        wa.out = whv;
+        wa.npts = npts;
+        wa.al = c->params[OFDFT_P_WGC_ALPHA];
+        wa.be = c->params[OFDFT_P_WGC_BETA];
+        wa.nref = nref;
+        wa.flags = reuse ? HVP_REUSE : 0;
+        if (chi) {
+            wa.cs = chi->cs;
+            wa.k = 2.0 * chi->a / chi->S;
+            OFDFT_LAUNCH(c, st, "hvp_wgc_head", hvp_wgc_head_kernel<HvpChiWgcArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, wa);
+        } else {
+            OFDFT_LAUNCH(c, st, "hvp_wgc_head", hvp_wgc_head_kernel<HvpWgcArgs>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, (HvpWgcArgs)wa);
+        }
+        const MixWgc mix = wgc_tab(c);
+        for (int t = reuse ? 2 : 0; t < 4; ++t) {
+            if (int rc = rfftn_internal_multi(c, f[t], sp, 3, st)) return rc;
+            OFDFT_LAUNCH(c, st, "spec_wgc_mix", spec_wgc_mix_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, sp[0], sp[1], sp[2], mix.t01, mix.t2,
+                         mix.ck, c->g.total);
+            if (int rc = irfftn_internal_multi(c, sp, f[t], 3, inv_n, st)) return rc;
+        }
+        const int wblocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
+        if (chi) {
+            OFDFT_LAUNCH(c, st, "hvp_wgc_tail", hvp_wgc_tail_kernel<HvpChiWgcArgs>, dim3(wblocks), dim3(kRedThreads), 0, wa, c->d_partial);
+        } else {
+            OFDFT_LAUNCH(c, st, "hvp_wgc_tail", hvp_wgc_tail_kernel<HvpWgcArgs>, dim3(wblocks), dim3(kRedThreads), 0, (HvpWgcArgs)wa, c->d_partial);
+            if (quad_terms)            // (before the combine kernel takes the partial buffer)
+                if (int rc = fetch_partials(c, wblocks, kHvpWgcScalars, wgc_sum, st)) return rc;
+        }
+    }
     if (ns) {
         for (int b0 = 0; b0 < ns; b0 += kBsBatch)
             if (int rc = rfftn_internal_multi(c, fin + b0, spec + b0, std::min(kBsBatch, ns - b0), st)) return rc;
@@ -227,6 +293,7 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
     ca.be = ts.nlp.be;
     ca.gpw = gpw;
     ca.gdiv = gdiv;
+    ca.whv = whv;
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
     if (chi) {
         ca.g = chi->g;
@@ -235,6 +302,9 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
         ca.c2 = 2.0 * chi->cs * c->dV;
         if (has_gga)
             OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpChiCombineArgs, true>), dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
+        else if (has_wgc)
+            OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpChiCombineArgs, false, true>), dim3(blocks), dim3(kRedThreads), 0, ca,
+                         c->d_partial);
         else
             OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpChiCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, ca, c->d_partial);
         OFDFT_REDUCE(c, st, c->d_partial, blocks, kHvpChiScalars, c->d_reduced);
@@ -245,12 +315,16 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
         if (has_gga)
             OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpCombineArgs, true>), dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca,
                          c->d_partial);
+        else if (has_wgc)
+            OFDFT_LAUNCH(c, st, "hvp_combine", (hvp_combine_kernel<HvpCombineArgs, false, true>), dim3(blocks), dim3(kRedThreads), 0,
+                         (HvpCombineArgs)ca, c->d_partial);
         else
             OFDFT_LAUNCH(c, st, "hvp_combine", hvp_combine_kernel<HvpCombineArgs>, dim3(blocks), dim3(kRedThreads), 0, (HvpCombineArgs)ca, c->d_partial);
         if (quad_terms) {
             double sums[kHvpScalars];
             if (int rc = fetch_partials(c, blocks, kHvpCombineScalars, sums, st)) return rc;
             for (int s = 0; s < kHvpGgaScalars; ++s) sums[kHvpCombineScalars + s] = gga_sums[s];       // bits 10, 11: pbe_x, pbe_c
+            sums[5] = wgc_sum[0];                                                                      // bit 5: wgc99_nl (the tail kernel)
             for (int t = 0; t < OFDFT_NTERMS; ++t) quad_terms[t] = (t < kHvpScalars && ((mask >> t) & 1)) ? sums[t] * c->dV : 0.0;
         }
     }

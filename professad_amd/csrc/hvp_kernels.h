@@ -194,11 +194,12 @@ struct HvpCombineArgs {
     int two;
     real al, be;
     const real* gpw;  const real* gdiv;   // GGA (kGga instantiations): the mid kernel's pointwise part, div flux
+    const real* whv;                      // WGC99 without PBE (kWgc instantiations): the tail kernel's field (with PBE it is inside gpw)
 };
 struct HvpPoint { real n, w, vh, lap, dlap, A, Cb, B, Ca; };
 __device__ __forceinline__ real hvp_combine_point(const HvpCombineArgs& a, const HvpPoint& p, acc_t (&acc)[kHvpCombineScalars], real hv0 = 0.0) {
     const real n = p.n, w = p.w;
-    real hv = hv0;                               // PBE: f_nn w + f_nsigma dsigma - 2 div flux (their w hv_t come from the mid kernel)
+    real hv = hv0;                               // PBE: f_nn w + f_nsigma dsigma - 2 div flux; WGC99: the tail's field (their w hv_t come from those kernels)
     if (a.mask & OFDFT_HARTREE) {
         acc[1] += w * p.vh;
         hv += p.vh;
@@ -270,7 +271,8 @@ __device__ __forceinline__ real hvp_chi_point(const HvpChiCombineArgs& a, real p
     return P;
 }
 // (every array pointer is valid: the host points the fields of absent terms at `n`, as for combine_kernel)
-template <class Args, bool kGga = false>
+// hv0, the start value of hv: kGga: gpw - 2 gdiv (the WGC99 tail has added its field to gpw where both run); kWgc: whv
+template <class Args, bool kGga = false, bool kWgc = false>
 static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a, acc_t* __restrict__ partial) {
     acc_t acc[kHvpCombineScalars];
 #pragma unroll
@@ -286,6 +288,8 @@ static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a,
         if constexpr (kGga) {
             const cplx pw = LD2(a.gpw), dv = LD2(a.gdiv);
             g0 = mkc(pw.x - 2.0 * dv.x, pw.y - 2.0 * dv.y);
+        } else if constexpr (kWgc) {
+            g0 = LD2(a.whv);
         }
         if constexpr (Args::kChi) {
             const cplx phi = n, d = w, g = a.g ? LD2(a.g) : mkc(0.0, 0.0);
@@ -307,6 +311,7 @@ static __global__ __launch_bounds__(kRedThreads) void hvp_combine_kernel(Args a,
         const long long i = a.npts - 1;
         real g0 = 0.0;
         if constexpr (kGga) g0 = a.gpw[i] - 2.0 * a.gdiv[i];
+        else if constexpr (kWgc) g0 = a.whv[i];
         if constexpr (Args::kChi) {
             real n, w;
             hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
@@ -385,6 +390,142 @@ static __global__ __launch_bounds__(kRedThreads) void hvp_gga_mid_kernel(Args a,
         a.gw[2][i] = p.f2;
     }
     if constexpr (!Args::kChi) block_reduce_store<kHvpGgaScalars>(acc, partial);
+}
+
+// ---- WGC99 stage (OFDFT_OPT_HVP_WGC = 1).  n_ref is a constant of the differentiation (functionals.py:952-954 take
+// round(N) with .item()), so the nonlocal energy is E = c dV sum p . (M a) with a fixed symmetric 3 x 3 block M of real convolution
+// kernels (spec_wgc_mix_kernel) between pointwise functions of n: with theta = n - n_ref,
+//   a = (A, A theta, A theta^2 / 2), A = n^beta;      p = (P, P theta, P theta^2 / 2), P = n^alpha;      U = M a,  G = M p,
+//   hv = c sum_i [ p_i'' w U_i + p_i' (M (a' w))_i + a_i'' w G_i + a_i' (M (p' w))_i ]           (' = d/dn, d theta / dn = 1).
+// The head writes a, p (density-only: not with HVP_REUSE) and a' w, p' w; the host runs each triple through M in place; the tail forms
+// hv, adds it to `add` (the PBE stage's pointwise field) where given, and reduces sum w hv.  Both kernels take the chi-space pair
+// (phi, d) as head and combine do, forming n and w = dn on the fly; the chi-space tail reduces nothing.
+constexpr int kHvpWgcScalars = 1;
+struct HvpWgcArgs {
+    static constexpr bool kChi = false;
+    const real* n;
+    const real* w;
+    real* a[3];   real* p[3];    // head: a, p out;            tail: U, G in       ("hv:wU0..2", "hv:wG0..2": retained)
+    real* da[3];  real* dp[3];   // head: a' w, p' w out;      tail: M (a' w), M (p' w) in
+    const real* add;             // tail: nullptr or a field hv is added to (may be `out`)
+    real* out;                   // tail: hv (may be da[0]: every thread reads its own elements before it writes them)
+    long long npts;
+    real al, be, nref;
+    unsigned flags;              // HVP_REUSE
+};
+struct HvpChiWgcArgs : HvpWgcArgs {
+    static constexpr bool kChi = true;
+    real cs, k;
+};
+// (f, f theta, f theta^2 / 2) for f = n^e, with its first and second derivative in n; the power is the evaluation's (fm::pow_pos:
+// bluestein.h bs_prep, zpass.h), 0 where n is not positive
+struct WgcTriple { real v[3], d[3], dd[3]; };
+__device__ __forceinline__ WgcTriple wgc_triple(real n, real th, real e) {
+    const real f2 = n > 0.0 ? fm::pow_pos(n, e - (real)2.0) : (real)0.0;
+    const real f1 = f2 * n, f = f1 * n, h = 0.5 * th * th;
+    const real g1 = e * f1, g2 = e * (e - 1.0) * f2;
+    WgcTriple t;
+    t.v[0] = f;    t.v[1] = f * th;                  t.v[2] = f * h;
+    t.d[0] = g1;   t.d[1] = g1 * th + f;             t.d[2] = g1 * h + f * th;
+    t.dd[0] = g2;  t.dd[1] = g2 * th + 2.0 * g1;     t.dd[2] = g2 * h + 2.0 * g1 * th + f;
+    return t;
+}
+template <class Args>
+static __global__ void hvp_wgc_head_kernel(Args a) {
+    const bool dens = !(a.flags & HVP_REUSE);
+    const long long n2 = a.npts >> 1;
+#define ST2(ptr, u, v) reinterpret_cast<cplx*>(ptr)[i] = mkc(u, v)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        cplx n = reinterpret_cast<const cplx*>(a.n)[i], w = reinterpret_cast<const cplx*>(a.w)[i];
+        if constexpr (Args::kChi) {
+            const cplx phi = n, d = w;
+            hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
+            hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
+        }
+        const WgcTriple b0 = wgc_triple(n.x, n.x - a.nref, a.be), b1 = wgc_triple(n.y, n.y - a.nref, a.be);
+        const WgcTriple p0 = wgc_triple(n.x, n.x - a.nref, a.al), p1 = wgc_triple(n.y, n.y - a.nref, a.al);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (dens) {
+                ST2(a.a[j], b0.v[j], b1.v[j]);
+                ST2(a.p[j], p0.v[j], p1.v[j]);
+            }
+            ST2(a.da[j], b0.d[j] * w.x, b1.d[j] * w.y);
+            ST2(a.dp[j], p0.d[j] * w.x, p1.d[j] * w.y);
+        }
+    }
+#undef ST2
+    if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long i = a.npts - 1;
+        real n = a.n[i], w = a.w[i];
+        if constexpr (Args::kChi) hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
+        const WgcTriple b = wgc_triple(n, n - a.nref, a.be), p = wgc_triple(n, n - a.nref, a.al);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (dens) {
+                a.a[j][i] = b.v[j];
+                a.p[j][i] = p.v[j];
+            }
+            a.da[j][i] = b.d[j] * w;
+            a.dp[j][i] = p.d[j] * w;
+        }
+    }
+}
+struct HvpWgcPoint { real U[3], G[3], Ma[3], Mp[3]; };
+__device__ __forceinline__ real hvp_wgc_point(const HvpWgcArgs& a, real n, real w, const HvpWgcPoint& q, acc_t (&acc)[kHvpWgcScalars]) {
+    const WgcTriple b = wgc_triple(n, n - a.nref, a.be), p = wgc_triple(n, n - a.nref, a.al);
+    real s = 0.0, t = 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        s += p.dd[j] * q.U[j] + b.dd[j] * q.G[j];
+        t += p.d[j] * q.Ma[j] + b.d[j] * q.Mp[j];
+    }
+    const real hv = kCtf * (s * w + t);
+    acc[0] += w * hv;
+    return hv;
+}
+template <class Args>
+static __global__ __launch_bounds__(kRedThreads) void hvp_wgc_tail_kernel(Args a, acc_t* __restrict__ partial) {
+    acc_t acc[kHvpWgcScalars] = {0.0};
+    const long long n2 = a.npts >> 1;
+#define LD2(ptr) reinterpret_cast<const cplx*>(ptr)[i]
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+        cplx n = LD2(a.n), w = LD2(a.w);
+        if constexpr (Args::kChi) {
+            const cplx phi = n, d = w;
+            hvp_chi_density(a.cs, a.k, phi.x, d.x, n.x, w.x);
+            hvp_chi_density(a.cs, a.k, phi.y, d.y, n.y, w.y);
+        }
+        HvpWgcPoint q0, q1;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const cplx U = LD2(a.a[j]), G = LD2(a.p[j]), Ma = LD2(a.da[j]), Mp = LD2(a.dp[j]);
+            q0.U[j] = U.x;    q1.U[j] = U.y;
+            q0.G[j] = G.x;    q1.G[j] = G.y;
+            q0.Ma[j] = Ma.x;  q1.Ma[j] = Ma.y;
+            q0.Mp[j] = Mp.x;  q1.Mp[j] = Mp.y;
+        }
+        const cplx h0 = a.add ? LD2(a.add) : mkc(0.0, 0.0);
+        const real v0 = hvp_wgc_point(a, n.x, w.x, q0, acc), v1 = hvp_wgc_point(a, n.y, w.y, q1, acc);
+        reinterpret_cast<cplx*>(a.out)[i] = mkc(h0.x + v0, h0.y + v1);
+    }
+#undef LD2
+    if ((a.npts & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long i = a.npts - 1;
+        real n = a.n[i], w = a.w[i];
+        if constexpr (Args::kChi) hvp_chi_density(a.cs, a.k, a.n[i], a.w[i], n, w);
+        HvpWgcPoint q;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            q.U[j] = a.a[j][i];
+            q.G[j] = a.p[j][i];
+            q.Ma[j] = a.da[j][i];
+            q.Mp[j] = a.dp[j][i];
+        }
+        const real h0 = a.add ? a.add[i] : (real)0.0;
+        a.out[i] = h0 + hvp_wgc_point(a, n, w, q, acc);
+    }
+    if constexpr (!Args::kChi) block_reduce_store<kHvpWgcScalars>(acc, partial);
 }
 
 // ---- chi space, before the head: phi.d and phi.phi (fixed order, as every reduction here)

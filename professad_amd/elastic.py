@@ -61,7 +61,7 @@ class HipElasticBackend(optimize.HipResponseBackend):
 
 def refusal(engine, pme_order=None):
     """None, or why `elastic_constants` cannot run on this engine (raised before any device work).  pbe_x / pbe_c are refused
-    whatever the engine's OPT_HVP_GGA says: their strain derivative is not built."""
+    whatever the engine's OPT_HVP_GGA says, and wgc99_nl whatever its OPT_HVP_WGC says: their strain derivative is not built."""
     return optimize.response_refusal(engine, pme_order, 'strain')
 
 

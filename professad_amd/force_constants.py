@@ -41,7 +41,7 @@ def refusal(engine, pme_order=None):
 
 def batch_refusal(engine):
     """None, or why `force_constants(batch=k)` cannot run where `batch=None` can: with the engine's OPT_HVP_GGA at 1 pbe_x / pbe_c pass
-    the single-column solves, and the batched ones keep refusing them by name"""
+    the single-column solves (with its OPT_HVP_WGC at 1, wgc99_nl), and the batched ones keep refusing them by name"""
     return optimize.second_order_refusal(engine, gga_missing='batch')
 
 

@@ -7,8 +7,8 @@ takes ``v_ext`` as a third argument) of src/professad/functionals.py, keeps the 
 derivative computed by the engine (no autograd through FFTs).  Under ``create_graph=True`` that derivative is itself
 differentiable in ``den``: its backward is the engine's Hessian-vector product (``Engine.hessian_vector``), for the terms
 that have one (Hartree, TF, vW, the Wang-Teter family, the local XC terms); the others raise ``NotImplementedError`` there.
-PBE stays among the others here: its second derivative is an option of an ``Engine`` of one's own (``OPT_HVP_GGA``),
-and the engines behind these terms are shared and keep the default.
+PBE and WGC99 stay among the others here: their second derivatives are options of an ``Engine`` of one's own (``OPT_HVP_GGA``,
+``OPT_HVP_WGC``), and the engines behind these terms are shared and keep the default.
 ``get_inv_G`` (functional_tools.py:34-70) rests on it.
 
 So ``terms=[IonElectron, Hartree, WangTeter, PerdewBurkeErnzerhof]`` built from THIS module can be

@@ -433,10 +433,17 @@ class TwoPointGradientDescent:
 CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_CURVATURE = 0, 1, 2, 3      # exit reasons of a solve (OFDFT_CG_*; _native.CG_REASONS)
 _UNSERVED = ('wgc99_nl', 'pbe_x', 'pbe_c', 'gga_k', 'vwgtf', 'nlk')    # terms without a second derivative (ofdft_hessian_vector)
 _GGA_OPT_IN = ('pbe_x', 'pbe_c')           # ... served by the single-column products once the engine's OPT_HVP_GGA is 1
+_WGC_OPT_IN = ('wgc99_nl',)                # ... once its OPT_HVP_WGC is 1
 _GGA_MISSING = {
     'batch': 'batching is what is missing -- the multi-column product has no PBE stage; use the single-column path (batch=None, '
              'density_response, Engine.hessian_vector_chi)',
     'strain': 'the strain derivative of PBE is not built (elastic constants, bulk modulus, Engine.strain_hessian, '
+              'Engine.potential_strain_gradient)',
+}
+_WGC_MISSING = {
+    'batch': 'batching is what is missing -- the multi-column product has no WGC99 stage; use the single-column path (batch=None, '
+             'density_response, Engine.hessian_vector_chi)',
+    'strain': 'the strain derivative of WGC99 is not built (elastic constants, bulk modulus, Engine.strain_hessian, '
               'Engine.potential_strain_gradient)',
 }
 
@@ -448,34 +455,53 @@ def hvp_gga_enabled(engine):
     return option is not None and option(N.OPT_HVP_GGA) == 1
 
 
-def gga_strain_refusal(engine):
-    """None, or -- with the engine's OPT_HVP_GGA at 1 and pbe_x / pbe_c among its terms -- why its strain entries do not serve them:
-    the products then let these terms through, the strain entries say so before any device work"""
+def hvp_wgc_enabled(engine):
+    """the engine's OPT_HVP_WGC is 1 (as `hvp_gga_enabled`)"""
     from . import _native as N
-    if hvp_gga_enabled(engine) and engine._terms_key is not None:
-        for name in _GGA_OPT_IN:
-            if engine._mask() & N.TERM_BITS[name]:
-                return 'no second derivative of the term %s here: %s' % (name, _GGA_MISSING['strain'])
+    option = getattr(engine, 'option', None)
+    return option is not None and option(N.OPT_HVP_WGC) == 1
+
+
+def _opted_in(engine):
+    """term name -> what the batched and strain paths lack for it, for the terms the engine's options open to the single-column products"""
+    opened = {}
+    if hvp_wgc_enabled(engine):
+        opened.update((name, _WGC_MISSING) for name in _WGC_OPT_IN)
+    if hvp_gga_enabled(engine):
+        opened.update((name, _GGA_MISSING) for name in _GGA_OPT_IN)
+    return opened
+
+
+def gga_strain_refusal(engine):
+    """None, or -- with the engine's OPT_HVP_GGA (OPT_HVP_WGC) at 1 and pbe_x / pbe_c (wgc99_nl) among its terms -- why its strain
+    entries do not serve them: the products then let these terms through, the strain entries say so before any device work"""
+    from . import _native as N
+    opened = _opted_in(engine)
+    if opened and engine._terms_key is not None:
+        for name in _UNSERVED:
+            if name in opened and engine._mask() & N.TERM_BITS[name]:
+                return 'no second derivative of the term %s here: %s' % (name, opened[name]['strain'])
     return None
 
 
 def second_order_refusal(engine, gga_missing=None):
     """None, or why the engine cannot serve Hessian-vector products in chi (what ofdft_hessian_vector_chi itself refuses).
-    pbe_x / pbe_c pass when the engine's OPT_HVP_GGA is 1 -- unless `gga_missing` names what the asking path lacks for them
-    ('batch': the multi-column entries, 'strain': the elastic entries), which keep refusing them by name."""
+    pbe_x / pbe_c pass when the engine's OPT_HVP_GGA is 1 and wgc99_nl when its OPT_HVP_WGC is 1 -- unless `gga_missing` names what
+    the asking path lacks for them ('batch': the multi-column entries, 'strain': the elastic entries), which keep refusing them by
+    name."""
     from . import _native as N
     if getattr(engine, 'comm', None) is not None:
         return 'the Hessian-vector product is served by single-GPU contexts; a slab-decomposed DistEngine has no second derivative'
     if engine.dtype != torch.double:
         return 'the Hessian-vector product is fp64 work (libofdft_hip.so); an fp32 engine does not serve it'
     mask = engine._mask()
-    gga_on = hvp_gga_enabled(engine)
+    opened = _opted_in(engine)
     for name in _UNSERVED:
         if mask & N.TERM_BITS[name]:
-            if name in _GGA_OPT_IN and gga_on:
+            if name in opened:
                 if gga_missing is None:
                     continue
-                return 'no second derivative of the term %s here: %s' % (name, _GGA_MISSING[gga_missing])
+                return 'no second derivative of the term %s here: %s' % (name, opened[name][gga_missing])
             return 'no second derivative of the term %s' % name
     if mask & N.TERM_BITS['wt_nl'] and np.frombuffer(engine._terms_key[1], dtype=np.float64)[12] != 0.0:
         return 'no second derivative of the stabilised Wang-Teter style functional (wts_kind)'
