@@ -516,7 +516,8 @@ int  ofdft_lbfgs_update(ofdft_lbfgs* h, const double* coef_s, const double* coef
  *                   (x += alpha p, r -= alpha (q - phi (phi . q) / S); sums r . r, phi . r), the stopping rules, and one
  *                   direction sweep (p = r - phi (phi . r) / S + beta p).  One stream synchronisation.
  *   ofdft_cg_status iterations done, reason, |r| / |r_0|.        ofdft_cg_solution copies x to the caller's array.
- * No atomics: bitwise reproducible. */
+ * These entries are the one-column case of ofdft_cgm_* below (a handle with ncols_max = 1, the scalars as one-element arrays, the
+ * reason that of column 0): one solver, one set of kernels, the same bits.  No atomics: bitwise reproducible. */
 #define OFDFT_CG_RUNNING   0
 #define OFDFT_CG_CONVERGED 1
 #define OFDFT_CG_MAXITER   2
@@ -552,7 +553,7 @@ int  ofdft_cg_direction(ofdft_cg* h, const void* phi_dev, double* info_host /* [
  * A handle for (n, ncols_max <= OFDFT_MULTI_MAX, device) holds x, r, p, q, z as [ncols_max] columns at the stride that
  * ofdft_cgm_vectors reports (n rounded up to even), and per column rho, phi . r, |r|^2, |r_0|^2, the iteration count and the exit
  * reason.  Not block Krylov: the columns share phi and S only, and each runs the recurrence of ofdft_cg_* with its own alpha and
- * beta, so a column's result, reason and count are those of a solo solve (its sums are formed in the solo kernels' order).
+ * beta, so a column's result, reason and count are those of a solo solve (its sums do not depend on the columns beside it).
  * Every sweep is one launch for all columns -- the column is the grid's y index, the per-column coefficients travel by value --
  * and one fetch of all columns' sums.  A column that has ended (converged, curvature, maxiter, NaN) is frozen: no later sweep
  * writes its x or r, and its reason and count stay.  The caller's product (ofdft_hessian_vector_chi_multi on p -> q of all

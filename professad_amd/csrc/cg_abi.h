@@ -1,266 +1,24 @@
 // C ABI of the device-resident conjugate-gradient solver (cg_kernels.h, include/ofdft_hip.h).  Included once, at the end of
 // engine.hip, behind lbfgs_abi.h whose helpers (lfail's pattern, DeviceScope) it follows.
+// One solver: ofdft_cgm_* below run ncols recurrences in lockstep behind one handle, every sweep one launch and one fetch for all
+// columns.  The columns share nothing but phi and S: each keeps its own alpha, beta, rho, phi.r, exit reason and
+// iteration count, and ends on its own; the run ends when every column has.  ofdft_cg_*, at the end of this file, are that solver
+// with ncols_max = 1: wrappers that pass the scalars as one-element arrays and report column 0.
 #pragma once
+#include <cstdarg>
 #include <new>
 
 #include "cg_kernels.h"
 
-struct ofdft_cg {
-    long long n = 0;
-    int device = 0;
-    real *x = nullptr, *r = nullptr, *p = nullptr, *q = nullptr;
-    real* z = nullptr;               // preconditioned mode: z = M^-1 r, written by the caller (allocated on first use)
-    bool pre_next = false;           // ofdft_cg_set_preconditioned: the mode of the next ofdft_cg_start
-    bool pre = false;                // the mode of the running solve
-    bool dir_ready = false;          // preconditioned mode: ofdft_cg_direction has formed p for the coming step
-    bool dir_first = false;          // ... and none has run since ofdft_cg_start (beta = 0)
-    double rho = 0.0, phir = 0.0;    // r.Pz of the last direction; phi.r of the last update sweep
-    double *d_partial = nullptr, *d_out = nullptr, *h_out = nullptr;
-    bool started = false;
-    int iters = 0, maxiter = 0, reason = OFDFT_CG_RUNNING;
-    double bb = 0.0, S = 0.0, rr = 0.0, rtol = 0.0;
-    char err[256] = "";
+// the words in which the messages of the two families of entries differ
+struct CgWords {
+    const char *pfx, *all_have, *directions, *are;
 };
+static const CgWords kCgOne = {"ofdft_cg", "the solve has", "direction", "is"};
+static const CgWords kCgMulti = {"ofdft_cgm", "every column has", "directions", "are"};
 
-namespace {
-
-int cfail(ofdft_cg* o, int code, const char* msg) {
-    if (o) std::snprintf(o->err, sizeof(o->err), "%s", msg);
-    return code;
-}
-#define CG_TRY(o, expr)                                                           \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) return cfail(o, OFDFT_EHIP, hipGetErrorString(e_)); \
-    } while (0)
-
-int cg_blocks(const ofdft_cg* o) {
-    long long want = (o->n / 2 + kRedThreads) / kRedThreads;
-    return (int)(want < 1 ? 1 : (want > kRedBlocks ? kRedBlocks : want));
-}
-int cg_ensure_z(ofdft_cg* o) {
-    if (!o->z) CG_TRY(o, hipMalloc((void**)&o->z, sizeof(real) * (size_t)o->n));
-    return OFDFT_OK;
-}
-// second-level sum of `ns` scalars, to the host (one synchronisation)
-int cg_fetch(ofdft_cg* o, int blocks, int ns, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ns), dim3(kRedThreads), 0, st, (const double*)o->d_partial, blocks, ns, o->d_out);
-    CG_TRY(o, hipMemcpyAsync(o->h_out, o->d_out, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    CG_TRY(o, hipStreamSynchronize(st));
-    CG_TRY(o, hipGetLastError());
-    for (int s = 0; s < ns; ++s) out[s] = o->h_out[s];
-    return OFDFT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ofdft_cg_create(ofdft_cg** out, long long n, int device_id) {
-    if (!out || n < 1) return OFDFT_EINVAL;
-    *out = nullptr;
-    ofdft_cg* o = new (std::nothrow) ofdft_cg();
-    if (!o) return OFDFT_ENOMEM;
-    o->n = n;
-    o->device = device_id;
-    DeviceScope device_scope_(device_id);
-    hipError_t e = device_scope_.err;
-    const size_t vb = sizeof(real) * (size_t)n;
-    for (real** v : {&o->x, &o->r, &o->p, &o->q})
-        if (e == hipSuccess) e = hipMalloc((void**)v, vb);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->d_partial, sizeof(double) * kRedBlocks * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&o->d_out, sizeof(double) * 4);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_out, sizeof(double) * 4);
-    if (e != hipSuccess) {
-        ofdft_cg_destroy(o);
-        return e == hipErrorOutOfMemory ? OFDFT_ENOMEM : OFDFT_EHIP;
-    }
-    *out = o;
-    return OFDFT_OK;
-}
-
-void ofdft_cg_destroy(ofdft_cg* o) {
-    if (!o) return;
-    DeviceScope device_scope_(o->device);
-    for (real* v : {o->x, o->r, o->p, o->q, o->z})
-        if (v) (void)hipFree(v);
-    if (o->d_partial) (void)hipFree(o->d_partial);
-    if (o->d_out) (void)hipFree(o->d_out);
-    if (o->h_out) (void)hipHostFree(o->h_out);
-    delete o;
-}
-
-const char* ofdft_cg_last_error(const ofdft_cg* o) { return o ? o->err : "null handle"; }
-
-int ofdft_cg_start(ofdft_cg* o, const void* phi_dev, const void* b_dev, double rtol, int maxiter, double* info_host, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!o || !phi_dev || !b_dev || !(rtol >= 0.0) || maxiter < 1) return OFDFT_EINVAL;
-    DeviceScope device_scope_(o->device);
-    CG_TRY(o, device_scope_.err);
-    o->started = false;
-    o->pre = o->pre_next;
-    if (o->pre)
-        if (int rc = cg_ensure_z(o)) return rc;
-    const real* phi = (const real*)phi_dev;
-    const real* b = (const real*)b_dev;
-    const int blocks = cg_blocks(o);
-    hipLaunchKernelGGL(cg_start_dots_kernel, dim3(blocks), dim3(kRedThreads), 0, st, phi, b, o->n, o->d_partial);
-    double s3[3];
-    if (int rc = cg_fetch(o, blocks, 3, s3, st)) return rc;
-    if (!(s3[1] > 0.0)) return cfail(o, OFDFT_EINVAL, "ofdft_cg_start: phi is zero everywhere");
-    hipLaunchKernelGGL(cg_start_kernel, dim3(blocks), dim3(kRedThreads), 0, st, phi, b, (real)(s3[2] / s3[1]), o->x, o->r, o->p, o->n,
-                       o->d_partial);
-    double rr;
-    if (int rc = cg_fetch(o, blocks, 1, &rr, st)) return rc;
-    o->bb = rr;              // the norm of the projected right-hand side is the yardstick of the relative residual
-    o->S = s3[1];
-    o->rr = rr;
-    o->rtol = rtol;
-    o->maxiter = maxiter;
-    o->iters = 0;
-    o->dir_ready = false;      // preconditioned mode: p = r of the sweep above is not a direction yet (ofdft_cg_direction forms it)
-    o->dir_first = true;
-    o->rho = 0.0;
-    o->phir = 0.0;             // r = P b
-    o->reason = rr > 0.0 ? OFDFT_CG_RUNNING : OFDFT_CG_CONVERGED;      // b = 0: x = 0 solves it
-    o->started = true;
-    if (info_host) {
-        info_host[0] = rr;
-        info_host[1] = s3[1];
-        info_host[2] = s3[2];
-    }
-    return OFDFT_OK;
-}
-
-int ofdft_cg_vectors(ofdft_cg* o, void** x_dev, void** r_dev, void** p_dev, void** q_dev) {
-    if (!o) return OFDFT_EINVAL;
-    if (x_dev) *x_dev = o->x;
-    if (r_dev) *r_dev = o->r;
-    if (p_dev) *p_dev = o->p;
-    if (q_dev) *q_dev = o->q;
-    return OFDFT_OK;
-}
-
-int ofdft_cg_step(ofdft_cg* o, const void* phi_dev, double p_dot_q, double phi_dot_q, int* reason, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!o || !phi_dev || !reason) return OFDFT_EINVAL;
-    if (!o->started) return cfail(o, OFDFT_ESTATE, "ofdft_cg_step: ofdft_cg_start has not been called");
-    if (o->reason != OFDFT_CG_RUNNING) return cfail(o, OFDFT_ESTATE, "ofdft_cg_step: the solve has ended (ofdft_cg_status)");
-    if (o->pre && !o->dir_ready)
-        return cfail(o, OFDFT_ESTATE, "ofdft_cg_step: preconditioned mode, and ofdft_cg_direction has not formed the direction of this step");
-    DeviceScope device_scope_(o->device);
-    CG_TRY(o, device_scope_.err);
-    const real* phi = (const real*)phi_dev;
-    if (!(p_dot_q > 0.0)) {            // non-positive curvature (or NaN): x stays; before the first update x = p, the steepest descent step
-        if (o->iters == 0) {
-            CG_TRY(o, hipMemcpyAsync(o->x, o->p, sizeof(real) * (size_t)o->n, hipMemcpyDeviceToDevice, st));
-            CG_TRY(o, hipStreamSynchronize(st));
-        }
-        *reason = o->reason = OFDFT_CG_CURVATURE;
-        return OFDFT_OK;
-    }
-    const int blocks = cg_blocks(o);
-    const double alpha = (o->pre ? o->rho : o->rr) / p_dot_q;
-    hipLaunchKernelGGL(cg_update_kernel, dim3(blocks), dim3(kRedThreads), 0, st, phi, (const real*)o->p, (const real*)o->q, (real)alpha,
-                       (real)(phi_dot_q / o->S), o->x, o->r, o->n, o->d_partial);
-    double s2[2];
-    if (int rc = cg_fetch(o, blocks, 2, s2, st)) return rc;
-    o->iters++;
-    const double rr_old = o->rr;
-    o->rr = s2[0];
-    o->phir = s2[1];
-    o->dir_ready = false;
-    if (o->rr != o->rr) o->reason = OFDFT_CG_CURVATURE;      // a NaN in the product: nothing more to gain from this solve
-    else if (!(o->rr > o->rtol * o->rtol * o->bb)) o->reason = OFDFT_CG_CONVERGED;      // |r| <= rtol |b|
-    else if (o->iters >= o->maxiter) o->reason = OFDFT_CG_MAXITER;
-    else if (!o->pre)
-        hipLaunchKernelGGL(cg_direction_kernel, dim3(blocks), dim3(256), 0, st, phi, (const real*)o->r, (real)(o->rr / rr_old),
-                           (real)(s2[1] / o->S), o->p, o->n);
-    *reason = o->reason;
-    return OFDFT_OK;
-}
-
-int ofdft_cg_set_preconditioned(ofdft_cg* o, int on) {
-    if (!o) return OFDFT_EINVAL;
-    o->pre_next = on != 0;
-    return OFDFT_OK;
-}
-
-int ofdft_cg_z(ofdft_cg* o, void** z_dev) {
-    if (!o || !z_dev) return OFDFT_EINVAL;
-    DeviceScope device_scope_(o->device);
-    CG_TRY(o, device_scope_.err);
-    if (int rc = cg_ensure_z(o)) return rc;
-    *z_dev = o->z;
-    return OFDFT_OK;
-}
-
-// preconditioned mode, between the update sweep of one step and the product of the next: with z = M^-1 r in place,
-// rho = r.Pz = r.z - (phi.r)(phi.z) / S, beta = rho / rho_old (0 after ofdft_cg_start), p = Pz + beta p.  One synchronisation.
-int ofdft_cg_direction(ofdft_cg* o, const void* phi_dev, double* info_host, int* reason, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!o || !phi_dev || !reason) return OFDFT_EINVAL;
-    if (!o->started) return cfail(o, OFDFT_ESTATE, "ofdft_cg_direction: ofdft_cg_start has not been called");
-    if (!o->pre) return cfail(o, OFDFT_ESTATE, "ofdft_cg_direction: the solve runs in plain mode (ofdft_cg_set_preconditioned before ofdft_cg_start)");
-    if (o->reason != OFDFT_CG_RUNNING) return cfail(o, OFDFT_ESTATE, "ofdft_cg_direction: the solve has ended (ofdft_cg_status)");
-    if (o->dir_ready) return cfail(o, OFDFT_ESTATE, "ofdft_cg_direction: the direction of this step is already formed (ofdft_cg_step)");
-    DeviceScope device_scope_(o->device);
-    CG_TRY(o, device_scope_.err);
-    const real* phi = (const real*)phi_dev;
-    const int blocks = cg_blocks(o);
-    hipLaunchKernelGGL(cg_pre_dots_kernel, dim3(blocks), dim3(kRedThreads), 0, st, phi, (const real*)o->r, (const real*)o->z, o->n, o->d_partial);
-    double s2[2];
-    if (int rc = cg_fetch(o, blocks, 2, s2, st)) return rc;
-    const double rho = s2[0] - o->phir * s2[1] / o->S;
-    if (info_host) {
-        info_host[0] = s2[0];
-        info_host[1] = s2[1];
-        info_host[2] = rho;
-        info_host[3] = o->dir_first ? 0.0 : rho / o->rho;
-    }
-    if (!(rho > 0.0)) {                // M is positive definite: only a NaN or a vanished residual comes here; x stays
-        *reason = o->reason = OFDFT_CG_CURVATURE;
-        return OFDFT_OK;
-    }
-    const real s = (real)(s2[1] / o->S);
-    if (o->dir_first)
-        hipLaunchKernelGGL(cg_pre_direction_kernel<true>, dim3(blocks), dim3(kRedThreads), 0, st, phi, (const real*)o->z, (real)0.0, s, o->p, o->n);
-    else
-        hipLaunchKernelGGL(cg_pre_direction_kernel<false>, dim3(blocks), dim3(kRedThreads), 0, st, phi, (const real*)o->z, (real)(rho / o->rho), s,
-                           o->p, o->n);
-    CG_TRY(o, hipGetLastError());
-    o->rho = rho;
-    o->dir_first = false;
-    o->dir_ready = true;
-    *reason = o->reason;
-    return OFDFT_OK;
-}
-
-// x of the solve, copied to the caller's array (the stream's order; no wait)
-int ofdft_cg_solution(ofdft_cg* o, void* x_out_dev, void* stream) {
-    if (!o || !x_out_dev) return OFDFT_EINVAL;
-    if (!o->started) return cfail(o, OFDFT_ESTATE, "ofdft_cg_solution: ofdft_cg_start has not been called");
-    DeviceScope device_scope_(o->device);
-    CG_TRY(o, device_scope_.err);
-    CG_TRY(o, hipMemcpyAsync(x_out_dev, o->x, sizeof(real) * (size_t)o->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return OFDFT_OK;
-}
-
-int ofdft_cg_status(const ofdft_cg* o, int* iterations, int* reason, double* rel_residual) {
-    if (!o) return OFDFT_EINVAL;
-    if (iterations) *iterations = o->iters;
-    if (reason) *reason = o->reason;
-    if (rel_residual) *rel_residual = o->bb > 0.0 ? std::sqrt(o->rr / o->bb) : 0.0;
-    return OFDFT_OK;
-}
-
-}  // extern "C"
-
-// ================================================================================================================================
-// Several solves in lockstep (include/ofdft_hip.h): ncols recurrences of the solver above behind one handle, every
-// sweep one launch and one fetch for all columns.  The columns share nothing but phi and S: each keeps its own alpha, beta, rho,
-// phi.r, exit reason and iteration count, and ends on its own; the run ends when every column has.
 struct ofdft_cgm {
+    const CgWords* w = &kCgMulti;
     long long n = 0, ld = 0;         // points per column; column stride of the handle's vectors (n rounded up to even)
     int ncols_max = 0, ncols = 0, device = 0;
     real *x = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *z = nullptr;      // [ncols_max][ld]; z on first use
@@ -277,14 +35,19 @@ struct ofdft_cgm {
 
 namespace {
 
-int mfail(ofdft_cgm* o, int code, const char* msg) {
-    if (o) std::snprintf(o->err, sizeof(o->err), "%s", msg);
+int mfail(ofdft_cgm* o, int code, const char* fmt, ...) {
+    if (o) {
+        va_list ap;
+        va_start(ap, fmt);
+        std::vsnprintf(o->err, sizeof(o->err), fmt, ap);
+        va_end(ap);
+    }
     return code;
 }
-#define CGM_TRY(o, expr)                                                          \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) return mfail(o, OFDFT_EHIP, hipGetErrorString(e_)); \
+#define CGM_TRY(o, expr)                                                                \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess) return mfail(o, OFDFT_EHIP, "%s", hipGetErrorString(e_)); \
     } while (0)
 
 int cgm_blocks(const ofdft_cgm* o) {
@@ -310,15 +73,25 @@ int cgm_running(const ofdft_cgm* o) {
     return k;
 }
 
-}  // namespace
+template <class H>
+void cgm_destroy(H* o) {
+    if (!o) return;
+    DeviceScope device_scope_(o->device);
+    for (real* v : {o->x, o->r, o->p, o->q, o->z})
+        if (v) (void)hipFree(v);
+    if (o->d_partial) (void)hipFree(o->d_partial);
+    if (o->d_out) (void)hipFree(o->d_out);
+    if (o->h_out) (void)hipHostFree(o->h_out);
+    delete o;
+}
 
-extern "C" {
-
-int ofdft_cgm_create(ofdft_cgm** out, long long n, int ncols_max, int device_id) {
+template <class H>
+int cgm_create(H** out, long long n, int ncols_max, int device_id, const CgWords* w) {
     if (!out || n < 1 || ncols_max < 1 || ncols_max > kCgmMax) return OFDFT_EINVAL;
     *out = nullptr;
-    ofdft_cgm* o = new (std::nothrow) ofdft_cgm();
+    H* o = new (std::nothrow) H();
     if (!o) return OFDFT_ENOMEM;
+    o->w = w;
     o->n = n;
     o->ld = (n + 1) & ~1LL;
     o->ncols_max = ncols_max;
@@ -332,23 +105,20 @@ int ofdft_cgm_create(ofdft_cgm** out, long long n, int ncols_max, int device_id)
     if (e == hipSuccess) e = hipMalloc((void**)&o->d_out, sizeof(double) * 3 * ncols_max);
     if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_out, sizeof(double) * 3 * ncols_max);
     if (e != hipSuccess) {
-        ofdft_cgm_destroy(o);
+        cgm_destroy(o);
         return e == hipErrorOutOfMemory ? OFDFT_ENOMEM : OFDFT_EHIP;
     }
     *out = o;
     return OFDFT_OK;
 }
 
-void ofdft_cgm_destroy(ofdft_cgm* o) {
-    if (!o) return;
-    DeviceScope device_scope_(o->device);
-    for (real* v : {o->x, o->r, o->p, o->q, o->z})
-        if (v) (void)hipFree(v);
-    if (o->d_partial) (void)hipFree(o->d_partial);
-    if (o->d_out) (void)hipFree(o->d_out);
-    if (o->h_out) (void)hipHostFree(o->h_out);
-    delete o;
-}
+}  // namespace
+
+extern "C" {
+
+int ofdft_cgm_create(ofdft_cgm** out, long long n, int ncols_max, int device_id) { return cgm_create(out, n, ncols_max, device_id, &kCgMulti); }
+
+void ofdft_cgm_destroy(ofdft_cgm* o) { cgm_destroy(o); }
 
 const char* ofdft_cgm_last_error(const ofdft_cgm* o) { return o ? o->err : "null handle"; }
 
@@ -382,11 +152,9 @@ int ofdft_cgm_start(ofdft_cgm* o, const void* phi_dev, const void* b_dev, long l
     hipStream_t st = (hipStream_t)stream;
     if (!o) return OFDFT_EINVAL;
     if (!phi_dev || !b_dev || !(rtol >= 0.0) || maxiter < 1) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: null argument, negative rtol or maxiter < 1");
-    if (ncols < 1 || ncols > o->ncols_max) {
-        std::snprintf(o->err, sizeof(o->err), "ofdft_cgm_start: ncols = %d is outside 1 .. %d, the ncols_max of this handle (at most OFDFT_MULTI_MAX = %d)",
-                      ncols, o->ncols_max, kCgmMax);
-        return OFDFT_EINVAL;
-    }
+    if (ncols < 1 || ncols > o->ncols_max)
+        return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: ncols = %d is outside 1 .. %d, the ncols_max of this handle (at most OFDFT_MULTI_MAX = %d)",
+                     ncols, o->ncols_max, kCgmMax);
     if (b_stride < o->n) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: b_stride is below the points of a column");
     DeviceScope device_scope_(o->device);
     CGM_TRY(o, device_scope_.err);
@@ -404,7 +172,7 @@ int ofdft_cgm_start(ofdft_cgm* o, const void* phi_dev, const void* b_dev, long l
     for (int c = 0; c < ncols; ++c)
         for (int s = 0; s < 3; ++s) s3[c][s] = o->h_out[3 * c + s];
     const double S = s3[0][1];
-    if (!(S > 0.0)) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_start: phi is zero everywhere");
+    if (!(S > 0.0)) return mfail(o, OFDFT_EINVAL, "%s_start: phi is zero everywhere", o->w->pfx);
     CgmCols cols{};
     for (int c = 0; c < ncols; ++c) cols.a[c] = (real)(s3[c][2] / S);
     cols.active = (1u << ncols) - 1u;
@@ -436,21 +204,25 @@ int ofdft_cgm_step(ofdft_cgm* o, const void* phi_dev, const double* p_dot_q, con
     hipStream_t st = (hipStream_t)stream;
     if (!o) return OFDFT_EINVAL;
     if (!phi_dev || !p_dot_q || !phi_dot_q || !running) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_step: null argument");
-    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: ofdft_cgm_start has not been called");
-    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: every column has ended (ofdft_cgm_status)");
+    const CgWords& w = *o->w;
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "%s_step: %s_start has not been called", w.pfx, w.pfx);
+    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "%s_step: %s ended (%s_status)", w.pfx, w.all_have, w.pfx);
     if (o->pre && !o->dir_ready)
-        return mfail(o, OFDFT_ESTATE, "ofdft_cgm_step: preconditioned mode, and ofdft_cgm_direction has not formed the directions of this step");
+        return mfail(o, OFDFT_ESTATE, "%s_step: preconditioned mode, and %s_direction has not formed the %s of this step", w.pfx, w.pfx, w.directions);
     DeviceScope device_scope_(o->device);
     CGM_TRY(o, device_scope_.err);
     const real* phi = (const real*)phi_dev;
     const int blocks = cgm_blocks(o);
     CgmCols up{};
+    bool copied = false;
     for (int c = 0; c < o->ncols; ++c) {
         ofdft_cgm::Col& k = o->col[c];
         if (k.reason != OFDFT_CG_RUNNING) continue;
         if (!(p_dot_q[c] > 0.0)) {          // non-positive curvature (or NaN): x stays; before the first update x = p, the steepest descent step
-            if (k.iters == 0)
+            if (k.iters == 0) {
                 CGM_TRY(o, hipMemcpyAsync(o->x + c * o->ld, o->p + c * o->ld, sizeof(real) * (size_t)o->n, hipMemcpyDeviceToDevice, st));
+                copied = true;
+            }
             k.reason = OFDFT_CG_CURVATURE;
             continue;
         }
@@ -482,7 +254,7 @@ int ofdft_cgm_step(ofdft_cgm* o, const void* phi_dev, const double* p_dot_q, con
         }
         if (dir.active)
             hipLaunchKernelGGL(cgm_direction_kernel, dim3(blocks, o->ncols), dim3(256), 0, st, phi, (const real*)o->r, dir, o->p, o->ld, o->n);
-    } else {
+    } else if (copied) {
         CGM_TRY(o, hipStreamSynchronize(st));      // (only first-step copies x = p were queued)
     }
     CGM_TRY(o, hipGetLastError());
@@ -491,15 +263,19 @@ int ofdft_cgm_step(ofdft_cgm* o, const void* phi_dev, const double* p_dot_q, con
 }
 
 // preconditioned mode, between the update sweep of one step and the product of the next: with z_c = M^-1 r_c in place for every
-// running column, rho_c, beta_c and p_c = P z_c + beta_c p_c as ofdft_cg_direction forms them.  One synchronisation.
+// running column, rho_c = r_c.P z_c = r_c.z_c - (phi.r_c)(phi.z_c) / S, beta_c = rho_c / rho_c_old (0 after the start) and
+// p_c = P z_c + beta_c p_c.  One synchronisation.
 int ofdft_cgm_direction(ofdft_cgm* o, const void* phi_dev, double* info_host, int* running, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!o) return OFDFT_EINVAL;
     if (!phi_dev || !running) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_direction: null argument");
-    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: ofdft_cgm_start has not been called");
-    if (!o->pre) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: the solve runs in plain mode (ofdft_cgm_set_preconditioned before ofdft_cgm_start)");
-    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: every column has ended (ofdft_cgm_status)");
-    if (o->dir_ready) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_direction: the directions of this step are already formed (ofdft_cgm_step)");
+    const CgWords& w = *o->w;
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "%s_direction: %s_start has not been called", w.pfx, w.pfx);
+    if (!o->pre)
+        return mfail(o, OFDFT_ESTATE, "%s_direction: the solve runs in plain mode (%s_set_preconditioned before %s_start)", w.pfx, w.pfx, w.pfx);
+    if (!cgm_running(o)) return mfail(o, OFDFT_ESTATE, "%s_direction: %s ended (%s_status)", w.pfx, w.all_have, w.pfx);
+    if (o->dir_ready)
+        return mfail(o, OFDFT_ESTATE, "%s_direction: the %s of this step %s already formed (%s_step)", w.pfx, w.directions, w.are, w.pfx);
     DeviceScope device_scope_(o->device);
     CGM_TRY(o, device_scope_.err);
     const real* phi = (const real*)phi_dev;
@@ -553,7 +329,7 @@ int ofdft_cgm_direction(ofdft_cgm* o, const void* phi_dev, double* info_host, in
 int ofdft_cgm_solution(ofdft_cgm* o, void* x_out_dev, long long stride, void* stream) {
     if (!o) return OFDFT_EINVAL;
     if (!x_out_dev) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_solution: null argument");
-    if (!o->started) return mfail(o, OFDFT_ESTATE, "ofdft_cgm_solution: ofdft_cgm_start has not been called");
+    if (!o->started) return mfail(o, OFDFT_ESTATE, "%s_solution: %s_start has not been called", o->w->pfx, o->w->pfx);
     if (stride < o->n) return mfail(o, OFDFT_EINVAL, "ofdft_cgm_solution: stride is below the points of a column");
     DeviceScope device_scope_(o->device);
     CGM_TRY(o, device_scope_.err);
@@ -569,6 +345,60 @@ int ofdft_cgm_status(const ofdft_cgm* o, int col, int* iterations, int* reason, 
     if (reason) *reason = k.reason;
     if (rel_residual) *rel_residual = k.bb > 0.0 ? std::sqrt(k.rr / k.bb) : 0.0;
     return OFDFT_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================================================
+// One solve (include/ofdft_hip.h): the handle is the solver above with ncols_max = 1, the entries translate the arguments.  The
+// argument checks stay here: OFDFT_EINVAL before any device work, and without a message.
+struct ofdft_cg : ofdft_cgm {};
+
+extern "C" {
+
+int ofdft_cg_create(ofdft_cg** out, long long n, int device_id) { return cgm_create(out, n, 1, device_id, &kCgOne); }
+
+void ofdft_cg_destroy(ofdft_cg* o) { cgm_destroy(o); }
+
+const char* ofdft_cg_last_error(const ofdft_cg* o) { return ofdft_cgm_last_error(o); }
+
+int ofdft_cg_start(ofdft_cg* o, const void* phi_dev, const void* b_dev, double rtol, int maxiter, double* info_host, void* stream) {
+    if (!o || !phi_dev || !b_dev || !(rtol >= 0.0) || maxiter < 1) return OFDFT_EINVAL;
+    return ofdft_cgm_start(o, phi_dev, b_dev, o->n, 1, rtol, maxiter, info_host, stream);
+}
+
+int ofdft_cg_vectors(ofdft_cg* o, void** x_dev, void** r_dev, void** p_dev, void** q_dev) {
+    return ofdft_cgm_vectors(o, x_dev, r_dev, p_dev, q_dev, nullptr);
+}
+
+int ofdft_cg_step(ofdft_cg* o, const void* phi_dev, double p_dot_q, double phi_dot_q, int* reason, void* stream) {
+    if (!o || !phi_dev || !reason) return OFDFT_EINVAL;
+    int running;
+    const int rc = ofdft_cgm_step(o, phi_dev, &p_dot_q, &phi_dot_q, &running, stream);
+    if (rc == OFDFT_OK) *reason = o->col[0].reason;
+    return rc;
+}
+
+int ofdft_cg_set_preconditioned(ofdft_cg* o, int on) { return ofdft_cgm_set_preconditioned(o, on); }
+
+int ofdft_cg_z(ofdft_cg* o, void** z_dev) { return ofdft_cgm_z(o, z_dev); }
+
+int ofdft_cg_direction(ofdft_cg* o, const void* phi_dev, double* info_host, int* reason, void* stream) {
+    if (!o || !phi_dev || !reason) return OFDFT_EINVAL;
+    int running;
+    const int rc = ofdft_cgm_direction(o, phi_dev, info_host, &running, stream);
+    if (rc == OFDFT_OK) *reason = o->col[0].reason;
+    return rc;
+}
+
+// x of the solve, copied to the caller's array (the stream's order; no wait)
+int ofdft_cg_solution(ofdft_cg* o, void* x_out_dev, void* stream) {
+    if (!o || !x_out_dev) return OFDFT_EINVAL;
+    return ofdft_cgm_solution(o, x_out_dev, o->n, stream);
+}
+
+int ofdft_cg_status(const ofdft_cg* o, int* iterations, int* reason, double* rel_residual) {
+    return ofdft_cgm_status(o, 0, iterations, reason, rel_residual);
 }
 
 }  // extern "C"

@@ -49,6 +49,43 @@ const char* hvp_refusal(ofdft_ctx* c, HvpCaller caller) {
     return nullptr;
 }
 
+// The spectral stage of a product, single- or multi-column: one item per transform -- real input (also the head kernel's output),
+// spectrum, operator, real output -- run in the order added.
+struct SpecStage {
+    const real* fin[kHvpMultiSpectra];
+    cplx* spec[kHvpMultiSpectra];
+    real* fout[kHvpMultiSpectra];
+    int op[kHvpMultiSpectra];
+    int ns = 0;
+    void add(const real* in, cplx* s, int o, real* out) {
+        fin[ns] = in;
+        spec[ns] = s;
+        fout[ns] = out;
+        op[ns++] = o;
+    }
+    // forward batches of kBsBatch, every spectrum times its operator in one launch (`name` in the profile), inverse batches
+    int run(ofdft_ctx* c, const TermScalars& ts, const char* name, hipStream_t st) {
+        if (!ns) return 0;
+        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
+            if (int rc = rfftn_internal_multi(c, fin + b0, spec + b0, std::min(kBsBatch, ns - b0), st)) return rc;
+        HvmSpecArgs sa{};
+        for (int j = 0; j < ns; ++j) {
+            sa.s[j] = spec[j];
+            sa.op[j] = (unsigned char)op[j];
+            if (op[j] == SPEC_LINDHARD) sa.lindhard = 1;
+        }
+        sa.ns = ns;
+        sa.kg = c->kg;
+        sa.pref = ts.wt_pref;
+        sa.inv2kf = ts.wt_inv2kf;
+        OFDFT_LAUNCH(c, st, name, hvm_spec_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, sa);
+        const double inv_n = 1.0 / (double)c->npts;
+        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
+            if (int rc = irfftn_internal_multi(c, spec + b0, fout + b0, std::min(kBsBatch, ns - b0), inv_n, st)) return rc;
+        return 0;
+    }
+};
+
 // `first` = n (or phi), `dir` = w (or d), `out` = hv (or H d before the shift).  The caller has run begin_call and the argument checks.
 int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double* quad_terms, bool reuse, HvpChi* chi, hipStream_t st) {
     const unsigned mask = c->mask;
@@ -72,18 +109,12 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
     const TermScalars ts = term_scalars(c, nel);
     const bool two = has_wt && ts.nlp.two;
 
-    // one item per transform: real input (also the head kernel's output), spectrum, operator, real output
-    const real* fin[kHvpMaxSpectra];
-    cplx* spec[kHvpMaxSpectra];
-    real* fout[kHvpMaxSpectra];
-    int op[kHvpMaxSpectra];
-    int ns = 0;
+    SpecStage stage;
     real *vh = nullptr, *lap = nullptr, *dlap = nullptr, *A = nullptr, *Cb = nullptr, *B = nullptr, *Ca = nullptr;
     auto item = [&](const real* in, const char* sname, int o, real* out_) -> int {
-        if (int rc = spec_ws(c, sname, &spec[ns])) return rc;
-        fin[ns] = in;
-        fout[ns] = out_;
-        op[ns++] = o;
+        cplx* s;
+        if (int rc = spec_ws(c, sname, &s)) return rc;
+        stage.add(in, s, o, out_);
         return 0;
     };
     if (has_h || (chi && has_gga))
@@ -258,23 +289,7 @@ int hvp_core(ofdft_ctx* c, const real* first, const real* dir, real* out, double
                 if (int rc = fetch_partials(c, wblocks, kHvpWgcScalars, wgc_sum, st)) return rc;
         }
     }
-    if (ns) {
-        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
-            if (int rc = rfftn_internal_multi(c, fin + b0, spec + b0, std::min(kBsBatch, ns - b0), st)) return rc;
-        HvpSpecArgs sa{};
-        for (int j = 0; j < ns; ++j) {
-            sa.s[j] = spec[j];
-            sa.op[j] = op[j];
-        }
-        sa.ns = ns;
-        sa.lindhard = has_wt ? 1 : 0;
-        sa.kg = c->kg;
-        sa.pref = ts.wt_pref;
-        sa.inv2kf = ts.wt_inv2kf;
-        OFDFT_LAUNCH(c, st, "hvp_spec", hvp_spec_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, sa);
-        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
-            if (int rc = irfftn_internal_multi(c, spec + b0, fout + b0, std::min(kBsBatch, ns - b0), inv_n, st)) return rc;
-    }
+    if (int rc = stage.run(c, ts, "hvp_spec", st)) return rc;
     HvpChiCombineArgs ca{};
     ca.n = den;
     ca.w = w;
@@ -404,51 +419,6 @@ int ofdft_hessian_vector_chi(ofdft_ctx* c, const void* chi_dev, const void* dir_
     return OFDFT_OK;
 }
 
-// z = irfftn(rfftn(r) / (k^2 + kappa2)): the kinetic preconditioner of the conjugate gradients (include/ofdft_hip.h).
-// The solver calls it between products that run with reuse_density = 1, so it goes round begin_call, like the first-order ion
-// entries (engine_ions_stress.inc.h): hvp_valid and hvp_chi_S stay, which is sound because the one workspace it takes is the
-// spectrum "s0", transient in every product, and no "hv:*" field.
-int ofdft_precondition(ofdft_ctx* c, const void* r_dev, void* z_dev, double kappa2, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!c) return OFDFT_EINVAL;
-    OFDFT_ON_DEVICE(c, c->device);
-    if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "ofdft_precondition is served by single-GPU contexts: slab-decomposed contexts have no preconditioner");
-    if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
-    if (!r_dev || !z_dev) return fail(c, OFDFT_EINVAL, "null argument");
-    if (!(kappa2 > 0.0) || !std::isfinite(kappa2)) return fail(c, OFDFT_EINVAL, "ofdft_precondition: kappa2 must be positive and finite");
-    if (z_dev == r_dev) return fail(c, OFDFT_EINVAL, "ofdft_precondition: z_dev must not be r_dev (the transform is not in place)");
-    const real* r = (const real*)r_dev;
-    real* z = (real*)z_dev;
-    const double inv_n = 1.0 / (double)c->npts;
-    const MixScale<SPEC_SCREENED> mix{c->kg, (real)kappa2, (real)0.0};
-    cplx* s0;
-    if (int rc = spec_ws(c, "s0", &s0)) return rc;
-    if (c->fast && !c->force_unfused) {            // z + y | x with the multiply inside | y + z: five spectrum passes
-        if (int rc = fwd_zy(c, r, s0, st)) return rc;
-        XfIo io{};
-        io.in[0] = s0;
-        io.out[0] = s0;
-        if (int rc = xfused<1, 1>(c, io, mix, st, "xfused_pre")) return rc;
-        if (int rc = inv_yz(c, s0, z, inv_n, st)) return rc;
-    } else if (bluestein_xmix_ok(c) && !c->force_unfused) {      // chirp-z extents: the same shape around the x-mix kernel
-        const real* in[1] = {r};
-        cplx* sp[1] = {s0};
-        real* out[1] = {z};
-        if (int rc = bluestein_fwd_zy_multi(c, in, sp, 1, st)) return rc;
-        if (int rc = bluestein_xmix<1, 1>(c, sp, sp, mix, st)) return rc;
-        if (int rc = bluestein_inv_yz_multi(c, sp, out, 1, inv_n, st)) return rc;
-    } else {                                       // forward, multiply, inverse: seven passes
-        if (int rc = rfftn_internal(c, r, s0, st)) return rc;
-        OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_SCREENED>), dim3(grid_for(c->g.total)), dim3(256), 0, (const cplx*)s0, s0, c->kg,
-                     (real)kappa2, (real)0.0);
-        if (int rc = irfftn_internal(c, s0, z, inv_n, st)) return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipGetLastError());
-    if (c->profiling) prof_collect(c);
-    return OFDFT_OK;
-}
-
 // ---- several columns per call (include/ofdft_hip.h) ------------------------------------------------------------
 namespace {
 
@@ -524,7 +494,6 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
     const bool has_h = mask & OFDFT_HARTREE, has_vw = mask & OFDFT_VW, has_wt = mask & OFDFT_WT_NL;
     const TermScalars ts = term_scalars(c, n_electrons);
     const bool two = has_wt && ts.nlp.two;
-    const double inv_n = 1.0 / (double)npts;
 
     // a_j = phi.d_j of every column and S: one sweep, one fetch
     const int blocks = grid_for(npts / 2 + 1, kRedThreads, kRedBlocks);
@@ -535,18 +504,9 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
     if (!(S > 0.0)) return fail(c, OFDFT_EINVAL, "%s: chi is zero everywhere", who);
     const double cs = n_electrons / (S * c->dV), c2 = 2.0 * cs * c->dV;
 
-    // one item per transform, the density-only ones first
-    const real* fin[kHvpMultiSpectra];
-    cplx* spec[kHvpMultiSpectra];
-    real* fout[kHvpMultiSpectra];
-    int op[kHvpMultiSpectra];
-    int ns = 0;
-    auto item = [&](real* field, cplx* s, int o) {
-        fin[ns] = field;
-        spec[ns] = s;
-        fout[ns] = field;
-        op[ns++] = o;
-    };
+    // the density-only items first; every field is transformed in place
+    SpecStage stage;
+    auto item = [&](real* field, cplx* s, int o) { stage.add(field, s, o, field); };
     real *lap = nullptr, *A = nullptr, *B = nullptr;
     real *vh[kMultiMax] = {}, *dlap[kMultiMax] = {}, *Cb[kMultiMax] = {}, *Ca[kMultiMax] = {};
     cplx* s;
@@ -593,7 +553,7 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
             }
         }
     }
-    if (ns) {
+    if (stage.ns) {
         HvmHeadArgs ha{};
         ha.phi = phi;
         ha.d = d;
@@ -614,22 +574,8 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
         ha.be = ts.nlp.be;
         ha.flags = (has_vw ? HVP_VW : 0) | (has_wt ? HVP_WT : 0) | (two ? HVP_WT2 : 0) | (reuse ? HVP_REUSE : 0);
         HVM_DISPATCH(ncols, OFDFT_LAUNCH(c, st, "hvm_head", hvm_head_kernel<kNC>, dim3(grid_for(npts / 2 + 1)), dim3(256), 0, ha));
-        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
-            if (int rc = rfftn_internal_multi(c, fin + b0, spec + b0, std::min(kBsBatch, ns - b0), st)) return rc;
-        HvmSpecArgs sa{};
-        for (int j = 0; j < ns; ++j) {
-            sa.s[j] = spec[j];
-            sa.op[j] = (unsigned char)op[j];
-        }
-        sa.ns = ns;
-        sa.lindhard = has_wt ? 1 : 0;
-        sa.kg = c->kg;
-        sa.pref = ts.wt_pref;
-        sa.inv2kf = ts.wt_inv2kf;
-        OFDFT_LAUNCH(c, st, "hvm_spec", hvm_spec_kernel, dim3(grid_for(c->g.total)), dim3(256), 0, sa);
-        for (int b0 = 0; b0 < ns; b0 += kBsBatch)
-            if (int rc = irfftn_internal_multi(c, spec + b0, fout + b0, std::min(kBsBatch, ns - b0), inv_n, st)) return rc;
     }
+    if (int rc = stage.run(c, ts, "hvm_spec", st)) return rc;
     HvmCombineArgs ca{};
     ca.phi = phi;
     ca.d = d;
@@ -677,24 +623,24 @@ int ofdft_hessian_vector_chi_multi(ofdft_ctx* c, const void* chi_dev, const void
     return OFDFT_OK;
 }
 
-// z_j = irfftn(rfftn(r_j) / (k^2 + kappa2)) for ncols columns: the pipelines of ofdft_precondition, `kBsBatch` columns at a time where a
-// pass takes several fields (the chirp-z helpers), one column per launch through the fused radix passes, one synchronisation at the
-// end.  Like the single-column entry it goes round begin_call; its spectra ("s0", "s0#1", ...) are transient in every product.
-int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride, void* z_dev, long long z_stride, int ncols, double kappa2,
-                             void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!c) return OFDFT_EINVAL;
-    OFDFT_ON_DEVICE(c, c->device);
-    const char* who = "ofdft_precondition_multi";
+// z_j = irfftn(rfftn(r_j) / (k^2 + kappa2)) for ncols columns: the kinetic preconditioner of the conjugate gradients
+// (include/ofdft_hip.h).  The solver calls it between products that run with reuse_density = 1, so the entries go
+// round begin_call, like the first-order ion entries (engine_ions_stress.inc.h): hvp_valid and hvp_chi_S stay, which is sound
+// because the workspaces it takes are the spectra "s0", "s0#1", ..., transient in every product, and no "hv:*" field.
+namespace {
+
+// the checks both entries share; `who` names the entry
+int precondition_checks(ofdft_ctx* c, const char* who, const void* r_dev, const void* z_dev) {
     if (c->nranks > 1) return fail(c, OFDFT_EINVAL, "%s is served by single-GPU contexts: slab-decomposed contexts have no preconditioner", who);
     if (!c->cell_set) return fail(c, OFDFT_ESTATE, "ofdft_set_cell has not been called");
     if (!r_dev || !z_dev) return fail(c, OFDFT_EINVAL, "null argument");
-    if (int rc = multi_checks(c, who, ncols, r_stride, z_stride)) return rc;
-    if (!(kappa2 > 0.0) || !std::isfinite(kappa2)) return fail(c, OFDFT_EINVAL, "%s: kappa2 must be positive and finite", who);
-    const real* r = (const real*)r_dev;
-    real* z = (real*)z_dev;
-    if (ranges_overlap(r, (ncols - 1) * r_stride + c->npts, z, (ncols - 1) * z_stride + c->npts))
-        return fail(c, OFDFT_EINVAL, "%s: z_dev overlaps r_dev (the transform is not in place)", who);
+    return 0;
+}
+bool kappa2_ok(double kappa2) { return kappa2 > 0.0 && std::isfinite(kappa2); }
+
+// The three pipelines, `kBsBatch` columns at a time where a pass takes several fields (the chirp-z helpers), one column per launch
+// through the fused radix passes; one synchronisation at the end.  One column enqueues one transform's launches.
+int precondition_columns(ofdft_ctx* c, const real* r, long long r_stride, real* z, long long z_stride, int ncols, double kappa2, hipStream_t st) {
     const double inv_n = 1.0 / (double)c->npts;
     const MixScale<SPEC_SCREENED> mix{c->kg, (real)kappa2, (real)0.0};
     cplx* sp[kBsBatch];
@@ -708,7 +654,7 @@ int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride
             in[a] = r + (j0 + a) * r_stride;
             out[a] = z + (j0 + a) * z_stride;
         }
-        if (c->fast && !c->force_unfused) {
+        if (c->fast && !c->force_unfused) {            // z + y | x with the multiply inside | y + z: five spectrum passes
             for (int a = 0; a < nb; ++a) {
                 if (int rc = fwd_zy(c, in[a], sp[a], st)) return rc;
                 XfIo io{};
@@ -717,12 +663,12 @@ int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride
                 if (int rc = xfused<1, 1>(c, io, mix, st, "xfused_pre")) return rc;
                 if (int rc = inv_yz(c, sp[a], out[a], inv_n, st)) return rc;
             }
-        } else if (bluestein_xmix_ok(c) && !c->force_unfused) {
+        } else if (bluestein_xmix_ok(c) && !c->force_unfused) {      // chirp-z extents: the same shape around the x-mix kernel
             if (int rc = bluestein_fwd_zy_multi(c, in, sp, nb, st)) return rc;
             for (int a = 0; a < nb; ++a)
                 if (int rc = bluestein_xmix<1, 1>(c, sp + a, sp + a, mix, st)) return rc;
             if (int rc = bluestein_inv_yz_multi(c, sp, out, nb, inv_n, st)) return rc;
-        } else {
+        } else {                                       // forward, multiply, inverse: seven passes
             if (int rc = rfftn_internal_multi(c, in, sp, nb, st)) return rc;
             for (int a = 0; a < nb; ++a)
                 OFDFT_LAUNCH(c, st, "spec_scale", (spec_scale_kernel<SPEC_SCREENED>), dim3(grid_for(c->g.total)), dim3(256), 0, (const cplx*)sp[a],
@@ -734,4 +680,30 @@ int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride
     HIP_TRY(c, hipGetLastError());
     if (c->profiling) prof_collect(c);
     return OFDFT_OK;
+}
+
+}  // namespace
+
+int ofdft_precondition(ofdft_ctx* c, const void* r_dev, void* z_dev, double kappa2, void* stream) {
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    if (int rc = precondition_checks(c, "ofdft_precondition", r_dev, z_dev)) return rc;
+    if (!kappa2_ok(kappa2)) return fail(c, OFDFT_EINVAL, "ofdft_precondition: kappa2 must be positive and finite");
+    if (z_dev == r_dev) return fail(c, OFDFT_EINVAL, "ofdft_precondition: z_dev must not be r_dev (the transform is not in place)");
+    return precondition_columns(c, (const real*)r_dev, c->npts, (real*)z_dev, c->npts, 1, kappa2, (hipStream_t)stream);
+}
+
+int ofdft_precondition_multi(ofdft_ctx* c, const void* r_dev, long long r_stride, void* z_dev, long long z_stride, int ncols, double kappa2,
+                             void* stream) {
+    if (!c) return OFDFT_EINVAL;
+    OFDFT_ON_DEVICE(c, c->device);
+    const char* who = "ofdft_precondition_multi";
+    const real* r = (const real*)r_dev;
+    real* z = (real*)z_dev;
+    if (int rc = precondition_checks(c, who, r_dev, z_dev)) return rc;
+    if (int rc = multi_checks(c, who, ncols, r_stride, z_stride)) return rc;
+    if (!kappa2_ok(kappa2)) return fail(c, OFDFT_EINVAL, "%s: kappa2 must be positive and finite", who);
+    if (ranges_overlap(r, (ncols - 1) * r_stride + c->npts, z, (ncols - 1) * z_stride + c->npts))
+        return fail(c, OFDFT_EINVAL, "%s: z_dev overlaps r_dev (the transform is not in place)", who);
+    return precondition_columns(c, r, r_stride, z, z_stride, ncols, kappa2, (hipStream_t)stream);
 }

@@ -8,7 +8,6 @@
 
 namespace ofdft {
 
-constexpr int kHvpMaxSpectra = 7;      // w | sqrt n, d sqrt n | n^beta, n^(beta-1) w | n^alpha, n^(alpha-1) w
 constexpr int kHvpScalars = 12;        // per-term sums of w hv_t, indexed by the term's bit position (ion_electron .. pbe_c)
 constexpr int kHvpCombineScalars = 10; // ... of which the combine kernel reduces ion_electron .. chachiyo_c; pbe_x, pbe_c: the GGA mid kernel
 constexpr int kHvpGgaScalars = 2;
@@ -108,33 +107,6 @@ static __global__ void hvp_head_kernel(Args a) {
         if (wt2) {
             if (dens) a.pa[i] = p.pa;
             a.paw[i] = p.paw;
-        }
-    }
-}
-
-// ---- spectral: every spectrum of the call times its operator, in place; k, eta and the Lindhard kernel once per k-point
-struct HvpSpecArgs {
-    cplx* s[kHvpMaxSpectra];
-    int op[kHvpMaxSpectra];      // SPEC_HARTREE: 4 pi / k^2 (0 at k = 0), SPEC_LAPLACE: -k^2, SPEC_LINDHARD: pref (1 / G^-1(eta) - 3 eta^2 - 1)
-    int ns, lindhard;            // lindhard: some spectrum takes the kernel
-    KGeom kg;
-    real pref, inv2kf;           // term_scalars: wt_pref, wt_inv2kf
-};
-static __global__ void hvp_spec_kernel(HvpSpecArgs a) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.kg.g.total; i += (long long)gridDim.x * blockDim.x) {
-        real kx, ky, kz, k2;
-        kvec(a.kg, i, kx, ky, kz, k2);
-        real f[3];
-        f[SPEC_HARTREE] = (k2 != 0.0) ? 4.0 * kPiR / k2 : 0.0;                                    // functionals.py:67-70
-        f[SPEC_LAPLACE] = -k2;                                                                    // functional_tools.py:227
-        f[SPEC_LINDHARD] = a.lindhard ? a.pref * lindhard_shape((k2 != 0.0) ? sqrt(k2) * a.inv2kf : 0.0) : 0.0;   // functionals.py:637-638,648
-#pragma unroll
-        for (int j = 0; j < kHvpMaxSpectra; ++j) {
-            if (j < a.ns) {
-                const real fj = a.op[j] == SPEC_HARTREE ? f[SPEC_HARTREE] : (a.op[j] == SPEC_LAPLACE ? f[SPEC_LAPLACE] : f[SPEC_LINDHARD]);
-                const cplx v = a.s[j][i];
-                a.s[j][i] = mkc(v.x * fj, v.y * fj);
-            }
         }
     }
 }
@@ -666,13 +638,14 @@ static __global__ void hvm_head_kernel(HvmHeadArgs a) {
     }
 }
 
-// ---- spectral: every spectrum of every column times its operator, in place; k, eta and the Lindhard kernel once per k-point
+// ---- spectral: every spectrum of the call (single-column products too: engine_hvp.inc.h, SpecStage) times its operator, in place;
+// k, eta and the Lindhard kernel once per k-point
 struct HvmSpecArgs {
     cplx* s[kHvpMultiSpectra];
-    unsigned char op[kHvpMultiSpectra + 1];
-    int ns, lindhard;
+    unsigned char op[kHvpMultiSpectra + 1];      // SPEC_HARTREE: 4 pi / k^2 (0 at k = 0), SPEC_LAPLACE: -k^2, SPEC_LINDHARD: pref (1 / G^-1(eta) - 3 eta^2 - 1)
+    int ns, lindhard;                            // lindhard: some spectrum takes the kernel
     KGeom kg;
-    real pref, inv2kf;
+    real pref, inv2kf;                           // term_scalars: wt_pref, wt_inv2kf
 };
 static __global__ void hvm_spec_kernel(HvmSpecArgs a) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.kg.g.total; i += (long long)gridDim.x * blockDim.x) {

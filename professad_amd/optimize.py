@@ -526,12 +526,48 @@ def kinetic_kappa2(n_elec, volume):
     return (4.0 / 3.0) * (3.0 * math.pi ** 2 * n_elec / volume) ** (2.0 / 3.0)
 
 
-class HipCgBackend:
+class _HipCgBase:
+    """What the device backends for one column and for several share: the preconditioner setting and its kappa^2, the error check
+    and the release of the handle `_h`.  `_abi` is the prefix of the solver's entries (ofdft_cg or ofdft_cgm)."""
+    _abi = None
+
+    @property
+    def preconditioned(self):
+        return self.precondition is not None
+
+    def set_precondition(self, precondition):
+        """takes effect at the next `start`"""
+        self.precondition = check_precondition(precondition)
+
+    def _kappa2(self, n_elec):
+        return kinetic_kappa2(n_elec, self.eng.volume) if self.precondition == 'auto' else self.precondition
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (what, rc, getattr(self.lib, self._abi + '_last_error')(self._h).decode()))
+
+    def hv(self, den, w):
+        return self.eng.hessian_vector(den, w)
+
+    def close(self):
+        if self._h:
+            getattr(self.lib, self._abi + '_destroy')(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipCgBackend(_HipCgBase):
     """Conjugate gradients for P H P x = b on the device (ofdft_cg_* and ofdft_hessian_vector_chi in libofdft_hip.so; no CPU
     fallback): x, r, p, q live behind the handle, the engine's product reads p and writes q in place.
     `precondition`: None (plain), 'auto' (kappa^2 = (4/3) (3 pi^2 N / vol)^(2/3) from the `n_elec` of each solve) or kappa^2 > 0:
     every iteration then opens with z = F^-1[r^ / (k^2 + kappa^2)] (`ofdft_precondition`) and `ofdft_cg_direction`; `set_precondition`
     changes it between solves."""
+    _abi = 'ofdft_cg'
 
     def __init__(self, engine, precondition=None):
         why = second_order_refusal(engine)
@@ -548,18 +584,6 @@ class HipCgBackend:
         self._check(self.lib.ofdft_cg_vectors(self._h, None, None, C.byref(self._p), C.byref(self._q)), 'ofdft_cg_vectors')
         self._scal = (C.c_double * 5)()
         self._r, self._z = C.c_void_p(0), C.c_void_p(0)
-
-    @property
-    def preconditioned(self):
-        return self.precondition is not None
-
-    def set_precondition(self, precondition):
-        """takes effect at the next `start`"""
-        self.precondition = check_precondition(precondition)
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError('%s failed (%d): %s' % (what, rc, self.lib.ofdft_cg_last_error(self._h).decode()))
 
     def start(self, phi, b, rtol, maxiter):
         e = self.eng
@@ -581,8 +605,7 @@ class HipCgBackend:
     def pre_direction(self, phi, n_elec):
         """preconditioned mode, in front of every product: z = M^-1 r, then p = P z + beta p -> exit reason"""
         e = self.eng
-        kappa2 = kinetic_kappa2(n_elec, e.volume) if self.precondition == 'auto' else self.precondition
-        e._check(self.lib.ofdft_precondition(e._ctx, self._r, self._z, float(kappa2), e._stream()), 'ofdft_precondition')
+        e._check(self.lib.ofdft_precondition(e._ctx, self._r, self._z, float(self._kappa2(n_elec)), e._stream()), 'ofdft_precondition')
         reason = C.c_int(0)
         phi = e._grid_tensor(phi, 'chi')
         self._check(self.lib.ofdft_cg_direction(self._h, _vp(phi), None, C.byref(reason), e._stream()), 'ofdft_cg_direction')
@@ -604,20 +627,6 @@ class HipCgBackend:
         x = torch.empty(self.eng.shape, dtype=self.eng.dtype, device=self.eng._dev_exact)
         self._check(self.lib.ofdft_cg_solution(self._h, C.c_void_p(x.data_ptr()), self.eng._stream()), 'ofdft_cg_solution')
         return x
-
-    def hv(self, den, w):
-        return self.eng.hessian_vector(den, w)
-
-    def close(self):
-        if self._h:
-            self.lib.ofdft_cg_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def solve_projected(backend, phi, g, b, n_elec, rtol, maxiter):
@@ -695,6 +704,24 @@ def _own_backend_only(who, backend, precondition):
         raise ValueError('%s: `precondition` configures the backend the call builds; with `backend` given, set it on that backend' % who)
 
 
+def _response_density(chi, n_elec, dV):
+    """-> (c, n) with n = c chi^2 the density of chi (any scale), sum n dV = n_elec"""
+    c = n_elec / (float((chi * chi).sum()) * dV)
+    return c, c * chi * chi
+
+
+def _response_rhs(chi, c, n, n_elec, dV, dv):
+    """the right-hand side -2 c chi (dv - sum(dv n) dV / N) dV of the response to the perturbation dv"""
+    shift = float((dv * n).sum()) * dV / n_elec
+    return (-2.0 * c * dV) * chi * (dv - shift)
+
+
+def _response_result(b, chi, c, n, n_elec, dV, dv, dchi):
+    """-> (dn, dmu) of the perturbation dv from the solution dchi"""
+    dn = 2.0 * c * chi * dchi
+    return dn, float((n * (b.hv(n, dn) + dv)).sum()) * dV / n_elec
+
+
 def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=None, precondition=None):
     """First-order change of the ground-state density under a perturbation `dv` of the external potential, at the ground state
     `chi` (any scale) of the engine's terms: the implicit derivative of the minimiser, one conjugate-gradient solve with the
@@ -707,14 +734,10 @@ def density_response(engine, chi, n_elec, dv, rtol=1e-10, maxiter=500, backend=N
     _own_backend_only('density_response', backend, precondition)
     b = backend if backend is not None else HipCgBackend(engine, precondition)
     dV = b.dV
-    S = float((chi * chi).sum())
-    c = n_elec / (S * dV)
-    n = c * chi * chi
-    shift = float((dv * n).sum()) * dV / n_elec
-    rhs = (-2.0 * c * dV) * chi * (dv - shift)
+    c, n = _response_density(chi, n_elec, dV)
+    rhs = _response_rhs(chi, c, n, n_elec, dV, dv)
     dchi, iters, reason, rel, nprod = solve_projected(b, chi, None, rhs, n_elec, rtol, maxiter)
-    dn = 2.0 * c * chi * dchi
-    dmu = float((n * (b.hv(n, dn) + dv)).sum()) * dV / n_elec
+    dn, dmu = _response_result(b, chi, c, n, n_elec, dV, dv, dchi)
     if backend is None:
         b.close()
     return dict(dn=dn, dmu=dmu, iterations=iters, rel_residual=rel, reason=reason, hvp_count=nprod)
@@ -737,12 +760,13 @@ def _stack(fields):
     return torch.stack(list(fields)) if isinstance(fields[0], torch.Tensor) else np.stack(list(fields))
 
 
-class HipCgMultiBackend:
+class HipCgMultiBackend(_HipCgBase):
     """`HipCgBackend` for up to `ncols` right-hand sides in lockstep (ofdft_cgm_*, ofdft_hessian_vector_chi_multi and
     ofdft_precondition_multi in libofdft_hip.so; no CPU fallback): the columns of x, r, p, q, z live behind the
     handle, one product call forms q_j = H p_j for all of them.  The methods of `HipCgBackend`, taking a stack `bs` [B, *shape]
     and returning per-column lists.  Not block Krylov: each column is the recurrence a solo solve runs, with its own
     coefficients, exit reason and iteration count; a column that has ended is frozen while the others go on."""
+    _abi = 'ofdft_cgm'
 
     def __init__(self, engine, ncols, precondition=None):
         why = second_order_refusal(engine, gga_missing='batch')
@@ -765,13 +789,6 @@ class HipCgMultiBackend:
         self._scal = (C.c_double * (5 * MULTI_MAX))()
         self._pq, self._phiq = (C.c_double * MULTI_MAX)(), (C.c_double * MULTI_MAX)()
         self.ncols = 0
-
-    preconditioned = HipCgBackend.preconditioned
-    set_precondition = HipCgBackend.set_precondition
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError('%s failed (%d): %s' % (what, rc, self.lib.ofdft_cgm_last_error(self._h).decode()))
 
     def start(self, phi, bs, rtol, maxiter):
         e = self.eng
@@ -800,9 +817,8 @@ class HipCgMultiBackend:
     def pre_direction(self, phi, n_elec):
         """preconditioned mode, in front of every product: z_j = M^-1 r_j, then p_j = P z_j + beta_j p_j -> exit reasons"""
         e = self.eng
-        kappa2 = kinetic_kappa2(n_elec, e.volume) if self.precondition == 'auto' else self.precondition
-        e._check(self.lib.ofdft_precondition_multi(e._ctx, self._r, self._ld, self._z, self._ld, self.ncols, float(kappa2), e._stream()),
-                 'ofdft_precondition_multi')
+        e._check(self.lib.ofdft_precondition_multi(e._ctx, self._r, self._ld, self._z, self._ld, self.ncols, float(self._kappa2(n_elec)),
+                                                   e._stream()), 'ofdft_precondition_multi')
         running = C.c_int(0)
         phi = e._grid_tensor(phi, 'chi')
         self._check(self.lib.ofdft_cgm_direction(self._h, _vp(phi), None, C.byref(running), e._stream()), 'ofdft_cgm_direction')
@@ -829,20 +845,6 @@ class HipCgMultiBackend:
         x = torch.empty((self.ncols,) + tuple(self.eng.shape), dtype=self.eng.dtype, device=self.eng._dev_exact)
         self._check(self.lib.ofdft_cgm_solution(self._h, C.c_void_p(x.data_ptr()), self.eng.npts, self.eng._stream()), 'ofdft_cgm_solution')
         return x
-
-    def hv(self, den, w):
-        return self.eng.hessian_vector(den, w)
-
-    def close(self):
-        if self._h:
-            self.lib.ofdft_cgm_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def solve_projected_multi(backend, phi, bs, n_elec, rtol, maxiter):
@@ -878,20 +880,14 @@ def density_response_multi(engine, chi, n_elec, dvs, rtol=1e-10, maxiter=500, ba
     b = backend if backend is not None else HipCgMultiBackend(engine, B, precondition)
     try:
         dV = b.dV
-        S = float((chi * chi).sum())
-        c = n_elec / (S * dV)
-        n = c * chi * chi
-        rhs = []
-        for j in range(B):
-            shift = float((dvs[j] * n).sum()) * dV / n_elec
-            rhs.append((-2.0 * c * dV) * chi * (dvs[j] - shift))
+        c, n = _response_density(chi, n_elec, dV)
+        rhs = [_response_rhs(chi, c, n, n_elec, dV, dvs[j]) for j in range(B)]
         dchi, iters, reasons, rels, nprod = solve_projected_multi(b, chi, _stack(rhs), n_elec, rtol, maxiter)
-        dn = [2.0 * c * chi * dchi[j] for j in range(B)]
-        dmu = [float((n * (b.hv(n, dn[j]) + dvs[j])).sum()) * dV / n_elec for j in range(B)]
+        dn, dmu = zip(*[_response_result(b, chi, c, n, n_elec, dV, dvs[j], dchi[j]) for j in range(B)])
     finally:
         if backend is None:
             b.close()
-    return dict(dn=_stack(dn), dmu=dmu, iterations=iters, rel_residual=rels, reason=reasons, hvp_count=nprod)
+    return dict(dn=_stack(dn), dmu=list(dmu), iterations=iters, rel_residual=rels, reason=reasons, hvp_count=nprod)
 
 
 def resolve_batch(who, backend, batch):
