@@ -52,8 +52,12 @@ def mix(tab, x):
 
 
 def triple(n, th, e):
-    """(f, f theta, f theta^2 / 2) for f = n^e with its first and second derivatives in n"""
-    f, f1, f2 = n ** e, e * n ** (e - 1), e * (e - 1) * n ** (e - 2)
+    """(f, f theta, f theta^2 / 2) for f = n^e with its first and second derivatives in n.  Where n is not positive f, f' and f'' count
+    as 0, the rule of the device's wgc_triple (hvp_kernels.h): n^(e - 2) is infinite at n = 0 for both exponents, and the point is a
+    zero of chi, which takes no part in the chi-space product."""
+    pos = n > 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f, f1, f2 = (np.where(pos, x, 0) for x in (n ** e, e * n ** (e - 1), e * (e - 1) * n ** (e - 2)))
     h = th * th / 2
     return ([f, f * th, f * h], [f1, f1 * th + f, f1 * h + f * th], [f2, f2 * th + 2 * f1, f2 * h + 2 * f1 * th + f])
 
@@ -117,3 +121,15 @@ def hessian_vector_chi(box, phi, d, g, n_elec, terms, alpha=5 / 6, beta=5 / 6):
         quot = np.where(phi != 0, d * g / phi, 0.0)
     Hd = -(2 * a / S) * g + quot + 2 * c * phi * (dv - dmu) * dV
     return dict(dHd=float((d * Hd).sum()), phiHd=float((phi * Hd).sum()), a=a, S=S, dmu=dmu), Hd
+
+
+class NumpyCgBackend(H.NumpyCgBackend):
+    """hvp_gga_double.NumpyCgBackend over this module's products"""
+
+    def product(self, phi, g, n_elec, reuse):
+        s, self.q = hessian_vector_chi(self.box, phi, self.p, g, n_elec, self.terms, self.al, self.be)
+        self.products += 1
+        return s['dHd'], s['phiHd']
+
+    def hv(self, den, w):
+        return hessian_vector(self.box, den, w, self.terms, self.al, self.be)[1]
